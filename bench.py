@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: corrected bases/s of the MI355X hot path on synthetic dhigh reads (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--len L] [--config 2|3] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--len L] [--config 2|3|5] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of  kmermatcher -> rescorediagonal -> ancient_correction -> ancient_read_assemble  (--config 3, default:
 BASELINE.json configs[2]; with N > 1 configs[3]) or of ancient_correction alone (--config 2: configs[1], 5 M reads) over
@@ -13,7 +14,10 @@ reads (--scaling strong, default).  --scheme exact (default): every rank holds t
 all-gathered) - the result is the single-device one.  --scheme reads: rank r owns reads [r R/N, (r+1) R/N), runs the stages on them
 alone and the per-shard contigs are all-gathered in ONE collective inside the timed step - the north star's wording, but not the
 single-device result (the JSON line says so).  --scaling weak gives every rank its own R-read corpus, seed + rank.
-Rank 0 prints ONE JSON line.  (CDM_BENCH_BACKEND=gloo: the ranks rendezvous over gloo and the library's calls go over a gloo transport
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; --full adds what takes runs of its
+own: cpu_baseline, gpu_module_wall and vs_cpu_baseline (the reference's modules, the device modules and the fused loop on DB files of
+--cpu-reads reads, minutes).  --dump-outputs DIR writes what the last timed step computed, as .npy files (dump_seqdb), before the line.
+(CDM_BENCH_BACKEND=gloo: the ranks rendezvous over gloo and the library's calls go over a gloo transport
 instead of librccl, so that several ranks can share one device - tests/test_gpu_two_ranks.py; RCCL wants a device per rank.)
 """
 import argparse
@@ -125,6 +129,44 @@ def module_walls(n_reads, L, seed, threads):
     return cpu, gpu
 
 
+DUMP_SAMPLE = 1 << 15          # --dump-outputs: sequences of the sample of a larger output DB
+DUMP_LETTERS = 8 << 20         # ... and at most this many letters of it (float32: 32 MB)
+DUMP_SEED = 20260101
+
+
+def dump_seqdb(out_dir, name, db, counts):
+    """--dump-outputs: the sequence DB a caller of the timed path receives (on the device), written to out_dir as float arrays:
+      <name>_counts.npy        float64 [sequences, letters, sequences with wasExtended = 1] + `counts` (the step's other figures)
+      <name>_length_hist.npy   float64, sequences per length over the whole DB
+      <name>_keys / _lengths / _extended / _offsets / _letters.npy   a fixed, seeded sample of the DB in key order: DUMP_SAMPLE
+                               positions of the key-sorted DB (the same ones at the same size), cut to DUMP_LETTERS letters; the
+                               letters as their byte values (float32), sequence i at letters[offsets[i]:offsets[i + 1]]
+    Keyed, not by position: two builds that hand the same records back in another order dump the same arrays."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lens, keys, ext = db.meta()
+    n = len(lens)
+    offs = np.zeros(n, np.uint64)
+    if n:
+        offs[1:] = np.cumsum(lens[:-1].astype(np.uint64) + 1)
+    buf = np.empty(int(lens.astype(np.uint64).sum()) + n, np.uint8)
+    if n:
+        db.download_into(buf, offs)
+    order = np.argsort(keys, kind="stable")
+    pick = order[np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))] if n > DUMP_SAMPLE else order
+    pick = pick[np.cumsum(lens[pick].astype(np.int64)) <= DUMP_LETTERS]
+    sample_offs = np.zeros(len(pick) + 1, np.float64)
+    sample_offs[1:] = np.cumsum(lens[pick].astype(np.float64))
+    letters = np.concatenate([buf[int(offs[i]):int(offs[i]) + int(lens[i])] for i in pick] or [np.zeros(0, np.uint8)])
+    arrays = {"counts": np.array([n, int(lens.astype(np.uint64).sum()), int((ext == 1).sum())] + list(counts), np.float64),
+              "length_hist": np.bincount(lens).astype(np.float64) if n else np.zeros(0, np.float64),
+              "keys": keys[pick].astype(np.float64), "lengths": lens[pick].astype(np.float32), "extended": ext[pick].astype(np.float32),
+              "offsets": sample_offs, "letters": letters.astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, "%s_%s.npy" % (name, k)), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks (before anything touches the GPU) and exit with their code"""
     import socket
@@ -211,6 +253,8 @@ def run_loop_config(args, ctx, capi, cd, dist, rank, world, plan, torch, comm=No
             tb = torch.tensor([total], dtype=torch.float64, device=("cpu" if dist.get_backend() == "gloo" else "cuda"))
             dist.all_reduce(tb)
             total = float(tb.item())
+    if rank == 0 and args.dump_outputs:
+        dump_seqdb(args.dump_outputs, "final", out, (circular,))
     if rank == 0:
         chain_b = sum(ALG_B_PER_BASE.values())
         ach = chain_b * total / dt / 1e9
@@ -245,7 +289,9 @@ def main():
                          "query-sharded stages + all-gathers of the new DBs), bit-identical to one device; reads = every rank runs the stages on its own read shard and "
                          "the contigs are all-gathered (the north star's wording; NOT equivalent to the single-device run: a shard sees 1/N of every pile-up)")
     ap.add_argument("--cpu-reads", type=int, default=10_000_000, help="reads of the sample the reference's modules, the device modules and the fused loop are timed on (same DB files)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline and module-wall figures out")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baseline and the module walls on DB files of --cpu-reads reads (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_seqdb)")
     args = ap.parse_args()
     if args.seed is None:
         args.seed = 2 if args.config == 5 else 1
@@ -374,6 +420,8 @@ def main():
         if args.config == 3 and not exact and gather_info:
             gathered = {"contigs": gather_info["contigs"], "bases": gather_info["bases"], "seconds_per_step": gather_info["seconds"] / max(1, gather_info["calls"]),
                         "inside_timed_region": True}
+    if rank == 0 and args.dump_outputs:
+        dump_seqdb(args.dump_outputs, "corr" if args.config == 2 else "asm", asm, stats)
     if rank == 0:
         k_ms = [m / args.steps for m in kernel_ms]
         step_ms = 1e3 * dt / args.steps
@@ -451,7 +499,7 @@ def main():
         }
         if gathered is not None:
             line["config"]["allgather_contigs"] = gathered
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the module legs start their own processes on this device: everything this process holds there goes first (sequences,
             # results, the library's cache of device blocks, torch's), so that they meet the device a deployment's module meets
             import gc

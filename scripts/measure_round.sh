@@ -6,7 +6,7 @@ tag=${1:-meas}
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
 step() { name=$1; tmo=$2; shift 2; echo "== $name"; start=$(date +%s); timeout -k 10 $tmo "$@" > $O/${tag}_$name.log 2>&1; rc=$?; echo "== $name rc=$rc in $(( $(date +%s) - start ))s"; tail -n 2 $O/${tag}_$name.log | cut -c1-300; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timed out: stopping"; exit $rc; fi; }
 step tests 900 python -m pytest tests -m gpu -x -q
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 cd /tmp && export TMPDIR=/tmp
 step prof3 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_prof3 -o p --output-format csv -- python3 $R/bench.py --no-cpu-baseline
 step prof2 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_prof2 -o p --output-format csv -- python3 $R/bench.py --config 2 --no-cpu-baseline
