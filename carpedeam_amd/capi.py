@@ -63,6 +63,8 @@ EXPORTS = [
     "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kpart_free", "cdm_dev_copy",
     "cdm_seqdb_from_packed_ext", "cdm_seqdb_copy_ext", "cdm_seqdb_export_packed", "cdm_seqdb_import_packed", "cdm_contig_merge", "cdm_cyclecheck", "cdm_seqdb_has_raw", "cdm_seqdb_copy_raw", "cdm_seqdb_attach_raw",
     "cdm_rescore_hamming", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
+    "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
+    "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -83,6 +85,15 @@ class CdmError(RuntimeError):
 
 
 _lib = None
+
+
+class MergeParams(C.Structure):
+    """cdm_merge_params: mergereads' fixed values by default (mergereads.cpp:20-24)"""
+    _fields_ = [("min_overlap", C.c_int), ("max_overlap", C.c_int), ("max_mismatch_density", C.c_float)]
+
+    @classmethod
+    def default(cls):
+        return cls(15, 65, 0.10)
 
 
 def lib():
@@ -122,6 +133,16 @@ def lib():
         l.cdm_seqdb_copy_raw.argtypes = [vp, vp, vp, vp]
         l.cdm_seqdb_attach_raw.argtypes = [vp, vp, vp, vp]
         l.cdm_seqdb_from_packed.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint8, C.POINTER(vp)]
+        l.cdm_pairs_merge.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(MergeParams), C.POINTER(vp)]
+        for f in (l.cdm_pairs_count, l.cdm_pairs_entries, l.cdm_pairs_bytes):
+            f.argtypes = [vp]
+            f.restype = C.c_uint64
+        l.cdm_pairs_kernel_ms.argtypes = [vp]
+        l.cdm_pairs_kernel_ms.restype = C.c_float
+        l.cdm_pairs_download.argtypes = [vp, vp, vp, vp, vp, vp]
+        l.cdm_pairs_to_seqdb.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+        l.cdm_pairs_free.argtypes = [vp]
+        l.cdm_pairs_free.restype = None
         l.cdm_damage_load.argtypes = [vp, C.c_char_p]
         l.cdm_damage_get.argtypes = [vp, vp]
         l.cdm_kmermatch.argtypes = [vp, vp, C.POINTER(KmerParams), C.POINTER(vp)]
@@ -404,6 +425,45 @@ class Ctx:
         h = C.c_void_p()
         _check(lib().cdm_seqdb_upload(self.h, _ptr(data), _ptr(offs), _ptr(lens), _ptr(keys), _ptr(ext), n, C.byref(h)))
         return SeqDb(self, h)
+
+    def merge_pairs(self, pairs, par=None, to_seqdb=False, first_key=0):
+        """mergereads on the device for one batch.  pairs: [((seq1, qual1), (seq2, qual2))] as read (bytes).  Returns (status, entries):
+        status[i] = 1 when pair i was combined; entries = [seq] in mergereads' order (the consensus, or R1 and R2 reverse-complemented) -
+        or, with to_seqdb, a resident SeqDb of them (keys first_key, first_key + 1, ...; wasExtended 1)."""
+        n = len(pairs)
+        blobs = []
+        for side in (0, 1):
+            seqs = [bytes(p[side][0]) for p in pairs]
+            quals = [bytes(p[side][1]) for p in pairs]
+            lens = np.array([len(x) for x in seqs], np.uint32)
+            offs = np.zeros(n, np.uint64)
+            if n > 1:
+                offs[1:] = np.cumsum(lens[:-1].astype(np.uint64))
+            sb = np.frombuffer(b"".join(seqs) + b"\0", np.uint8)
+            qb = np.frombuffer(b"".join(quals) + b"\0", np.uint8)
+            blobs.append((sb, qb, offs, lens))
+        (s1, q1, o1, l1), (s2, q2, o2, l2) = blobs
+        par = par or MergeParams.default()
+        h = C.c_void_p()
+        _check(lib().cdm_pairs_merge(self.h, _ptr(s1), _ptr(q1), _ptr(o1), _ptr(l1), _ptr(s2), _ptr(q2), _ptr(o2), _ptr(l2), n, C.byref(par), C.byref(h)))
+        try:
+            status = np.zeros(n + 1, np.uint8)
+            ne, nb = lib().cdm_pairs_entries(h), lib().cdm_pairs_bytes(h)
+            if to_seqdb:
+                _check(lib().cdm_pairs_download(self.h, h, _ptr(status), None, None, None))
+                d = C.c_void_p()
+                _check(lib().cdm_pairs_to_seqdb(self.h, h, first_key, C.byref(d)))
+                return status[:n], SeqDb(self, d)
+            text = np.zeros(nb + 1, np.uint8)
+            elen = np.zeros(ne + 1, np.uint32)
+            _check(lib().cdm_pairs_download(self.h, h, _ptr(status), None, _ptr(text), _ptr(elen)))
+            raw, out, at = text.tobytes(), [], 0
+            for k in range(ne):
+                out.append(raw[at:at + int(elen[k])])
+                at += int(elen[k]) + 2
+            return status[:n], out
+        finally:
+            lib().cdm_pairs_free(h)
 
     def upload_keyed_seqdb(self, keyed):
         """keyed: dict key -> (payload incl. newline, ext) as mmdb.read_db / load_keyed give it."""

@@ -916,3 +916,52 @@ extern "C" int cdm_extend(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
     if (rc == CDM_OK) stageDone(ctx, 11);
     return rc;
 }
+
+// ---- a sequence DB from text that is on the device already (cdm_pairs_to_seqdb: the merged pairs become the DB the reads loop runs on
+// without a host round trip).  Entry j: text[off[j] .. off[j] + len[j]) = its letters, key first_key + j, wasExtended ext; packed as
+// cdm_seqdb_upload packs.
+namespace {
+__global__ void k_text_words(const uint32_t *__restrict__ entLen, uint64_t n, uint32_t firstKey, uint8_t extValue, uint32_t *__restrict__ len, uint32_t *__restrict__ key,
+                             uint8_t *__restrict__ ext, uint8_t *__restrict__ hasN, uint64_t *__restrict__ words) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    words[i] = i < n ? (entLen[i] + 15) / 16 : 0;
+    if (i < n) { len[i] = entLen[i]; key[i] = firstKey + (uint32_t) i; ext[i] = extValue; hasN[i] = 0; }
+}
+__global__ void k_woff32(const uint64_t *__restrict__ w64, uint64_t n, uint32_t *__restrict__ woff) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n) woff[i] = (uint32_t) w64[i];
+}
+}  // namespace
+int cdm_seqdb_from_device_text(cdm_ctx *ctx, const char *text, const uint64_t *off, const uint32_t *len, uint64_t n, uint32_t firstKey, uint8_t ext, cdm_seqdb **out) {
+    if (n == 0 || n >= 0xFFFFFFFFull) { cdm_set_error("a sequence DB of %llu entries", (unsigned long long) n); return CDM_ERR_UNSUPPORTED; }
+    CDM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    cdm_seqdb *db = nullptr;
+    int rc = cdm_seqdb_alloc(ctx, n, &db);
+    if (rc) return rc;
+    DevBuf<uint64_t> w, wo; DevBuf<unsigned long long> cnt;
+    if (!w.alloc(n + 1) || !wo.alloc(n + 1) || !cnt.alloc(2)) { cdm_seqdb_free(db); cdm_set_error("out of device memory building a sequence DB of %llu entries", (unsigned long long) n); return CDM_ERR_HIP; }
+    hipLaunchKernelGGL(k_text_words, CDM_GRID((n + 256) / 256, 256), dim3(256), 0, s, len, n, firstKey, ext, db->len, db->key, db->ext, db->hasN, w.p);
+    cdmscan::ScanTemp st;
+    if ((rc = cdmscan::exclusiveScan<uint64_t>(s, st, w.p, wo.p, n + 1)) != CDM_OK) { cdm_seqdb_free(db); return rc; }
+    uint64_t words = 0;
+    hipMemcpyAsync(&words, wo.p + n, 8, hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) { cdm_seqdb_free(db); cdm_set_error("sequence DB from device text: %s", hipGetErrorString(hipGetLastError())); return CDM_ERR_HIP; }
+    if (words >= 0xFFFFFF00ull) { cdm_seqdb_free(db); cdm_set_error("more than 2^32 code words (68 G bases) in one DB"); return CDM_ERR_UNSUPPORTED; }
+    if ((rc = seqdb_alloc_codes(db, words)) != CDM_OK) { cdm_seqdb_free(db); return rc; }
+    hipLaunchKernelGGL(k_woff32, CDM_GRID((n + 256) / 256, 256), dim3(256), 0, s, wo.p, n, db->woff);
+    hipMemsetAsync(cnt.p, 0, 16, s);
+    if (words) hipLaunchKernelGGL(k_pack, CDM_GRID((words + 255) / 256, 256), dim3(256), 0, s, text, off, db->len, db->woff, n, words, db->codes, db->nmask, db->hasN, cnt.p);
+    unsigned long long c[2] = {0, 0};
+    hipMemcpyAsync(c, cnt.p, 16, hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) { cdm_seqdb_free(db); cdm_set_error("sequence DB from device text: %s", hipGetErrorString(hipGetLastError())); return CDM_ERR_HIP; }
+    db->nCount = c[0];
+    if (c[1]) {
+        if ((rc = cdm_seqdb_alloc_raw(db)) != CDM_OK) { cdm_seqdb_free(db); return rc; }
+        hipLaunchKernelGGL(k_pack_raw, CDM_GRID((words + 255) / 256, 256), dim3(256), 0, s, text, off, db->len, db->woff, n, words, db->hasN, db->raw);
+    }
+    if ((rc = seqdbLenStats(ctx, db)) != CDM_OK) { cdm_seqdb_free(db); return rc; }
+    *out = db;
+    return CDM_OK;
+}

@@ -189,6 +189,8 @@ struct cdm_alns {
 
 int cdm_seqdb_alloc_like(cdm_ctx *ctx, const cdm_seqdb *src, cdm_seqdb **out);  // same n/lengths/layout, codes uninitialised
 int cdm_seqdb_alloc(cdm_ctx *ctx, uint64_t n, cdm_seqdb **out);
+// entry j = text[off[j] .. off[j] + len[j]) (device pointers), key first_key + j, wasExtended ext: packed as cdm_seqdb_upload packs (api.hip)
+int cdm_seqdb_from_device_text(cdm_ctx *ctx, const char *text, const uint64_t *off, const uint32_t *len, uint64_t n, uint32_t firstKey, uint8_t ext, cdm_seqdb **out);
 int cdm_seqdb_alloc_raw(cdm_seqdb *db);      // the raw plane for db->words code words (contents undefined)
 // sub-DB: sel[i] (device) = 0xFFFFFFFF drops sequence i, else keeps its first sel[i] letters; extValue < 0 keeps the wasExtended flags
 int cdm_seqdb_select(cdm_ctx *ctx, const cdm_seqdb *db, const uint32_t *sel, int extValue, cdm_seqdb **out);

@@ -7,7 +7,7 @@
  * workflow scripts call every module as "$MMSEQS" <module> (data/nuclassemble.sh:105-136, data/guidedNuclAssemble.sh:35-201,
  * lib/mmseqs/data/workflow/linclust.sh:24-87).  With argv[0] pointing back here, `carpedeam ancient_assemble reads.fq out.fa tmp
  * --ancient-damage dhigh` runs the reference's own workflow drivers and scripts, and every kmermatcher / rescorediagonal /
- * ancient_correction / ancient_read_assemble / ancient_contig_merge / cyclecheck / createdb / createhdb / convert2fasta call of
+ * ancient_correction / ancient_read_assemble / ancient_contig_merge / cyclecheck / createdb / mergereads / createhdb / convert2fasta call of
  * those scripts comes back through this program and lands on the MI355X.  A module call whose flags the device path does not
  * implement (carpedeam_mi355x exits with status 77 before doing any work) is REFUSED: this program exits with EXIT_FAILURE and the
  * dispatch log gets a "refused <module>" line.  An owned module is never computed by the reference binary: this program has no code
@@ -31,7 +31,7 @@
 #define CDM_EXIT_UNSUPPORTED 77
 
 static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_correction", "ancient_read_assemble", "ancient_contig_merge", "cyclecheck",
-                                    "createdb", "createhdb", "convert2fasta", "ancient_reads_loop",
+                                    "createdb", "createhdb", "convert2fasta", "ancient_reads_loop", "mergereads",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

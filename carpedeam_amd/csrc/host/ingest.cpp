@@ -2,7 +2,8 @@
 //   createdb       FASTA/FASTQ[.gz] -> sequence DB + header DB + .lookup + .source      lib/mmseqs/src/util/createdb.cpp:60-340
 //   convert2fasta  sequence DB + header DB -> FASTA                                     lib/mmseqs/src/util/convert2fasta.cpp
 //   createhdb      "<id> len:<len>[ cycle:<0|1>]" headers for assembled sequences        src/util/createhdb.cpp
-// plus readFastxAsDb, which hands the parsed reads to the device path without going through DB files (ancient_reads_loop).
+// plus readFastxAsDb, which hands the parsed reads to the device path without going through DB files (ancient_reads_loop), and
+// readFastqPair, the two files of a read pair with their qualities (mergereads).
 // The parser follows kseq.h as KSeqWrapper drives it (lib/mmseqs/lib/kseq/kseq.h): a record starts at a line whose first
 // character is '>' or '@'; name = up to the first white space, comment = rest of the line; the sequence is every following line
 // (without line ends) up to a line that starts with '>', '+' or '@'; after '+' as many quality characters as sequence letters
@@ -29,6 +30,10 @@ namespace {
 struct Entries {
     HVec<char> seqBlob, hdrBlob;               // "SEQ\n\0" / "header\n\0" per entry, in input order
     HVec<uint64_t> seqOff, hdrOff; HVec<uint32_t> seqLen, hdrLen, file;
+    // keepQual (mergereads): qualBlob holds each record's quality string at its sequence's offset; hasQual = 0 for a record without
+    // one (FASTA)
+    bool keepQual = false;
+    HVec<char> qualBlob; HVec<uint8_t> hasQual;
 };
 template <typename V> inline void appendBytes(V &v, const char *p, size_t n) {
     if (v.capacity() - v.size() < n) v.reserve(std::max(v.capacity() * 2, v.size() + n + (64u << 20)));
@@ -47,6 +52,7 @@ struct FastxParser {
     bool midLine = false;                       // SEQ / PLUS / QUAL: the current line began in an earlier block
     size_t recSeq = 0, recHdr = 0;              // where the current record's letters / header start in the blobs
     std::string header, qual;
+    bool recHasQual = false;                    // the current record has reached its quality string
     bool invalidEntry = false; size_t invalidAt = 0;
     // parallel parsing of a plain file: a parser owns the records that START in front of `limit` and stops - `stoppedAt` - where the
     // first one behind it starts
@@ -63,13 +69,20 @@ struct FastxParser {
             if (cl > 0) { header.push_back(' '); header.append(h + cs, cl); }
         }
         header.push_back('\n');
-        recSeq = e.seqBlob.size(); recHdr = e.hdrBlob.size();
+        recSeq = e.seqBlob.size(); recHdr = e.hdrBlob.size(); recHasQual = false;
         appendBytes(e.hdrBlob, header.data(), header.size()); e.hdrBlob.push_back('\0');
     }
     bool refused = false;                       // a record kseq returns -2 for: the reading of the file ends there
     void dropRecord() { e.seqBlob.resize(recSeq); e.hdrBlob.resize(recHdr); refused = true; }
     void endRecord() {
         const size_t L = e.seqBlob.size() - recSeq;
+        if (e.keepQual) {
+            const size_t need = recSeq + L + 2;
+            if (e.qualBlob.capacity() < need) e.qualBlob.reserve(std::max(e.qualBlob.capacity() * 2, need + (64u << 20)));
+            e.qualBlob.resize(need);
+            if (recHasQual) memcpy(e.qualBlob.data() + recSeq, qual.data(), L);
+            e.hasQual.push_back(recHasQual);
+        }
         e.seqOff.push_back(recSeq); e.seqLen.push_back((uint32_t) L + 2);
         e.seqBlob.push_back('\n'); e.seqBlob.push_back('\0');
         e.hdrOff.push_back(recHdr); e.hdrLen.push_back((uint32_t) header.size() + 1);
@@ -115,7 +128,7 @@ struct FastxParser {
                 else { seqPiece(p, (size_t) (end - p), eof); p = end; midLine = !eof; }
             } else if (st == PLUS) {
                 const char *nl = (const char *) memchr(p, '\n', (size_t) (end - p));
-                if (nl) { p = nl + 1; st = QUAL; qual.clear(); midLine = false; }
+                if (nl) { p = nl + 1; st = QUAL; qual.clear(); midLine = false; recHasQual = true; }
                 else { if (eof) { dropRecord(); st = STOP; } return (size_t) (end - begin); }      // no quality string: -2
             } else {   // QUAL
                 const size_t L = e.seqBlob.size() - recSeq;
@@ -212,6 +225,8 @@ bool parsePlainParallel(const std::string &path, uint32_t fileIdx, Entries &e) {
             Entries &pe = part[t];
             const size_t span = start[t + 1] - start[t];
             pe.seqBlob.reserve(span + 2); pe.hdrBlob.reserve(span / 2 + 2);
+            pe.keepQual = e.keepQual;
+            if (pe.keepQual) { pe.qualBlob.reserve(span / 2 + 2); pe.hasQual.reserve(span / 128 + 16); }
             const size_t guess = span / 128 + 16;
             pe.seqOff.reserve(guess); pe.hdrOff.reserve(guess); pe.seqLen.reserve(guess); pe.hdrLen.reserve(guess); pe.file.reserve(guess);
             FastxParser ps(pe, fileIdx);
@@ -229,12 +244,17 @@ bool parsePlainParallel(const std::string &path, uint32_t fileIdx, Entries &e) {
         if (e.seqBlob.capacity() < s0 + sb[T]) e.seqBlob.reserve(s0 + sb[T]);
         if (e.hdrBlob.capacity() < h0 + hb[T]) e.hdrBlob.reserve(h0 + hb[T]);
         e.seqBlob.resize(s0 + sb[T]); e.hdrBlob.resize(h0 + hb[T]);
+        if (e.keepQual) { if (e.qualBlob.capacity() < s0 + sb[T]) e.qualBlob.reserve(s0 + sb[T]); e.qualBlob.resize(s0 + sb[T]); e.hasQual.resize(n0 + cnt[T]); }
         e.seqOff.resize(n0 + cnt[T]); e.hdrOff.resize(n0 + cnt[T]); e.seqLen.resize(n0 + cnt[T]); e.hdrLen.resize(n0 + cnt[T]); e.file.resize(n0 + cnt[T]);
 #pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
         for (int t = 0; t < T; t++) {
             const Entries &pe = part[t];
             memcpy(e.seqBlob.data() + s0 + sb[t], pe.seqBlob.data(), pe.seqBlob.size());
             memcpy(e.hdrBlob.data() + h0 + hb[t], pe.hdrBlob.data(), pe.hdrBlob.size());
+            if (e.keepQual) {
+                memcpy(e.qualBlob.data() + s0 + sb[t], pe.qualBlob.data(), std::min(pe.qualBlob.size(), pe.seqBlob.size()));
+                memcpy(e.hasQual.data() + n0 + cnt[t], pe.hasQual.data(), pe.hasQual.size());
+            }
             for (size_t i = 0, k = n0 + cnt[t]; i < pe.seqOff.size(); i++, k++) {
                 e.seqOff[k] = pe.seqOff[i] + s0 + sb[t]; e.hdrOff[k] = pe.hdrOff[i] + h0 + hb[t];
                 e.seqLen[k] = pe.seqLen[i]; e.hdrLen[k] = pe.hdrLen[i]; e.file[k] = fileIdx;
@@ -245,7 +265,8 @@ bool parsePlainParallel(const std::string &path, uint32_t fileIdx, Entries &e) {
     if (getenv("CDM_TIMING")) fprintf(stderr, "  %s: %s\n", path.c_str(), ok ? "parsed by all threads (every stretch start confirmed)" : "parsed serially");
     return ok;
 }
-bool parseFile(const std::string &path, uint32_t fileIdx, Entries &e, std::string *err) {
+// allowEmptyName: a record whose name is empty is read as it stands (kseq has no objection; createdb's header parser has, Util.cpp)
+bool parseFile(const std::string &path, uint32_t fileIdx, Entries &e, std::string *err, bool allowEmptyName = false) {
     if (!getenv("CDM_INGEST_SERIAL") && parsePlainParallel(path, fileIdx, e)) return true;
     BlockReader r;
     if (!r.open(path)) { *err = "Cannot open " + path; return false; }
@@ -265,7 +286,7 @@ bool parseFile(const std::string &path, uint32_t fileIdx, Entries &e, std::strin
         if (last) break;
     }
     if (r.failed) { *err = "Cannot read " + path; return false; }
-    if (ps.invalidEntry) { *err = "Fasta entry " + std::to_string(ps.invalidAt) + " is invalid"; return false; }
+    if (ps.invalidEntry && !allowEmptyName) { *err = "Fasta entry " + std::to_string(ps.invalidAt) + " is invalid"; return false; }
     return true;
 }
 // Util::parseFastaHeader (Util.cpp:173-256): the identifier part of a header
@@ -400,4 +421,28 @@ int createhdbModule(const std::string &seqPath, const std::string &cyclePath, co
     }
     std::vector<OutChunk> chunks; chunks.push_back(std::move(c));
     return mmdbWriteChunks(outPath + "_h", 12, chunks, err) ? 0 : 1;
+}
+
+// The two files of a read pair, parsed at the same time (each with the parser above: plain files by all threads, .gz serially), with
+// their qualities.  The module's threads are split between the two files, so the two parsers together use no more of them than one.
+bool readFastqPair(const std::string &path1, const std::string &path2, FastqReads &r1, FastqReads &r2, std::string *err) {
+    std::string err1, err2; bool ok1 = false, ok2 = false;
+    const int T = std::max(1, omp_get_max_threads()), T1 = std::max(1, T / 2), T2 = std::max(1, T - T / 2);
+    auto one = [](const std::string &path, FastqReads &r, std::string *e, bool *ok, int threads) {
+        omp_set_num_threads(threads);           // (this thread's own teams: parsePlainParallel sizes its team by it)
+        Entries en; en.keepQual = true;
+        if (!(*ok = parseFile(path, 0, en, e, true))) return;
+        const size_t n = en.seqOff.size();
+        r.off.swap(en.seqOff); r.hoff.swap(en.hdrOff); r.hlen.swap(en.hdrLen); r.hasQual.swap(en.hasQual);
+        r.len.resize(n);
+        for (size_t i = 0; i < n; i++) r.len[i] = en.seqLen[i] - 2;
+        r.seq.swap(en.seqBlob); r.qual.swap(en.qualBlob); r.hdr.swap(en.hdrBlob);
+    };
+    std::thread t([&] { one(path2, r2, &err2, &ok2, T2); });
+    one(path1, r1, &err1, &ok1, T1);
+    omp_set_num_threads(T);
+    t.join();
+    if (!ok1) { *err = err1; return false; }
+    if (!ok2) { *err = err2; return false; }
+    return true;
 }

@@ -19,9 +19,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <numeric>
 #include <omp.h>
 #include <unistd.h>
 #include <sys/stat.h>
+#include <fcntl.h>
 #include <string>
 #include <thread>
 #include <vector>
@@ -981,8 +983,44 @@ int clusterModules(const std::string &cmd, Args &a) {
     return EXIT_SUCCESS;
 }
 
+bool readsRefused(const FastqReads &r1, const FastqReads &r2, size_t n) {
+    // a quality byte >= 0x80: the reference's SSE and scalar paths take different minima for it (combine_reads.cpp:120-245)
+    bool bad = false;
+#pragma omp parallel for reduction(|| : bad) schedule(dynamic, 65536)
+    for (size_t i = 0; i < n; i++) {
+        const char *q1 = r1.qual.data() + r1.off[i], *q2 = r2.qual.data() + r2.off[i];
+        bool b = false;
+        for (uint32_t j = 0; j < r1.len[i]; j++) b |= (q1[j] & 0x80) != 0;
+        for (uint32_t j = 0; j < r2.len[i]; j++) b |= (q2[j] & 0x80) != 0;
+        bad = bad || b;
+    }
+    return bad;
+}
+// the read pairs of mergereads' file pairs (files[2f], files[2f + 1]): both files of a pair parsed at once, pairs[f] = the records taken in
+// lockstep; every pair checked in input order as mergereads.cpp:62-70 checks it, then the refusal above - all before anything is written
+// or the device is opened.  Returns the number of pairs.
+size_t readPairs(const char *module, const std::vector<std::string> &files, std::vector<FastqReads> &r, std::vector<size_t> &pairs) {
+    std::string err;
+    r.clear(); r.resize(files.size()); pairs.assign(files.size() / 2, 0);
+    size_t total = 0;
+    for (size_t f = 0; f < pairs.size(); f++) {
+        if (!readFastqPair(files[2 * f], files[2 * f + 1], r[2 * f], r[2 * f + 1], &err)) die(err);
+        const FastqReads &r1 = r[2 * f], &r2 = r[2 * f + 1];
+        pairs[f] = std::min(r1.len.size(), r2.len.size());
+        for (size_t i = 0; i < pairs[f]; i++) {
+            if (r1.len[i] == 0 || r2.len[i] == 0) die("Invalid sequence record found");
+            if (!r1.hasQual[i] || !r2.hasQual[i]) die("Invalid quality record found");
+        }
+        total += pairs[f];
+    }
+    for (size_t f = 0; f < pairs.size(); f++)
+        if (readsRefused(r[2 * f], r[2 * f + 1], pairs[f])) unsupported(std::string(module) + ": a quality byte >= 0x80 in " + files[2 * f] + " / " + files[2 * f + 1] +
+                                                                       " is not supported by the MI355X path (not FASTQ; the reference's SSE and scalar paths disagree on it)");
+    return total;
+}
+
 int readsLoop(Args &a) {
-    if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
+    if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
     // the contig iterations' buffers grow ~1.5x per iteration: head room in the device-memory cache lets them fit the previous iteration's blocks
     cdm_pool_headroom(getenv("CDM_POOL_HEADROOM") ? (float) atof(getenv("CDM_POOL_HEADROOM")) : 1.6f);
     {   // the workflow's own flags for the reads loop (src/commons/LocalParameters.h:283-318) on top of the stage lists
@@ -992,7 +1030,10 @@ int readsLoop(Args &a) {
         checkFlags("ancient_reads_loop", a, ANCIENT_FLAGS, LOOP_FLAGS);
     }
     // input: a sequence DB, or - when there is no <input>.index - FASTA/FASTQ[.gz] reads, parsed and laid out as createdb would
-    // (createdb.cpp:150-280, --shuffle 1 by default) and uploaded without a DB on disk in between
+    // (createdb.cpp:150-280, --shuffle 1 by default) and uploaded without a DB on disk in between; three or more positional arguments
+    // without an index are paired-end reads R1 R2 [R1 R2 ...] OUT, merged on the device into the DB the loop runs on, with the keys,
+    // the order and the wasExtended flags mergereads writes (the workflow's paired-end way in, guidedNuclAssemble.sh:28-32, where
+    // --shuffle has no effect either)
     MmDb seq; std::string err;
     int dbtype = 1;
     cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL;
@@ -1000,6 +1041,15 @@ int readsLoop(Args &a) {
     Laps laps;
     FastxDb fx;
     const bool fromDb = stat((a.pos[0] + ".index").c_str(), &st) == 0;
+    const bool paired = !fromDb && a.pos.size() >= 3;
+    const std::string outPath = paired ? a.pos.back() : a.pos[1];
+    std::vector<FastqReads> pr; std::vector<size_t> prPairs;
+    if (paired) {
+        const std::vector<std::string> files(a.pos.begin(), a.pos.end() - 1);
+        if (files.size() % 2) die("ancient_reads_loop: " + std::to_string(files.size()) + " read files given: paired-end input takes R1 R2 [R1 R2 ...] <o:sequenceDB>");
+        // (refused here, before the reads are parsed: each rank would need the merged DB uploaded on its own)
+        if (iflag(a, "--gpus", 1) > 1) unsupported("ancient_reads_loop: --gpus > 1 with paired-end input is not supported by the MI355X path (merge the pairs with mergereads first)");
+    }
     auto uploadTo = [&](cdm_ctx *c) -> cdm_seqdb * {       // (the same host copy serves every rank of a --gpus N run)
         if (fromDb) return uploadSeqDb(c, seq);
         cdm_seqdb *d = NULL;
@@ -1010,13 +1060,42 @@ int readsLoop(Args &a) {
         if (!seq.load(a.pos[0], &err)) die(err);
         dbtype = seq.dbtype;
         laps.lap("DB files mapped");
+    } else if (paired) {
+        if (readPairs("ancient_reads_loop", std::vector<std::string>(a.pos.begin(), a.pos.end() - 1), pr, prPairs) == 0) die("ancient_reads_loop: the read files hold no pair");
+        laps.lap("reads files parsed");
     } else {
         if (!readFastxAsDb(std::vector<std::string>(1, a.pos[0]), iflag(a, "--shuffle", 1) != 0, fx, &err)) die(err);
         for (auto &l : fx.len) l -= 2;
         laps.lap("reads file parsed");
     }
     ctx = openCtx(); laps.lap("device context");
-    db = uploadTo(ctx); laps.lap("sequences up");
+    if (paired) {
+        // one batch: the DB has to be resident anyway.  More than one file pair: their reads side by side in one pair of blobs first.
+        FastqReads c1, c2;
+        const FastqReads *r1 = &pr[0], *r2 = &pr[1];
+        if (prPairs.size() > 1) {
+            auto join = [&](FastqReads &dst, int side) {
+                size_t bytes = 0, m = 0;
+                for (size_t f = 0; f < prPairs.size(); f++) { bytes += pr[2 * f + side].seq.size(); m += prPairs[f]; }
+                dst.seq.resize(bytes); dst.qual.resize(bytes); dst.off.reserve(m); dst.len.reserve(m);
+                size_t at = 0;
+                for (size_t f = 0; f < prPairs.size(); f++) {
+                    const FastqReads &s = pr[2 * f + side];
+                    memcpy(dst.seq.data() + at, s.seq.data(), s.seq.size()); memcpy(dst.qual.data() + at, s.qual.data(), std::min(s.qual.size(), s.seq.size()));
+                    for (size_t i = 0; i < prPairs[f]; i++) { dst.off.push_back(at + s.off[i]); dst.len.push_back(s.len[i]); }
+                    at += s.seq.size();
+                }
+            };
+            join(c1, 0); join(c2, 1);
+            r1 = &c1; r2 = &c2;
+        }
+        cdm_pairs *h = NULL;
+        check(cdm_pairs_merge(ctx, r1->seq.data(), r1->qual.data(), r1->off.data(), r1->len.data(), r2->seq.data(), r2->qual.data(), r2->off.data(), r2->len.data(),
+                              std::accumulate(prPairs.begin(), prPairs.end(), (size_t) 0), NULL, &h), "mergereads");
+        check(cdm_pairs_to_seqdb(ctx, h, 0, &db), "mergereads");
+        cdm_pairs_free(h);
+        laps.lap("pairs merged into the DB");
+    } else { db = uploadTo(ctx); laps.lap("sequences up"); }
     check(cdm_damage_load(ctx, a.flag.count("--ancient-damage") ? a.flag["--ancient-damage"].c_str() : ""), "Profile not 12 fields");
     cdm_kmer_params kp;
     kp.kmer_size = (int) iflag(a, "--k-ancient-reads", 20); kp.kmers_per_seq = (int) iflag(a, "--kmer-per-seq-ancient", 200);
@@ -1130,7 +1209,7 @@ int readsLoop(Args &a) {
         }
     }
     laps.lap("iterations");
-    if (cyclic.key.empty()) { writeSeqDb(ctx, db, a.pos[1], dbtype); laps.lap("sequences down, DB written"); }
+    if (cyclic.key.empty()) { writeSeqDb(ctx, db, outPath, dbtype); laps.lap("sequences down, DB written"); }
     else {   // concatdbs --preserve-keys of the linear and the circular contigs, written in key order
         OutChunk all; appendEntries(ctx, db, all);
         std::vector<std::pair<uint32_t, std::pair<const OutChunk *, size_t>>> order;
@@ -1143,7 +1222,7 @@ int readsLoop(Args &a) {
             const OutChunk &c = *o.second.first; const size_t i = o.second.second;
             merged[0].add(o.first, c.data.data() + (&c == &all ? offA[i] : offC[i]), c.len[i] - 1, c.ext[i]);
         }
-        if (!mmdbWriteChunks(a.pos[1], dbtype, merged, &err)) die(err);
+        if (!mmdbWriteChunks(outPath, dbtype, merged, &err)) die(err);
     }
     cdm_seqdb_free(db); cdm_ctx_destroy(ctx);
     return EXIT_SUCCESS;
@@ -1211,6 +1290,93 @@ int convert2fasta(Args &a) {
     if (convert2fastaModule(a.pos[0], a.pos[1], &err)) die(err);
     return EXIT_SUCCESS;
 }
+// ---- mergereads (src/assembler/mergereads.cpp): paired-end reads merged with FLASH's combine_reads (lib/flash) on the device
+// (csrc/pairmerge.hip, cdm_pairs_merge).  File pair i is (files[2i], files[2i + 1]).  The reference counts the output among its file
+// names (mergereads.cpp:38-48), so with an odd number of inputs its last pair is (last input, output DB): refused here with the
+// reference's message for the usual case, an output that is not there yet.  The records of a pair's files are taken in lockstep until
+// either file ends.  Entries: a combined pair gives its consensus under R1's
+// name, any other pair R1 and the reverse-complemented R2 under their names; keys 0, 1, ... in input order; "SEQ\n\0" / "name\n\0";
+// every entry wasExtended = 1 (DBWriter::writeEnd(id, 0, true), DBWriter.h:30); no .lookup, no .source.
+//   CDM_MERGE_BATCH=<pairs>: pairs per device batch (default: 8 M pairs, or fewer so that a batch holds at most 2 GB of read bytes)
+static int pieceSink(void *user, const char *data, uint64_t offset, uint64_t bytes) {
+    const std::pair<int, uint64_t> &f = *(const std::pair<int, uint64_t> *) user;
+    return mmdbWritePiece(f.first, data, f.second + offset, bytes) ? 0 : 1;
+}
+int mergereads(Args &a) {
+    static const FlagSpec MERGEREADS_FLAGS[] = {{"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};     // LocalParameters onlythreads
+    checkFlags("mergereads", a, MERGEREADS_FLAGS);
+    if (a.pos.size() < 2) die("Usage: carpedeam mergereads <i:fastqFile1_R1[.gz]> <i:fastqFile1_R2[.gz]> ... <o:sequenceDB>");
+    const std::string outPath = a.pos.back();
+    std::vector<std::string> files(a.pos.begin(), a.pos.end() - 1);
+    if (files.size() % 2) {
+        struct stat st;
+        if (stat(outPath.c_str(), &st) != 0) die(outPath + ": No such file or directory");      // what the reference says opening it as the last R2
+        // the output exists: the reference reads it as the last pair's R2 while it writes it anew - not reproduced
+        unsupported("mergereads: an odd number of input files (" + std::to_string(files.size()) + ") with an existing output DB is not supported by the MI355X path "
+                    "(the reference would read " + outPath + " as the last R2)");
+    }
+    Laps laps;
+    std::string err;
+    std::vector<FastqReads> r; std::vector<size_t> pairs;
+    const size_t total = readPairs("mergereads", files, r, pairs);
+    laps.lap("reads files parsed");
+    cdm_ctx *ctx = total ? openCtx() : NULL;
+    if (ctx) laps.lap("device context");
+    const int dataFd = open(outPath.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (dataFd < 0) die("Could not open " + outPath + " for writing");
+    HVec<uint64_t> eOff; HVec<uint32_t> eLen, hLen; HVec<uint64_t> hOff; HVec<char> hBlob;
+    eOff.reserve(2 * total + 1); eLen.reserve(2 * total + 1); hOff.reserve(2 * total + 1); hLen.reserve(2 * total + 1);
+    uint64_t textAt = 0;
+    const long batchEnv = getenv("CDM_MERGE_BATCH") ? atol(getenv("CDM_MERGE_BATCH")) : 0;
+    double devMs = 0;
+    std::vector<uint8_t> status; std::vector<uint32_t> elen;
+    for (size_t f = 0; f < pairs.size(); f++) {
+        const FastqReads &r1 = r[2 * f], &r2 = r[2 * f + 1];
+        for (size_t lo = 0; lo < pairs[f];) {
+            size_t hi = lo, bytes = 0;
+            const size_t maxPairs = batchEnv > 0 ? (size_t) batchEnv : (size_t) 8 << 20;
+            while (hi < pairs[f] && hi - lo < maxPairs && (batchEnv > 0 || hi == lo || bytes + r1.len[hi] + r2.len[hi] <= ((size_t) 2 << 30))) { bytes += r1.len[hi] + r2.len[hi]; hi++; }
+            const size_t m = hi - lo;
+            cdm_pairs *h = NULL;
+            check(cdm_pairs_merge(ctx, r1.seq.data(), r1.qual.data(), r1.off.data() + lo, r1.len.data() + lo, r2.seq.data(), r2.qual.data(), r2.off.data() + lo,
+                                  r2.len.data() + lo, m, NULL, &h), "mergereads");
+            devMs += cdm_pairs_kernel_ms(h);
+            const uint64_t ents = cdm_pairs_entries(h);
+            status.resize(m); elen.resize(ents);
+            check(cdm_pairs_download(ctx, h, status.data(), NULL, NULL, elen.data()), "mergereads: download");
+            std::pair<int, uint64_t> sinkAt(dataFd, textAt);
+            check(cdm_pairs_download_stream(ctx, h, 64u << 20, pieceSink, &sinkAt), "mergereads: download");
+            cdm_pairs_free(h);
+            // the index columns of the sequence DB and the header entries: R1's name for a combined pair, R1's and R2's names otherwise
+            size_t e = 0;
+            auto name = [&](const FastqReads &rr, size_t i) {
+                const char *p = rr.hdr.data() + rr.hoff[i];
+                size_t k = 0; while (p[k] != ' ' && p[k] != '\n') k++;         // the stored header is "name[ comment]\n"
+                hOff.push_back(hBlob.size()); hLen.push_back((uint32_t) k + 2);
+                if (hBlob.capacity() - hBlob.size() < k + 2) hBlob.reserve(std::max(hBlob.capacity() * 2, hBlob.size() + k + 2 + (16u << 20)));
+                hBlob.insert(hBlob.end(), p, p + k); hBlob.push_back('\n'); hBlob.push_back('\0');
+            };
+            for (size_t i = 0; i < m; i++) {
+                name(r1, lo + i);
+                if (!status[i]) name(r2, lo + i);
+                for (int k = status[i] ? 1 : 2; k > 0; k--, e++) { eOff.push_back(textAt); eLen.push_back(elen[e] + 2); textAt += elen[e] + 2; }
+            }
+            lo = hi;
+        }
+    }
+    if (ctx) laps.lap("pairs merged on the device, text written");
+    if (close(dataFd) != 0) die("Could not write " + outPath);
+    const size_t n = eOff.size();
+    HVec<uint32_t> keys(n); HVec<uint8_t> ext(n);
+    for (size_t i = 0; i < n; i++) { keys[i] = (uint32_t) i; ext[i] = 1; }
+    if (!mmdbWriteBlob(outPath, 1, NULL, 0, keys.data(), eOff.data(), eLen.data(), ext.data(), n, &err, MMDB_DATA_ELSEWHERE)) die(err);
+    if (!mmdbWriteBlob(outPath + "_h", 12, n ? hBlob.data() : "", hBlob.size(), keys.data(), hOff.data(), hLen.data(), ext.data(), n, &err)) die(err);
+    laps.lap("index and header DB written");
+    seqSideFromText(outPath);
+    if (getenv("CDM_TIMING")) fprintf(stderr, "  %llu pairs -> %llu entries; merge kernels %.3f ms on the device\n", (unsigned long long) total, (unsigned long long) n, devMs);
+    if (ctx) cdm_ctx_destroy(ctx);
+    return EXIT_SUCCESS;
+}
 int createhdb(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam createhdb <i:sequenceDB> [<i:sequenceDBcycle>] <o:headerDB>");
     checkFlags("createhdb", a, PLAIN_FLAGS);
@@ -1240,7 +1406,7 @@ static bool workInChild() {
 }
 int main(int argc, char **argv) {
     workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|createdb|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -1261,6 +1427,7 @@ int main(int argc, char **argv) {
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);
     else if (cmd == "createhdb") rc = createhdb(a);
+    else if (cmd == "mergereads") rc = mergereads(a);
     else if (cmd == "cyclecheck") rc = cyclecheck(a);
     else { fprintf(stderr, "Invalid Command: %s\n", cmd.c_str()); return EXIT_FAILURE; }
     fprintf(stderr, "Time for processing: %.3fs\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

@@ -398,6 +398,55 @@ int cdm_reads_iteration_dist(cdm_ctx *ctx, cdm_comm *comm, const cdm_seqdb *db, 
 int cdm_contig_iteration_dist(cdm_ctx *ctx, cdm_comm *comm, const cdm_seqdb *db, const cdm_kmer_params *kpar, const cdm_rescore_params *rpar,
                               const cdm_ancient_params *apar, float merge_seq_id_thr, cdm_alns **alns, cdm_seqdb **corr, cdm_seqdb **next);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Paired-end merging: the module mergereads (src/assembler/mergereads.cpp) - FLASH's combine_reads with the parameters fixed at
+ * mergereads.cpp:20-24 (min overlap 15, max overlap 65, max mismatch density 0.10f, no outies, no capped mismatch qualities) - for
+ * one batch of pairs.  csrc/pairmerge.hip.
+ *
+ * Input, pair i: R1 = seq1[off1[i] .. + len1[i]) with its qualities at the same offsets in qual1, R2 likewise in seq2 / qual2, AS READ:
+ * the device reverse-complements R2 with FLASH's table (lib/flash/read.cpp:4-13: IUPAC codes and lower case to their complements,
+ * U -> A, every other byte to '.') and reverses its qualities.  Lengths must be >= 1 (mergereads: "Invalid sequence record found").
+ *
+ * pair_align (lib/flash/combine_reads.cpp:266-334): shifts i = max(0, L1 - L2) .. L1 - min_overlap; the overlap length is L1 - i minus
+ * the positions where either base is 'N' (upper case only); a shift counts when that length is >= min_overlap; with
+ * score_len = (float) min(length, max_overlap), density = mismatches / score_len and qual = sum of min(q1, q2) over the mismatches /
+ * score_len, both in float, mismatches comparing raw bytes, qualities the raw ASCII bytes (Phred+33 not subtracted).  The shift with the
+ * smallest (density, qual), the first one on ties, is taken when its density is <= max_mismatch_density.
+ * generate_combined_read (:338-446): R1's prefix, the overlap (equal bases kept, else the base of the higher quality - signed char -,
+ * on equal qualities R2's unless it is 'N'), R2's tail.  Qualities of the combined read are not produced (mergereads writes none).
+ *
+ * Output, in mergereads' entry order (mergereads.cpp:77-114): a combined pair gives one entry (the consensus), any other pair two
+ * (R1 as read, then the reverse-complemented R2); entry text "SEQ\n\0", back to back.
+ *
+ * Quality bytes >= 0x80 are refused (CDM_ERR_UNSUPPORTED): the reference's SSE path takes their minimum unsigned and its scalar path
+ * signed (combine_reads.cpp:120-245), so no single answer exists for them; valid FASTQ never has them.
+ */
+typedef struct cdm_pairs cdm_pairs;   /* one merged batch, resident in HBM */
+typedef struct cdm_merge_params {
+    int min_overlap;              /* 15 */
+    int max_overlap;              /* 65 */
+    float max_mismatch_density;   /* 0.10f */
+} cdm_merge_params;
+/* par may be NULL: mergereads' values.  min_overlap, max_overlap >= 1 and 0 <= max_mismatch_density <= 1e6 (NaN and inf are
+ * CDM_ERR_INVALID) */
+int cdm_pairs_merge(cdm_ctx *ctx, const char *seq1, const char *qual1, const uint64_t *off1, const uint32_t *len1,
+                    const char *seq2, const char *qual2, const uint64_t *off2, const uint32_t *len2, uint64_t n,
+                    const cdm_merge_params *par, cdm_pairs **out);
+uint64_t cdm_pairs_count(const cdm_pairs *h);     /* pairs */
+uint64_t cdm_pairs_entries(const cdm_pairs *h);   /* output entries: pairs + pairs not combined */
+uint64_t cdm_pairs_bytes(const cdm_pairs *h);     /* bytes of the entries' text */
+float cdm_pairs_kernel_ms(const cdm_pairs *h);    /* device time of the merge (kernels and scans), ms */
+/* any argument may be NULL.  status[n]: 1 combined, 0 not; merged_len[n]: the consensus length (0: not combined);
+ * text[bytes]: the entries' text; entry_len[entries]: sequence length of each entry (without "\n\0") */
+int cdm_pairs_download(cdm_ctx *ctx, const cdm_pairs *h, uint8_t *status, uint32_t *merged_len, char *text, uint32_t *entry_len);
+/* the text in pieces of piece_bytes through pinned staging buffers, as cdm_seqdb_download_stream */
+int cdm_pairs_download_stream(cdm_ctx *ctx, const cdm_pairs *h, uint64_t piece_bytes,
+                              int (*sink)(void *user, const char *data, uint64_t offset, uint64_t bytes), void *user);
+/* the entries as a resident sequence DB - no host round trip.  Keys first_key, first_key + 1, ...; wasExtended 1 on every entry, as
+ * mergereads writes its DB (DBWriter::writeEnd(id, 0, true), mergereads.cpp:82-110; DBWriter.h:30) */
+int cdm_pairs_to_seqdb(cdm_ctx *ctx, const cdm_pairs *h, uint32_t first_key, cdm_seqdb **out);
+void cdm_pairs_free(cdm_pairs *h);
+
 #ifdef __cplusplus
 }
 #endif
