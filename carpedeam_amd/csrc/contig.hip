@@ -6,8 +6,9 @@
 // comparator (:25-70: lgammaf / logf / exp of the C library decide the order, and it is no strict weak ordering), the extension loop
 // and the re-alignment of parked hits - runs on the device as well since round 5 (contigqueue.hip: the comparator from tables of the
 // C library's own values, libstdc++'s heap step for step).  The host code of rounds 2-4 (host/contigmerge.cpp, compiled like the
-// reference) stays for --unsafe 1, for small calls in a process that has not filled those tables, for the queries the device hands
-// back, and as what the tests compare the device queue with (hostQueue below).
+// reference) stays for small calls in a process that has not filled those tables, for the queries the device hands back, and as what
+// the tests compare the device queue with (hostQueue below).  --unsafe 1 counts its columns against a consensus of the extending
+// candidates instead of the query: contigunsafe.hip rewrites those counts before the device queue runs.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -177,13 +178,12 @@ extern "C" int cdm_contig_merge(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_aln
     const bool timing = cdmGetenv("CDM_TIMING") != nullptr;
     auto tPrev = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) { if (timing) { const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  contig merge: %-28s %.3f s\n", what, std::chrono::duration<double>(t - tPrev).count()); tPrev = t; } };
-    // Where the queue runs: on the device, unless --unsafe 1 (its consensus works on the host's strings) - or the call is small and this
-    // process has not filled the device queue's tables yet: they take about a second once per process, which a module process started per
-    // iteration (the reference's scripts) pays every time, while the host queue takes ~80 ns per record all in.  CDM_CONTIG_QUEUE=host|device
-    // pins either.
+    // Where the queue runs, in either mode: on the device, unless the call is small and this process has not filled the device queue's
+    // tables yet: they take about a second once per process, which a module process started per iteration (the reference's scripts)
+    // pays every time, while the host queue takes ~80 ns per record all in.  CDM_CONTIG_QUEUE=host|device pins either.
     const char *where = cdmGetenv("CDM_CONTIG_QUEUE");
     const bool small = nRec < (8ull << 20) && !cdm_contig_tables_ready(ctx->device);
-    const bool onHost = par->unsafe != 0 || (where ? !strcmp(where, "host") : small);
+    const bool onHost = where ? !strcmp(where, "host") : small;
     std::vector<uint32_t> grownIdx; std::vector<uint8_t> outExt; cdm_seqdb *grown = nullptr;
     if (onHost) {
         if (int rc = hostQueue(ctx, db, alns, par, mergeSeqIdThr, dStats.p, nullptr, grownIdx, &grown, outExt)) return rc;
@@ -194,8 +194,14 @@ extern "C" int cdm_contig_merge(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_aln
         lap("overlay");
         return rcUp;
     }
+    // --unsafe 1: the counts against the consensus, and the queries the host has to take
+    DevBuf<uint8_t> handBack;
+    if (par->unsafe != 0) {
+        if (!handBack.alloc(n)) { cdm_set_error("cdm_contig_merge: out of device memory"); return CDM_ERR_HIP; }
+        if (int rc = cdm_contig_unsafe_columns(ctx, db, alns, par, mergeSeqIdThr, meta.p, owner.p, dStats.p, handBack.p)) return rc;
+    }
     CqResult res;
-    if (int rc = cdm_contig_queue_device(ctx, db, alns, par, mergeSeqIdThr, meta.p, owner.p, dStats.p, &res)) { if (res.grown) cdm_seqdb_free(res.grown); return rc; }
+    if (int rc = cdm_contig_queue_device(ctx, db, alns, par, mergeSeqIdThr, meta.p, owner.p, dStats.p, handBack.p, &res)) { if (res.grown) cdm_seqdb_free(res.grown); return rc; }
     hipEventElapsedTime(&ctx->lastMs[12], ctx->ev0, ctx->ev1);
     tPrev = std::chrono::steady_clock::now();
     if (!res.nHandedBack) {

@@ -17,6 +17,8 @@
 //     series sums at most yMis such terms, and a comparison whose sum lands within 1e-12 of 0.45 or 0.55 (probability ~4e-12 per
 //     comparison) hands its QUERY back to the host code, as does an argument beyond the tables and a sequence with letters beyond
 //     ACGTN in play: cdm_contig_merge_host runs for those queries alone (contig.hip);
+//   * --unsafe 1 runs here too: contigunsafe.hip first rewrites the five counts of ContigStat that the mode's consensus decides, and
+//     names the queries whose columns hold letters beyond ACGTN (handBack), which round 0 hands back;
 //   * the heap is libstdc++'s: std::push_heap (__push_heap) and std::pop_heap (__adjust_heap, then __push_heap) step for step, on the
 //     query's own stretch of a record-index array.
 //
@@ -111,6 +113,7 @@ struct CqArgs {
     const CqBuf *bufs;                      // [round]
     unsigned int *counters;                 // 0 undefined case, 1 queries handed back, 2 grown this round, 3 parked this round, 4 active next round, 5 first active
     uint32_t fallbackEvery;                 // tests: hand every k-th query back
+    const uint8_t *handBack;                // NULL, or [n]: 1 = hand this query back (--unsafe 1: letters beyond ACGTN in its columns)
 };
 
 __device__ __forceinline__ bool tabIndex(float x, int top, uint32_t &i) { i = __float_as_uint(x) - CQ_ONE; return i < ((uint32_t) top << 23); }
@@ -172,6 +175,7 @@ __global__ __launch_bounds__(256) void k_cq_any(CqArgs a, uint32_t *__restrict__
     if (q >= a.n) return;
     uint32_t any = 0;
     for (uint64_t r = a.aoff[q]; r < a.aoff[q + 1] && !any; r++) any = a.gate[r];
+    if (a.handBack && a.handBack[q]) any = 1;           // (active, so that round 0 hands it back whatever its gate says)
     flag[q] = any;
     a.heapN[q] = 0; a.parkN[q] = 0; a.curLen[q] = a.meta[q].len; a.verRound[q] = CQ_NONE; a.verWoff[q] = 0; a.leftOff[q] = 0;
     a.qflags[q] = (a.meta[q].flags & 1u) ? QF_HASN : 0u;
@@ -247,7 +251,7 @@ __device__ __forceinline__ void cqRound(const CqArgs &a, uint32_t q, uint32_t ro
     uint32_t hn = a.heapN[q];
     const SeqMeta qm = a.meta[q];
     uint32_t flags = a.qflags[q];
-    bool giveUp = (qm.flags & 4u) != 0 || (a.fallbackEvery && q % a.fallbackEvery == 0);
+    bool giveUp = (qm.flags & 4u) != 0 || (a.fallbackEvery && q % a.fallbackEvery == 0) || (a.handBack && a.handBack[q]);
     // ---- pushes: round 0 the gated records in the order of the records, later the parked hits that still pass, in the order they were parked
     if (!giveUp) {
         if (round == 0) {
@@ -499,7 +503,7 @@ __global__ __launch_bounds__(256) void k_cq_gather(CqArgs a, const uint32_t *__r
 }  // namespace
 
 int cdm_contig_queue_device(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const cdm_ancient_params *par, float mergeSeqIdThr, const SeqMeta *meta, const uint32_t *owner,
-                            const ContigStat *dStats, CqResult *res) {
+                            const ContigStat *dStats, const uint8_t *handBack, CqResult *res) {
     hipStream_t s = ctx->stream;
     const uint32_t n = (uint32_t) db->n;
     const uint64_t nRec = alns->count;
@@ -523,6 +527,7 @@ int cdm_contig_queue_device(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *a
     a.key = key.p; a.co = co.p; a.gate = gate.p; a.heap = heap.p; a.park = park.p; a.heapN = heapN.p; a.parkN = parkN.p; a.curLen = curLen.p; a.verRound = verRound.p; a.verWoff = verWoff.p;
     a.leftOff = leftOff.p; a.qflags = qflags.p; a.bufs = bufs.p; a.counters = counters.p;
     a.fallbackEvery = cdmGetenv("CDM_CONTIG_HAND_BACK_EVERY") ? (uint32_t) atoi(cdmGetenv("CDM_CONTIG_HAND_BACK_EVERY")) : 0u;
+    a.handBack = handBack;
     CDM_HIP(hipMemsetAsync(counters.p, 0, 32, s));
     if (nRec) hipLaunchKernelGGL(k_cq_gate, CDM_GRID((nRec + 255) / 256, 256), dim3(256), 0, s, a);
     if (n) hipLaunchKernelGGL(k_cq_any, dim3((n + 255) / 256), dim3(256), 0, s, a, flag.p);

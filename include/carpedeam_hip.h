@@ -319,8 +319,9 @@ int cdm_extend(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const cd
  * (orientation, identities, the counts of updateSeqIdConsensus / ancientMatchCount) runs on the device, and since round 5 so do the
  * queue - a Beta-posterior comparator built on the C library's lgammaf / logf (:25-70), not a strict weak ordering: the device reads
  * those two functions from tables of the library's own values and replays libstdc++'s heap step for step (csrc/contigqueue.hip) -
- * and the extension loop (:276-470).  The library's host code (the same libstdc++ priority queue as the reference) runs for
- * par->unsafe = 1, for small calls in a process that has not filled the tables yet, and for the rare query the device hands back
+ * and the extension loop (:276-470), in both modes: par->unsafe = 1 counts its columns against the majority-vote consensus of the
+ * extending candidates on the device as well (csrc/contigunsafe.hip).  The library's host code (the same libstdc++ priority queue as
+ * the reference) runs for small calls in a process that has not filled the tables yet and for the rare query the device hands back
  * (CDM_CONTIG_QUEUE=host|device pins either).  Same result either way.
  * merge_seq_id_thr is --min-merge-seq-id; par->ry_seq_id_thr, max_seq_len, unsafe, min_cov_safe are used from par.
  */
