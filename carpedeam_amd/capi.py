@@ -44,6 +44,27 @@ class HammingParams(C.Structure):
         return cls(0.97, 0.001, 1, 0.99, 0, 0, 1)
 
 
+class AlignParams(C.Structure):
+    """cdm_align_params: gap costs, z-drop and band of linclust's `align` as `ancient_assemble` runs it"""
+    _fields_ = [("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("zdrop", C.c_int32), ("band", C.c_int32)]
+
+    @classmethod
+    def linclust(cls):
+        return cls(5, 2, 200, 64)
+
+
+class AlignHit(C.Structure):
+    """cdm_align_hit: one seeded hit of the gapped step (sequence indices, strand, cut lengths, the seed's ends, the stale letters)"""
+    _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("q_len", C.c_uint32), ("t_len", C.c_uint32), ("q_end", C.c_int32), ("t_end", C.c_int32),
+                ("reverse", C.c_uint8), ("wrapped", C.c_uint8), ("stale_q", C.c_uint8), ("stale_t", C.c_uint8)]
+
+
+ALIGN_HIT_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("q_len", "<u4"), ("t_len", "<u4"), ("q_end", "<i4"), ("t_end", "<i4"),
+                            ("reverse", "u1"), ("wrapped", "u1"), ("stale_q", "u1"), ("stale_t", "u1")])
+ALIGN_RESULT_DTYPE = np.dtype([("score", "<i4"), ("q_start", "<i4"), ("q_end", "<i4"), ("t_start", "<i4"), ("t_end", "<i4"), ("identities", "<i4"),
+                               ("columns", "<i4"), ("rows", "<i4")])
+
+
 class AncientParams(C.Structure):
     _fields_ = [("seq_id_thr", C.c_float), ("corr_reads_ry_seq_id", C.c_float), ("ry_seq_id_thr", C.c_float), ("rand_align_penal", C.c_float),
                 ("excess_penal", C.c_float), ("likelihood_threshold", C.c_float), ("unsafe", C.c_int32), ("min_cov_safe", C.c_int32),
@@ -62,7 +83,7 @@ EXPORTS = [
     "cdm_evalue", "cdm_bit_score", "cdm_gapped_evalue", "cdm_correct", "cdm_extend",
     "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kpart_free", "cdm_dev_copy",
     "cdm_seqdb_from_packed_ext", "cdm_seqdb_copy_ext", "cdm_seqdb_export_packed", "cdm_seqdb_import_packed", "cdm_contig_merge", "cdm_cyclecheck", "cdm_seqdb_has_raw", "cdm_seqdb_copy_raw", "cdm_seqdb_attach_raw",
-    "cdm_rescore_hamming", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
+    "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
@@ -150,6 +171,8 @@ def lib():
         l.cdm_hits_download.argtypes = [vp, vp, vp, vp]
         l.cdm_rescore.argtypes = [vp, vp, vp, C.POINTER(RescoreParams), C.POINTER(vp)]
         l.cdm_rescore_hamming.argtypes = [vp, vp, vp, C.POINTER(HammingParams), C.POINTER(vp)]
+        l.cdm_align_hits.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.c_uint64, vp, vp]
+        l.cdm_align_mode.argtypes = []
         l.cdm_pool_headroom.argtypes = [C.c_float]
         l.cdm_pool_headroom.restype = None
         l.cdm_alns_upload.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
@@ -550,6 +573,16 @@ class Ctx:
         h = C.c_void_p()
         _check(lib().cdm_rescore_hamming(self.h, db.h, hits.h, C.byref(par), C.byref(h)))
         return Hits(self, h, db.n)
+
+    def align_hits(self, db, hits, par=None):
+        """the gapped extensions of `align` for seeded hits (a structured array of ALIGN_HIT_DTYPE); returns (results of
+        ALIGN_RESULT_DTYPE, {"slices", "rows", "trace_bytes", "seconds"})"""
+        par = par or AlignParams.linclust()
+        hits = np.ascontiguousarray(hits, ALIGN_HIT_DTYPE)
+        res = np.zeros(len(hits), ALIGN_RESULT_DTYPE)
+        stats = np.zeros(4, np.uint64)
+        _check(lib().cdm_align_hits(self.h, db.h, C.byref(par), _ptr(hits), len(hits), _ptr(res), _ptr(stats)))
+        return res, {"slices": int(stats[0]), "rows": int(stats[1]), "trace_bytes": int(stats[2]), "seconds": stats[3] / 1e6}
 
     def correct(self, db, alns, par=None):
         par = par or AncientParams.default()

@@ -14,6 +14,7 @@
 // routine's statements one by one.  tests/test_align_module.py compares the module with the reference's object code on contig sets
 // with substitutions, insertions, deletions, rotations and reverse complements.
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -21,6 +22,8 @@
 #include <cstring>
 #include <omp.h>
 #include <string>
+#include <thread>
+#include <utility>
 #include <vector>
 
 #include "carpedeam_hip.h"
@@ -254,6 +257,15 @@ struct AlignParams {       // (host/main.cpp holds the same declaration)
     int gapOpen = 5, gapExtend = 2, zdrop = 40; unsigned maxAccept = INT_MAX, maxReject = INT_MAX; size_t maxSeqLen = 65535;
 };
 
+namespace {
+// a hit between the seed and its record: what the seed (no extension needed), the host's extension or the device's gave
+struct Pending { uint32_t dbKey; int qL, tL, origLen; bool isReverse, isIdentity, onDevice; int score1, qs1, qe1, ds1, de1, aaIds; unsigned btLen; };
+struct ThreadWork {
+    std::vector<Pending> pend; std::vector<cdm_align_hit> dev; std::vector<std::pair<uint32_t, uint32_t>> entries;       // (query key, hits) per prefilter entry
+    uint64_t extended = 0;
+};
+}  // namespace
+
 int alignModule(const std::string &qPath, const std::string &tPath, const std::string &prefPath, const std::string &outPath, const AlignParams &P, std::string *err) {
     if (qPath != tPath) { *err = "align: query and target DB must be the same on the MI355X path"; return 77; }
     MmDb seq, pref;
@@ -268,8 +280,47 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
     const int T = std::max(1, omp_get_max_threads());
     std::vector<OutChunk> chunks((size_t) T);
     std::string failure; int failCode = 0;
-#pragma omp parallel for schedule(static, 1) num_threads(T)
-    for (int th = 0; th < T; th++) {
+    // ---- Matcher::getSWResult's tail: the record of a hit from what the seed or the extension gave, and whether it passes
+    auto finish = [&](const Pending &h, Result &res) -> bool {
+        const int score1 = h.score1, qs1 = h.qs1, qe1 = h.qe1, ds1 = h.ds1, de1 = h.de1, aaIds = h.aaIds, qL = h.qL, tL = h.tL, origLen = h.origLen;
+        const unsigned btLen = h.btLen;
+        float qcov = computeCov((unsigned) qs1, (unsigned) qe1, (unsigned) qL);
+        if (P.wrapped) qcov = std::min(1.0f, qcov * 2);
+        float dbcov = computeCov((unsigned) ds1, (unsigned) de1, (unsigned) tL);
+        double evalue = 0; int bits = 0;
+        cdm_gapped_evalue(P.gapOpen, P.gapExtend, (double) score1, (double) origLen, dbRes, &evalue, &bits);
+        const unsigned alnLength = btLen;           // (the edit script's length; without one: max(|qe1 - qs1|, |de1 - ds1|) + 1)
+        float seqId;
+        switch (P.seqIdMode) {
+            case 1: seqId = static_cast<float>(aaIds) / static_cast<float>(std::min(origLen, tL)); break;
+            case 2: seqId = static_cast<float>(aaIds) / static_cast<float>(std::max(origLen, tL)); break;
+            default: seqId = static_cast<float>(aaIds) / static_cast<float>((int) alnLength);
+        }
+        res.dbKey = h.dbKey; res.score = bits; res.qcov = qcov; res.dbcov = dbcov; res.seqId = seqId; res.eval = evalue; res.alnLength = alnLength;
+        res.qStart = qs1; res.qEnd = qe1; res.qLen = (unsigned) origLen; res.dbLen = (unsigned) tL;
+        if (h.isReverse) { res.dbStart = de1; res.dbEnd = ds1; } else { res.dbStart = ds1; res.dbEnd = de1; }
+        if (h.isIdentity) { res.qcov = 1.0f; res.dbcov = 1.0f; res.seqId = 1.0f; }
+        return h.isIdentity || (res.eval <= P.evalThr && res.seqId >= P.seqIdThr && hasCoverage(P.covThr, P.covMode, res.qcov, res.dbcov) && (int) res.alnLength >= P.alnLenThr);
+    };
+    // the records of a query: sorted, as text (Matcher::resultToBuffer, no backtrace)
+    auto emit = [&](OutChunk &c, uint32_t queryKey, std::vector<Result> &results, std::string &out) {
+        char buf[256];
+        out.clear();
+        if (results.size() > 1) std::sort(results.begin(), results.end(), compareHits);
+        for (const Result &r : results) {
+            char *w = buf;
+            w = utoa(r.dbKey, w); *w++ = '\t'; w = itoa(r.score, w); *w++ = '\t'; w = seqIdText(r.seqId, w); *w++ = '\t';
+            w += sprintf(w, "%.3E", r.eval); *w++ = '\t';
+            w = itoa(r.qStart, w); *w++ = '\t'; w = itoa(r.qEnd, w); *w++ = '\t'; w = itoa(r.qLen, w); *w++ = '\t';
+            w = itoa(r.dbStart, w); *w++ = '\t'; w = itoa(r.dbEnd, w); *w++ = '\t'; w = itoa(r.dbLen, w); *w++ = '\n';
+            out.append(buf, (size_t) (w - buf));
+        }
+        c.add(queryKey, out.data(), out.size(), 0);
+    };
+    // The prefilter entries of worker thread th.  collect = false: every hit from the seed to the text (the host path).  collect = true: the
+    // device path's pre-pass - the same walk over the same chunk with the same buffers, so that the letters behind the sequences are the
+    // ones the host path's extension would read; the hits that need an extension are left in work.dev, all of them in work.pend
+    auto runChunk = [&](int th, bool collect, ThreadWork &work) {
         const size_t lo = pref.size() * (size_t) th / T, hi = pref.size() * (size_t) (th + 1) / T;
         OutChunk &c = chunks[th];
         std::string qDoubled, out;
@@ -282,11 +333,11 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
         std::vector<uint8_t> qNum(maxLen + 1, 0), qRc(maxLen + 1, 0), tNum(maxLen + 1, 0), qRev, qRcRev, tRev; std::string qRcChar;
         auto fit = [](std::vector<uint8_t> &b, size_t n) { if (b.size() < n + 1) b.resize(n + 1, 0); };
         std::vector<Result> results;
-        char buf[256];
         for (size_t id = lo; id < hi && !failCode; id++) {
             const uint32_t queryKey = pref.key[id];
             const char *data = pref.entry(id);
             results.clear(); out.clear();
+            const size_t pendAtEntry = work.pend.size();
             size_t origQueryLen = 0, queryLen = 0; const char *qChar = nullptr;
             if (*data != '\0') {
                 const int64_t qId = seq.idOf(queryKey);
@@ -338,8 +389,6 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
                 // ---- BandedNucleotideAligner::align
                 const char *qAlnChar = isReverse ? qRcChar.data() : qChar;
                 const uint8_t *qAlnRev = isReverse ? qRcRev.data() : qRev.data(), *qAln = isReverse ? qRc.data() : qNum.data();
-                tRev.resize(tLen + 1);
-                for (size_t i = 0; i <= tLen; i++) tRev[i] = tNum[tLen - i];
                 const int qL = (int) queryLen, tL = (int) tLen;
                 int origLen = qL;
                 Local aln;
@@ -374,13 +423,21 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
                 int qUS, qUE, dbUS, dbUE;
                 if (aln.diagonal >= 0) { qUS = aln.start + (int) dist; qUE = aln.end + (int) dist; dbUS = aln.start; dbUE = aln.end; }
                 else { qUS = aln.start; qUE = aln.end; dbUS = aln.start + (int) dist; dbUE = aln.end + (int) dist; }
-                Result res; int aaIds = 0; unsigned btLen = 0; bool haveCigar = true;
-                int score1, qs1, qe1, ds1, de1;
+                Pending h; h.dbKey = dbKey; h.qL = qL; h.tL = tL; h.origLen = origLen; h.isReverse = isReverse; h.isIdentity = isIdentity; h.onDevice = false; h.aaIds = 0; h.btLen = 0;
                 if (qUE - qUS == origLen - 1 && dbUS == 0 && dbUE == tL - 1) {        // the seed covers the whole of both: no extension
-                    score1 = (int) aln.score; qs1 = qUS; qe1 = qUE; ds1 = dbUS; de1 = dbUE;
-                    for (int i = qUS; i <= qUE; i++) aaIds += qAln[i] == tNum[(size_t) (dbUS + (i - qUS))] ? 1 : 0;
-                    btLen = (unsigned) origLen;
+                    h.score1 = (int) aln.score; h.qs1 = qUS; h.qe1 = qUE; h.ds1 = dbUS; h.de1 = dbUE;
+                    for (int i = qUS; i <= qUE; i++) h.aaIds += qAln[i] == tNum[(size_t) (dbUS + (i - qUS))] ? 1 : 0;
+                    h.btLen = (unsigned) origLen;
+                } else if (collect) {
+                    // the device's hit: what the extension needs beyond the letters of the DB - the strand, the cut lengths, the seed's ends
+                    // and the letters behind both sequences in THIS thread's buffers (the first elements of the reversed arrays)
+                    static const uint8_t toDevice[5] = {0, 1, 3, 2, 4};             // A,C,T,G,X of the matrix -> A,C,G,T,N of the device DB
+                    cdm_align_hit d; d.query = (uint32_t) seq.idOf(queryKey); d.target = (uint32_t) dbId; d.q_len = (uint32_t) qL; d.t_len = (uint32_t) tL; d.q_end = qUE; d.t_end = dbUE;
+                    d.reverse = isReverse ? 1 : 0; d.wrapped = P.wrapped ? 1 : 0; d.stale_q = toDevice[qAln[queryLen] > 4 ? 4 : qAln[queryLen]]; d.stale_t = toDevice[tNum[tLen] > 4 ? 4 : tNum[tLen]];
+                    work.dev.push_back(d); h.onDevice = true;
                 } else {
+                    tRev.resize(tLen + 1);
+                    for (size_t i = 0; i <= tLen; i++) tRev[i] = tNum[tLen - i];
                     const int qStartRev = (qL - qUE) - 1, tStartRev = (tL - dbUE) - 1;
                     int qRevLen = qL - qStartRev;
                     if (P.wrapped && qRevLen > origLen) qRevLen = origLen;
@@ -395,52 +452,95 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
                         extz(qRevLen, qAlnRev + qStartRev, tL - tStartRev, tRev.data() + tStartRev, M.sub[0][0], M.sub[0][1], (int8_t) P.gapOpen, (int8_t) P.gapExtend, 64, P.zdrop, true, ezAlign);
                         cigar.assign(ezAlign.cigar.rbegin(), ezAlign.cigar.rend());
                     } else cigar = ezAlign.cigar;
-                    score1 = ezAlign.max; qs1 = qStartPos; qe1 = qStartPos + ezAlign.max_q; de1 = tStartPos + ezAlign.max_t; ds1 = tStartPos;
-                    int tp = ds1, qp = qs1;
+                    h.score1 = ezAlign.max; h.qs1 = qStartPos; h.qe1 = qStartPos + ezAlign.max_q; h.de1 = tStartPos + ezAlign.max_t; h.ds1 = tStartPos;
+                    int tp = h.ds1, qp = h.qs1;
                     for (uint32_t cg : cigar) {
                         const uint32_t op = cg & 0xf, len = cg >> 4;
                         for (uint32_t i = 0; i < len; i++) {
-                            if (op == 0) { if (tNum[(size_t) tp] == qAln[qp]) aaIds++; ++qp; ++tp; }
+                            if (op == 0) { if (tNum[(size_t) tp] == qAln[qp]) h.aaIds++; ++qp; ++tp; }
                             else if (op == 1) ++qp; else ++tp;
                         }
-                        btLen += len;
+                        h.btLen += len;
                     }
-                    haveCigar = true;
+                    work.extended++;
                 }
-                float qcov = computeCov((unsigned) qs1, (unsigned) qe1, (unsigned) qL);
-                if (P.wrapped) qcov = std::min(1.0f, qcov * 2);
-                float dbcov = computeCov((unsigned) ds1, (unsigned) de1, (unsigned) tL);
-                double evalue = 0; int bits = 0;
-                cdm_gapped_evalue(P.gapOpen, P.gapExtend, (double) score1, (double) origLen, dbRes, &evalue, &bits);
-                // ---- Matcher::getSWResult's tail
-                unsigned alnLength = (unsigned) std::max(abs(qe1 - qs1), abs(de1 - ds1)) + 1;
-                if (haveCigar) alnLength = btLen;
-                float seqId;
-                switch (P.seqIdMode) {
-                    case 1: seqId = static_cast<float>(aaIds) / static_cast<float>(std::min(origLen, tL)); break;
-                    case 2: seqId = static_cast<float>(aaIds) / static_cast<float>(std::max(origLen, tL)); break;
-                    default: seqId = static_cast<float>(aaIds) / static_cast<float>((int) alnLength);
-                }
-                res.dbKey = dbKey; res.score = bits; res.qcov = qcov; res.dbcov = dbcov; res.seqId = seqId; res.eval = evalue; res.alnLength = alnLength;
-                res.qStart = qs1; res.qEnd = qe1; res.qLen = (unsigned) origLen; res.dbLen = (unsigned) tL;
-                if (isReverse) { res.dbStart = de1; res.dbEnd = ds1; } else { res.dbStart = ds1; res.dbEnd = de1; }
-                if (isIdentity) { res.qcov = 1.0f; res.dbcov = 1.0f; res.seqId = 1.0f; }
-                const bool ok = isIdentity || (res.eval <= P.evalThr && res.seqId >= P.seqIdThr && hasCoverage(P.covThr, P.covMode, res.qcov, res.dbcov) && (int) res.alnLength >= P.alnLenThr);
-                if (ok) { results.push_back(res); passed++; rejected = 0; } else rejected++;
+                if (collect) { work.pend.push_back(h); continue; }
+                Result res;
+                if (finish(h, res)) { results.push_back(res); passed++; rejected = 0; } else rejected++;
             }
+            if (collect) { work.entries.push_back(std::make_pair(queryKey, (uint32_t) (work.pend.size() - pendAtEntry))); if (failCode) break; continue; }
             if (failCode) break;
-            if (results.size() > 1) std::sort(results.begin(), results.end(), compareHits);
-            for (const Result &r : results) {       // Matcher::resultToBuffer, no backtrace
-                char *w = buf;
-                w = utoa(r.dbKey, w); *w++ = '\t'; w = itoa(r.score, w); *w++ = '\t'; w = seqIdText(r.seqId, w); *w++ = '\t';
-                w += sprintf(w, "%.3E", r.eval); *w++ = '\t';
-                w = itoa(r.qStart, w); *w++ = '\t'; w = itoa(r.qEnd, w); *w++ = '\t'; w = itoa(r.qLen, w); *w++ = '\t';
-                w = itoa(r.dbStart, w); *w++ = '\t'; w = itoa(r.dbEnd, w); *w++ = '\t'; w = itoa(r.dbLen, w); *w++ = '\n';
-                out.append(buf, (size_t) (w - buf));
-            }
-            c.add(queryKey, out.data(), out.size(), 0);
+            emit(c, queryKey, results, out);
         }
+    };
+    // ---- the path.  CDM_ALIGN=device takes the device path, CDM_ALIGN=host or nothing the host path: where the two cross over has not been
+    // measured (profiles/align_device.txt), so no input is sent to the device unasked.  With --max-accept / --max-rejected set, which hits
+    // are processed depends on the results in front of them: the host's order, whatever the switch says.
+    const int want = cdm_align_mode();
+    if (want < 0) { *err = std::string("align: ") + cdm_last_error(); return 1; }
+    const bool timing = getenv("CDM_TIMING") != NULL;
+    const bool everyHit = P.maxAccept == (unsigned) INT_MAX && P.maxReject == (unsigned) INT_MAX;
+    const char *ordinal = getenv("CARPEDEAM_DEVICE");
+    cdm_ctx *ctx = NULL;
+    if (everyHit && want == 2) {
+        if (cdm_ctx_create(ordinal ? atoi(ordinal) : 0, &ctx) != CDM_OK) { *err = std::string("align: CDM_ALIGN=device: Can not initialise the MI355X device: ") + cdm_last_error(); return 1; }
     }
-    if (failCode) { *err = failure; return failCode; }
+    std::vector<ThreadWork> work((size_t) T);
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    if (!ctx) {
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+        for (int th = 0; th < T; th++) runChunk(th, false, work[(size_t) th]);
+        if (failCode) { *err = failure; return failCode; }
+        uint64_t hits = 0;
+        for (const ThreadWork &w : work) hits += w.extended;
+        if (timing) fprintf(stderr, "  align: path=host hits=%llu slices=0 rows=0 prepass=0.000 device=0.000 finish=%.3f s\n", (unsigned long long) hits, since(t0));
+    } else {
+        // the sequence DB goes up while the pre-pass runs
+        cdm_seqdb *db = NULL; int upRc = 0; std::string upErr;
+        struct Release { cdm_ctx *&ctx; cdm_seqdb *&db; ~Release() { if (db) cdm_seqdb_free(db); cdm_ctx_destroy(ctx); } } release{ctx, db};       // on every way out
+        std::thread up([&] {
+            std::vector<uint32_t> lens(seq.size());
+            for (size_t i = 0; i < seq.size(); i++) lens[i] = seq.len[i] >= 2 ? (uint32_t) (seq.len[i] - 2) : 0;
+            upRc = cdm_seqdb_upload(ctx, seq.data(), seq.off.data(), lens.data(), seq.key.data(), seq.ext.data(), seq.size(), &db);
+            if (upRc != CDM_OK) upErr = cdm_last_error();
+        });
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+        for (int th = 0; th < T; th++) runChunk(th, true, work[(size_t) th]);
+        up.join();
+        if (failCode) { *err = failure; return failCode; }
+        if (upRc != CDM_OK) { *err = "align: Can not load the sequence DB: " + upErr; return 1; }
+        const double prepassS = since(t0);
+        std::vector<cdm_align_hit> all; std::vector<size_t> base((size_t) T);
+        for (int th = 0; th < T; th++) { base[(size_t) th] = all.size(); all.insert(all.end(), work[(size_t) th].dev.begin(), work[(size_t) th].dev.end()); }
+        std::vector<cdm_align_result> res(all.size());
+        cdm_align_params ap; ap.gap_open = P.gapOpen; ap.gap_extend = P.gapExtend; ap.zdrop = P.zdrop; ap.band = 64;
+        uint64_t stats[4] = {0, 0, 0, 0};
+        const auto t1 = std::chrono::steady_clock::now();
+        if (cdm_align_hits(ctx, db, &ap, all.data(), all.size(), res.data(), stats) != CDM_OK) { *err = std::string("align: ") + cdm_last_error(); return 1; }
+        const double deviceS = since(t1);
+        const auto t2 = std::chrono::steady_clock::now();
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+        for (int th = 0; th < T; th++) {
+            ThreadWork &w = work[(size_t) th];
+            size_t k = base[(size_t) th], next = 0;
+            std::vector<Result> results; std::string out;
+            for (const std::pair<uint32_t, uint32_t> &entry : w.entries) {
+                results.clear();
+                for (uint32_t i = 0; i < entry.second; i++) {
+                    Pending &h = w.pend[next++];
+                    if (h.onDevice) {
+                        const cdm_align_result &r = res[k++];
+                        h.score1 = r.score; h.qs1 = r.q_start; h.qe1 = r.q_end; h.ds1 = r.t_start; h.de1 = r.t_end; h.aaIds = r.identities; h.btLen = (unsigned) r.columns;
+                    }
+                    Result rec;
+                    if (finish(h, rec)) results.push_back(rec);
+                }
+                emit(chunks[(size_t) th], entry.first, results, out);
+            }
+        }
+        if (timing) fprintf(stderr, "  align: path=device hits=%llu slices=%llu rows=%llu prepass=%.3f device=%.3f finish=%.3f s (kernels %.3f s, %llu trace bytes in the largest slice)\n",
+                            (unsigned long long) all.size(), (unsigned long long) stats[0], (unsigned long long) stats[1], prepassS, deviceS, since(t2), (double) stats[3] / 1e6, (unsigned long long) stats[2]);
+    }
     return mmdbWriteChunks(outPath, 5, chunks, err) ? 0 : 1;
 }

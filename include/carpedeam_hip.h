@@ -286,6 +286,45 @@ int cdm_gapped_evalue(int gap_open, int gap_extend, double raw_score, double que
 int cdm_bit_score(double raw_score);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * align (linclust's gapped step on the assembled contigs; nucleotides, no backtrace output).  Replaces what
+ * BandedNucleotideAligner::align does between the ungapped seed and the result (lib/mmseqs/src/alignment/
+ * BandedNucleotideAligner.cpp:138-255 over lib/mmseqs/lib/ksw2/ksw2_extz2_sse.cpp:45-284) for a batch of independent hits: the reverse
+ * extension from the seed's end, the forward one from the start that found, the second reverse run where the first reached further,
+ * identities and columns of the edit script.  csrc/align.hip; the seed, E-values, filters and the text stay with the caller
+ * (csrc/host/align.cpp).  nucleotide.out's scores (+2 / -3, N a wildcard), band 64.
+ *
+ * A hit: query and target by index; reverse = the query is reverse-complemented; wrapped = --wrapped-scoring 1 (the query is its
+ * sequence twice); q_len / t_len = the lengths as aligned (the doubled query cut at 2 x --max-seq-len, the target at its cut);
+ * q_end / t_end = the seed's last column in the aligned query / the target.  The reference runs its reverse extension on arrays
+ * shifted by one letter, whose first element is the byte behind the sequence in the worker thread's buffer - left there by an
+ * earlier, longer sequence: stale_q / stale_t are those letters (A,C,G,T = 0..3, 4 = N; 0 in a fresh buffer).
+ * stats (may be NULL): [0] slices the hits ran in, [1] anti-diagonal rows computed, [2] trace bytes of the largest slice,
+ * [3] microseconds from the first launch to the last slice's end.
+ */
+typedef struct cdm_align_params {
+    int32_t gap_open, gap_extend; /* --gap-open, --gap-extend */
+    int32_t zdrop;                /* --zdrop */
+    int32_t band;                 /* 64 */
+} cdm_align_params;
+typedef struct cdm_align_hit {
+    uint32_t query, target;
+    uint32_t q_len, t_len;
+    int32_t q_end, t_end;
+    uint8_t reverse, wrapped, stale_q, stale_t;
+} cdm_align_hit;
+typedef struct cdm_align_result {
+    int32_t score;                  /* raw score of the gapped alignment */
+    int32_t q_start, q_end, t_start, t_end;
+    int32_t identities, columns;    /* aaIds and the length of the edit script */
+    int32_t rows;                   /* anti-diagonal rows the hit's extensions computed */
+} cdm_align_result;
+int cdm_align_hits(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_align_params *par, const cdm_align_hit *hits, uint64_t n,
+                   cdm_align_result *results, uint64_t *stats);
+/* the CDM_ALIGN switch of the `align` module from the library's snapshot of the environment: 0 unset (the module takes its host
+ * path), 1 host, 2 device; CDM_ERR_INVALID for any other value */
+int cdm_align_mode(void);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ancient_correction.  Replaces the loop at src/assembler/correction.cpp:200-476 (mostLikeliBaseRead :7-123).
  * Output: a new sequence DB with identical keys/lengths/flags and corrected bases.
  */
