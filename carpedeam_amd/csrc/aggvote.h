@@ -288,7 +288,7 @@ struct VoteEntArgs {
     // the target is cont[1]; only if cont[2] is set does the scan go on into the left-over tuples after them.  NULL on one device.
     const uint32_t *cont = nullptr;
 };
-constexpr int HEAD_WORDS = 2048;        // = kmermatch.hip CONT_CAP: the words of a head the ranks exchange
+constexpr int HEAD_WORDS = 2048;        // = kmer_vote.h CONT_CAP: the words of a head the ranks exchange
 // The head of a rank's entries: from its first entry on while the member id stays the same, whatever the representative (what a scan
 // coming in from the rank in front runs through, kmermatcher.cpp:875-887).  out[0] = words (2 per entry; HEAD_WORDS + 1: longer than
 // the list), out[1] = that id, out[2] = 1 if the head is everything this rank holds, out[3..] the entries, out[HEAD_WORDS + 3] = the

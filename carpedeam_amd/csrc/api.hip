@@ -1,5 +1,5 @@
 // C-ABI entry points: context, sequence DB (upload / 2-bit packing / download), hit and alignment containers.
-// Stage kernels live in correct.hip, rescore.hip, kmermatch.hip, extend.hip, synth.hip.
+// Stage kernels live in correct.hip, rescore.hip, kmermatch.hip (with its kmer_*.h stage headers), extend.hip, synth.hip.
 #include <cstdarg>
 #include <atomic>
 #include <cstring>

@@ -22,7 +22,7 @@ float cdmPoolHeadroomSwap(float f);      // sets the allocator's head room facto
 const char *cdmGetenv(const char *name);
 template <typename T> inline hipError_t cdmMalloc(T **p, size_t bytes) { return cdmMallocRaw(reinterpret_cast<void **>(p), bytes); }
 
-// most left-over tuples the reference's last per-target scan may run over on the device (kmermatch.hip k_stale_tail; dist.hip)
+// most left-over tuples the reference's last per-target scan may run over on the device (kmer_group.h k_stale_tail; dist.hip)
 constexpr int CDM_STALE_MAX = 62;
 // RAII device buffer from the caching allocator (freed on every exit path of a stage function)
 // experiments: dynamic LDS (bytes, from the environment) added to a launch to lower its occupancy

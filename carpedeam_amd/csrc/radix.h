@@ -34,6 +34,14 @@ static_assert(NT >= BINS && TILE <= 65536, "radix pass geometry");
 constexpr int LB = CDM_RX_LB;
 constexpr unsigned long long ST_AGG = 1ull << 62, ST_PREFIX = 2ull << 62, ST_MASK = (1ull << 62) - 1ull;
 
+// the two buffers a sort alternates between: where the data is now, and the other one
+template <typename T> struct DoubleBuf {
+    T *cur = nullptr, *alt = nullptr;
+    DoubleBuf() = default;
+    DoubleBuf(T *c, T *a) : cur(c), alt(a) {}
+    T *current() const { return cur; }
+    T *alternate() const { return alt; }
+};
 struct NoValue {};      // V = NoValue: keys only
 template <typename V> struct HasValue { static constexpr bool value = true; };
 template <> struct HasValue<NoValue> { static constexpr bool value = false; };
@@ -79,7 +87,7 @@ __global__ __launch_bounds__(BINS) void k_rx_offsets(unsigned long long *hist, i
 //               empty slot.  The pass is the most significant one: it drops the empty slots, partitions the others by the head digit (the
 //               `bits` key bits from `shift` on) and writes 8-byte SLOT TUPLES [ key bits below shift : 31 | strand : 1 | slot index : 32 ] -
 //               the head digit is implied by where a tuple lands (segment = digit), the slot index says which sequence and position the
-//               k-mer came from (the slots are laid out by sequence: kmermatch.hip).  Keys only.
+//               k-mer came from (the slots are laid out by sequence: kmer_tuple.h LayoutSlot).  Keys only.
 //   PASS_SEG    the array is cut into BINS segments (seg[0 .. BINS]: the head pass's digits); every segment is sorted on its own, stable:
 //               tiles do not cross a segment (segTile[d] = first tile of segment d), the chained scan starts afresh at a segment's first
 //               tile, digitBase is [segment][digit]
@@ -356,6 +364,14 @@ inline int sortPairs(hipStream_t s, int cuCount, K *k0, K *k1, V *v0, V *v1, uin
     }
     if (e != hipSuccess) { cdm_set_error("radix sort failed: %s", hipGetErrorString(hipGetLastError())); return CDM_ERR_HIP; }
     return CDM_OK;
+}
+// ... with the buffer pairs as DoubleBufs: current() holds the input, and the result when the call returns
+template <typename K, typename V>
+inline int sortPairs(hipStream_t s, int cuCount, DoubleBuf<K> &k, DoubleBuf<V> &v, uint64_t n, int beginBit, int endBit, float *passMs = nullptr) {
+    bool inFirst = true;
+    const int rc = sortPairs<K, V>(s, cuCount, k.cur, k.alt, v.cur, v.alt, n, beginBit, endBit, inFirst, passMs);
+    if (!inFirst) { std::swap(k.cur, k.alt); std::swap(v.cur, v.alt); }
+    return rc;
 }
 
 // keys only

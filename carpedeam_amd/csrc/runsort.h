@@ -33,7 +33,7 @@ template <> struct RunBitsOf<8> { typedef uint8_t T; };
 typedef RunBitsOf<RUN_ITEMS>::T RunBits;
 constexpr int RUN_CNT_BITS = 13;                                                 // a record's length <= RUN_TILE
 
-// Group keys come in two forms (kmermatch.hip, packGroupKey).  Narrow: [rep | id | diagonal | strand] in one word - while that fits 63
+// Group keys come in two forms (kmer_group.h, packGroupKey).  Narrow: [rep | id | diagonal | strand] in one word - while that fits 63
 // bits.  Wide (any DB: 2^32 sequences, contigs of millions of letters): [START | DROPPED | id | diagonal | strand] - the representative
 // is not in the member's key.  It does not have to be: the first tuple of a k-mer run IS the representative's own tuple, so the first
 // slot of every run with members carries GK_START and, in its id field, the representative - with GK_DROPPED if that tuple itself is

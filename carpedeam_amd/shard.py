@@ -23,7 +23,7 @@ import threading
 
 import numpy as np
 
-STALE_MAX = 62          # csrc/kmermatch.hip
+STALE_MAX = 62          # csrc/common.h CDM_STALE_MAX (csrc/kmer_group.h k_stale_tail)
 STALE_LEN = 67          # [0] count, [1] sequence id, [2..63] positions, [66] the scan reached the end of the range
 
 
@@ -72,7 +72,7 @@ def combine_stale(lists, holder):
 
 
 def build_cont(rank, counts, last_targets, heads):
-    """What the per-target scan of rank `rank`'s last segment runs into (VoteArgs::cont of csrc/kmermatch.hip): the heads of the
+    """What the per-target scan of rank `rank`'s last segment runs into (VoteArgs::cont of csrc/kmer_vote.h): the heads of the
     later ranks' sorted arrays while they carry the same target id and are consumed completely; [0] entries, [1] the target id,
     [2] = 1 if the scan then reaches the left-over list, [3..] entries.  None: no tuples on this rank."""
     if counts[rank] == 0:

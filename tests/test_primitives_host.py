@@ -60,7 +60,7 @@ LAYOUT_V = {"LayoutWideT": "u64", "LayoutHuge": "u64", "LayoutPacked": "u32", "L
 def product_instantiations():
     """(primitive, types...) of every rx::sortPairs / sortKeys / compactPairs and cdmscan:: call with explicit template arguments in
     carpedeam_amd/csrc; a layout's `typedef ... V` stands for each of its types"""
-    km = open(os.path.join(CSRC, "kmermatch.hip")).read()
+    km = open(os.path.join(CSRC, "kmer_tuple.h")).read()
     vs = set()
     for name, v in re.findall(r"struct (Layout\w+) \{\s*typedef (\w+) V;", km):
         assert LAYOUT_V.get(name) == TYPE_NAMES[v], "layout %s has V = %s: tell LAYOUT_V, and cover the type" % (name, v)
