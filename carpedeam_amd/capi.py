@@ -78,7 +78,7 @@ class AncientParams(C.Structure):
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
-    "cdm_seqdb_download", "cdm_seqdb_download_stream", "cdm_seqdb_free", "cdm_seqdb_select_ext", "cdm_seqdb_words", "cdm_seqdb_copy_packed", "cdm_seqdb_from_packed", "cdm_damage_load", "cdm_damage_get", "cdm_kmermatch", "cdm_hits_upload", "cdm_hits_count",
+    "cdm_seqdb_download", "cdm_seqdb_download_stream", "cdm_seqdb_free", "cdm_seqdb_select_ext", "cdm_seqdb_select_assembled", "cdm_seqdb_index_copy", "cdm_seqdb_words", "cdm_seqdb_copy_packed", "cdm_seqdb_from_packed", "cdm_damage_load", "cdm_damage_get", "cdm_kmermatch", "cdm_hits_upload", "cdm_hits_count",
     "cdm_hits_download", "cdm_hits_free", "cdm_rescore", "cdm_alns_upload", "cdm_alns_count", "cdm_alns_download", "cdm_alns_free",
     "cdm_evalue", "cdm_bit_score", "cdm_gapped_evalue", "cdm_correct", "cdm_extend",
     "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kpart_free", "cdm_dev_copy",
@@ -147,6 +147,8 @@ def lib():
             f.argtypes = [vp]
             f.restype = None
         l.cdm_seqdb_select_ext.argtypes = [vp, vp, C.POINTER(vp)]
+        l.cdm_seqdb_index_copy.argtypes = [vp, vp, C.POINTER(vp)]
+        l.cdm_seqdb_select_assembled.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(vp), u64p]
         l.cdm_seqdb_words.argtypes = [vp]
         l.cdm_seqdb_words.restype = C.c_uint64
         l.cdm_seqdb_copy_packed.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -516,6 +518,21 @@ class Ctx:
         split = np.zeros(max(db.n, 1), dtype=np.uint32)
         _check(lib().cdm_cyclecheck(self.h, db.h, max_seq_len, 1 if chop_cycle else 0, C.byref(c), C.byref(r), split.ctypes.data))
         return SeqDb(self, c), SeqDb(self, r), split[:db.n]
+
+    def index_copy(self, db):
+        """keys, lengths and flags of db as a DB without letters (the `source` of select_assembled)"""
+        h = C.c_void_p()
+        _check(lib().cdm_seqdb_index_copy(self.h, db.h, C.byref(h)))
+        return SeqDb(self, h)
+
+    def select_assembled(self, result, source, min_len):
+        """the workflow's selection of the assembled contigs (data/nuclassemble.sh:214-233): the entries of `result` that outgrew the
+        entry of the same key in `source` and hold at least min_len letters, as a new device DB (possibly empty)"""
+        h, kept = C.c_void_p(), C.c_uint64(0)
+        _check(lib().cdm_seqdb_select_assembled(self.h, result.h, source.h, min_len, C.byref(h), C.byref(kept)))
+        db = SeqDb(self, h)
+        assert db.n == kept.value
+        return db
 
     def from_packed_ext(self, codes_ptr, nmask_ptr, len_ptr, key_ptr, ext_ptr, n, words):
         h = C.c_void_p()

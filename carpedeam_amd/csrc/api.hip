@@ -610,6 +610,71 @@ extern "C" int cdm_seqdb_select_ext(cdm_ctx *ctx, const cdm_seqdb *db, cdm_seqdb
     if (n) hipLaunchKernelGGL(k_sel_from_ext, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, db->len, db->ext, n, sel.p);
     return cdm_seqdb_select(ctx, db, sel.p, 1, out);
 }
+// ---- the workflow's two selections of the assembled contigs (data/nuclassemble.sh:214-233) on a resident DB.  The script joins the
+// index of the result with the index of the source DB on the key and keeps `$3 > $7`, then `$3 > thr + 1`, where column 3 of an index
+// is the entry's length: the sequence plus "\n\0", i.e. len + 2.  The +2 stands on both sides of the first comparison and falls out:
+// len(result) > len(source).  In the second, len + 2 > thr + 1 is len > thr - 1, for integers len >= thr.  A result key the source
+// does not hold is not printed by the join: dropped.  The kept entries keep their keys, wasExtended flags, N and raw planes.
+// The source is read for its keys and lengths alone: cdm_seqdb_index_copy gives a DB of just those (and the flags), so that a caller
+// need not keep the letters of the DB it started from resident while that DB grows into the result.
+extern "C" int cdm_seqdb_index_copy(cdm_ctx *ctx, const cdm_seqdb *db, cdm_seqdb **out) {
+    if (!ctx || !db || !out) { cdm_set_error("cdm_seqdb_index_copy: NULL argument"); return CDM_ERR_INVALID; }
+    CDM_HIP(hipSetDevice(ctx->device));
+    cdm_seqdb *o = nullptr;
+    if (int rc = cdm_seqdb_alloc(ctx, db->n, &o)) return rc;
+    hipStream_t s = ctx->stream;
+    o->residues = db->residues; o->maxLen = db->maxLen;      // (no letters: words = 0, codes / nmask / raw stay NULL)
+    CDM_HIP(hipMemsetAsync(o->woff, 0, (db->n + 1) * 4, s));
+    CDM_HIP(hipMemsetAsync(o->hasN, 0, db->n + 8, s));
+    if (db->n) {
+        CDM_HIP(hipMemcpyAsync(o->len, db->len, db->n * 4, hipMemcpyDeviceToDevice, s));
+        CDM_HIP(hipMemcpyAsync(o->key, db->key, db->n * 4, hipMemcpyDeviceToDevice, s));
+        CDM_HIP(hipMemcpyAsync(o->ext, db->ext, db->n, hipMemcpyDeviceToDevice, s));
+    }
+    CDM_HIP(hipStreamSynchronize(s));
+    *out = o;
+    return CDM_OK;
+}
+namespace {
+__global__ void k_keys_ascend(const uint32_t *__restrict__ key, uint32_t n, unsigned int *__restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i + 1 < n && key[i] >= key[i + 1]) atomicOr(bad, 1u);
+}
+// sel[i] = len[i] if result entry i grew beyond its source entry and is long enough, else 0xFFFFFFFF; the source length by binary search
+// on the source's ascending keys
+__global__ void k_sel_assembled(const uint32_t *__restrict__ len, const uint32_t *__restrict__ key, uint32_t n, const uint32_t *__restrict__ srcKey,
+                                const uint32_t *__restrict__ srcLen, uint32_t m, uint32_t minLen, uint32_t *__restrict__ sel) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = key[i], L = len[i];
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (srcKey[mid] < k) lo = mid + 1; else hi = mid; }
+    const bool keep = lo < m && srcKey[lo] == k && L > srcLen[lo] && L >= minLen && L != 0xFFFFFFFFu;
+    sel[i] = keep ? L : 0xFFFFFFFFu;
+}
+}  // namespace
+extern "C" int cdm_seqdb_select_assembled(cdm_ctx *ctx, const cdm_seqdb *result, const cdm_seqdb *source, uint32_t min_len, cdm_seqdb **out, uint64_t *n_kept) {
+    if (!ctx || !result || !source || !out) { cdm_set_error("cdm_seqdb_select_assembled: NULL argument"); return CDM_ERR_INVALID; }
+    CDM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint32_t n = (uint32_t) result->n, m = (uint32_t) source->n;
+    DevBuf<uint32_t> sel; DevBuf<unsigned int> bad;
+    if (!sel.alloc((size_t) n + 1) || !bad.alloc(1)) { cdm_set_error("cdm_seqdb_select_assembled: out of device memory"); return CDM_ERR_HIP; }
+    unsigned int unsorted = 0;
+    CDM_HIP(hipMemsetAsync(bad.p, 0, 4, s));
+    if (m > 1) hipLaunchKernelGGL(k_keys_ascend, dim3((m + 255) / 256), dim3(256), 0, s, source->key, m, bad.p);
+    CDM_HIP(hipMemcpyAsync(&unsorted, bad.p, 4, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipStreamSynchronize(s));
+    if (unsorted) { cdm_set_error("cdm_seqdb_select_assembled: the keys of the source DB do not ascend strictly (a sequence DB is ordered by key)"); return CDM_ERR_INVALID; }
+    if (n) hipLaunchKernelGGL(k_sel_assembled, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t *) result->len, (const uint32_t *) result->key, n, (const uint32_t *) source->key, (const uint32_t *) source->len, m, min_len, sel.p);
+    CDM_LAUNCH_CHECK();
+    cdm_seqdb *o = nullptr;
+    const int rc = cdm_seqdb_select(ctx, result, sel.p, -1, &o);
+    if (rc != CDM_OK) return rc;
+    *out = o;
+    if (n_kept) *n_kept = o->n;
+    return CDM_OK;
+}
 namespace {
 __global__ void k_raw_flags(const uint8_t *__restrict__ hasN, uint64_t n, uint8_t *__restrict__ flags) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;

@@ -31,7 +31,7 @@
 #define CDM_EXIT_UNSUPPORTED 77
 
 static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_correction", "ancient_read_assemble", "ancient_contig_merge", "cyclecheck",
-                                    "createdb", "createhdb", "convert2fasta", "ancient_reads_loop", "mergereads",
+                                    "createdb", "createhdb", "convert2fasta", "ancient_reads_loop", "ancient_assemble_fused", "mergereads",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

@@ -22,6 +22,7 @@
 #include <numeric>
 #include <omp.h>
 #include <unistd.h>
+#include <dirent.h>
 #include <sys/stat.h>
 #include <fcntl.h>
 #include <string>
@@ -79,7 +80,8 @@ Args parse(int argc, char **argv) {
 // Per-module flag tables (the reference's own lists: lib/mmseqs/src/commons/Parameters.cpp:871-892 kmermatcher, :422-439
 // rescorediagonal, src/commons/LocalParameters.h:155-171 assembleresults = ancient_correction / ancient_read_assemble).
 //   'U' used by the MI355X path;  'N' accepted, no effect on this path in the reference either (or only on resources);
-//   'V' accepted only with one of the listed values (anything else would be computed differently: refused).
+//   'V' accepted only with one of the listed values (anything else would be computed differently: refused);
+//   'R' a flag the reference's list for the command knows and this path does not handle: refused whatever its value.
 // A flag that is not in the module's list is an error, as in Parameters::parseParameters (:1703 "Unrecognized parameter").
 struct FlagSpec { const char *name; char kind; const char *allowed; const char *why; };
 const FlagSpec KMERMATCHER_FLAGS[] = {
@@ -117,6 +119,7 @@ void checkFlags(const char *module, const Args &a, const FlagSpec *spec, const c
         bool known = f->name != NULL;
         for (const char *const *e = extra; !known && e && *e; e++) known = kv.first == *e;
         if (!known) die("Unrecognized parameter \"" + kv.first + "\"");
+        if (f->name && f->kind == 'R') unsupported(std::string(module) + ": " + kv.first + " is not supported by the MI355X path (" + f->why + ")");
         if (f->name && f->kind == 'V') {
             const std::string al = f->allowed;
             const bool ok = (al.size() >= 2 && al[0] == '*') ? kv.second.find(al.substr(1, al.size() - 2)) != std::string::npos : kv.second == al;
@@ -752,6 +755,21 @@ struct SideThread {
     void commit() { if (th.joinable()) { th.join(); if (ok) sideCommit(path, &hdr); } }
 };
 
+// the modules' parameters from their flags (kmermatcher; rescorediagonal's Hamming mode): ancient_assemble_fused reads them the same way
+cdm_kmer_params kmerParams(Args &a) {
+    cdm_kmer_params p;
+    p.kmer_size = (int) iflag(a, "-k", 15); p.kmers_per_seq = (int) iflag(a, "--kmer-per-seq", 21); p.kmers_per_seq_scale = fflag(a, "--kmer-per-seq-scale", 0.2f);
+    p.hash_shift = (uint64_t) iflag(a, "--hash-shift", 67); p.ignore_multi_kmer = (int) iflag(a, "--ignore-multi-kmer", 0);
+    p.include_only_extendable = (int) iflag(a, "--include-only-extendable", 0); p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.8f);
+    return p;
+}
+cdm_hamming_params hammingParams(Args &a, bool reversePrefilter) {
+    cdm_hamming_params p;
+    p.seq_id_thr = fflag(a, "--min-seq-id", 0.0f); p.eval_thr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
+    p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.0f); p.seq_id_mode = (int) iflag(a, "--seq-id-mode", 0); p.min_aln_len = (int) iflag(a, "--min-aln-len", 0);
+    p.reverse_prefilter = reversePrefilter;
+    return p;
+}
 int kmermatcher(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam kmermatcher <i:sequenceDB> <o:prefilterDB>");
     checkFlags("kmermatcher", a, KMERMATCHER_FLAGS);
@@ -764,10 +782,7 @@ int kmermatcher(Args &a) {
     if (in.fromSide) { if ((seq.dbtype & 0x7FFFFFFF) != 1) unsupported("The MI355X path works on nucleotide sequence DBs only"); if (!importSeqSide(ctx, in.side, &db)) die(std::string("Can not load the sequence DB: ") + cdm_last_error()); }
     else db = uploadSeqDb(ctx, seq);
     laps.lap("sequences up");
-    cdm_kmer_params p;
-    p.kmer_size = (int) iflag(a, "-k", 15); p.kmers_per_seq = (int) iflag(a, "--kmer-per-seq", 21); p.kmers_per_seq_scale = fflag(a, "--kmer-per-seq-scale", 0.2f);
-    p.hash_shift = (uint64_t) iflag(a, "--hash-shift", 67); p.ignore_multi_kmer = (int) iflag(a, "--ignore-multi-kmer", 0);
-    p.include_only_extendable = (int) iflag(a, "--include-only-extendable", 0); p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.8f);
+    cdm_kmer_params p = kmerParams(a);
     cdm_hits *hits = NULL;
     check(cdm_kmermatch(ctx, db, &p, &hits), "kmermatcher");
     HVec<uint64_t> off(seq.size() + 1); HVec<cdm_hit> rec(cdm_hits_count(hits));
@@ -802,10 +817,7 @@ int rescorediagonal(Args &a) {
         dev.join(); cdm_ctx *ctx = dev.ctx; cdm_seqdb *db = dev.db;
         cdm_hits *hits = NULL, *kept = NULL;
         check(cdm_hits_upload(ctx, db, off.data(), rec.data(), &hits), "upload");
-        cdm_hamming_params p;
-        p.seq_id_thr = fflag(a, "--min-seq-id", 0.0f); p.eval_thr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
-        p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.0f); p.seq_id_mode = (int) iflag(a, "--seq-id-mode", 0); p.min_aln_len = (int) iflag(a, "--min-aln-len", 0);
-        p.reverse_prefilter = (pref.dbtype & 0x7FFFFFFF) == 14;
+        cdm_hamming_params p = hammingParams(a, (pref.dbtype & 0x7FFFFFFF) == 14);
         check(cdm_rescore_hamming(ctx, db, hits, &p, &kept), "rescorediagonal");
         HVec<uint64_t> koff(seq.size() + 1); HVec<cdm_hit> krec(cdm_hits_count(kept));
         check(cdm_hits_download(ctx, kept, koff.data(), krec.data()), "download");
@@ -1019,36 +1031,38 @@ size_t readPairs(const char *module, const std::vector<std::string> &files, std:
     return total;
 }
 
-int readsLoop(Args &a) {
-    if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
+// the workflow's own flags for the reads loop (src/commons/LocalParameters.h:283-318) on top of the stage lists
+const char *const LOOP_FLAGS[] = {"--k-ancient-reads", "--kmer-per-seq-ancient", "--kmer-per-seq-scale-ancient", "--hash-shift", "--include-only-extendable-ancient-reads",
+                                  "-e", "--num-iter-reads-only", "--shuffle", "--num-iterations", "--k-ancient-contigs", "--include-only-extendable-ancient-contigs",
+                                  "--cycle-check", "--chop-cycle", "--gpus", NULL};
+// What the loop leaves behind: the context, the final DB (the circular contigs not in it) and the circular contigs set aside - on the
+// host (`cyclic`), or, for a caller that goes on with them on the device (keepResident), as the device DBs of the iterations that found
+// them (`cyclicDev`) together with the keys and lengths of the DB the loop started from (`source`: the createdb / mergereads result,
+// without its letters - cdm_seqdb_index_copy).
+struct LoopEnd { cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL, *source = NULL; OutChunk cyclic; std::vector<cdm_seqdb *> cyclicDev; int dbtype = 1; };
+// The loop itself, shared by ancient_reads_loop and ancient_assemble_fused: input parsing or pair merging, the read and contig
+// iterations, the script's cyclecheck step and --gpus.  inputs: a sequence DB (fromDb), one reads file, or R1 R2 [R1 R2 ...];
+// defaultTotal: --num-iterations where the flag is not given (< 0: the read iterations only).
+void runLoop(const char *module, Args &a, const std::vector<std::string> &inputs, bool fromDb, long defaultTotal, bool keepResident, LoopEnd &E, Laps &laps) {
+    const std::string mod = module;
     // the contig iterations' buffers grow ~1.5x per iteration: head room in the device-memory cache lets them fit the previous iteration's blocks
     cdm_pool_headroom(getenv("CDM_POOL_HEADROOM") ? (float) atof(getenv("CDM_POOL_HEADROOM")) : 1.6f);
-    {   // the workflow's own flags for the reads loop (src/commons/LocalParameters.h:283-318) on top of the stage lists
-        static const char *const LOOP_FLAGS[] = {"--k-ancient-reads", "--kmer-per-seq-ancient", "--kmer-per-seq-scale-ancient", "--hash-shift", "--include-only-extendable-ancient-reads",
-                                                 "-e", "--num-iter-reads-only", "--shuffle", "--num-iterations", "--k-ancient-contigs", "--include-only-extendable-ancient-contigs",
-                                                 "--cycle-check", "--chop-cycle", "--gpus", NULL};
-        checkFlags("ancient_reads_loop", a, ANCIENT_FLAGS, LOOP_FLAGS);
-    }
     // input: a sequence DB, or - when there is no <input>.index - FASTA/FASTQ[.gz] reads, parsed and laid out as createdb would
     // (createdb.cpp:150-280, --shuffle 1 by default) and uploaded without a DB on disk in between; three or more positional arguments
     // without an index are paired-end reads R1 R2 [R1 R2 ...] OUT, merged on the device into the DB the loop runs on, with the keys,
     // the order and the wasExtended flags mergereads writes (the workflow's paired-end way in, guidedNuclAssemble.sh:28-32, where
     // --shuffle has no effect either)
     MmDb seq; std::string err;
-    int dbtype = 1;
-    cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL;
-    struct stat st;
-    Laps laps;
+    int &dbtype = E.dbtype;
+    cdm_ctx *&ctx = E.ctx; cdm_seqdb *&db = E.db;
     FastxDb fx;
-    const bool fromDb = stat((a.pos[0] + ".index").c_str(), &st) == 0;
-    const bool paired = !fromDb && a.pos.size() >= 3;
-    const std::string outPath = paired ? a.pos.back() : a.pos[1];
+    const bool paired = !fromDb && inputs.size() >= 2;
     std::vector<FastqReads> pr; std::vector<size_t> prPairs;
     if (paired) {
-        const std::vector<std::string> files(a.pos.begin(), a.pos.end() - 1);
-        if (files.size() % 2) die("ancient_reads_loop: " + std::to_string(files.size()) + " read files given: paired-end input takes R1 R2 [R1 R2 ...] <o:sequenceDB>");
+        const std::vector<std::string> &files = inputs;
+        if (files.size() % 2) die(mod + ": " + std::to_string(files.size()) + " read files given: paired-end input takes R1 R2 [R1 R2 ...]");
         // (refused here, before the reads are parsed: each rank would need the merged DB uploaded on its own)
-        if (iflag(a, "--gpus", 1) > 1) unsupported("ancient_reads_loop: --gpus > 1 with paired-end input is not supported by the MI355X path (merge the pairs with mergereads first)");
+        if (iflag(a, "--gpus", 1) > 1) unsupported(mod + ": --gpus > 1 with paired-end input is not supported by the MI355X path (merge the pairs with mergereads first)");
     }
     auto uploadTo = [&](cdm_ctx *c) -> cdm_seqdb * {       // (the same host copy serves every rank of a --gpus N run)
         if (fromDb) return uploadSeqDb(c, seq);
@@ -1057,14 +1071,14 @@ int readsLoop(Args &a) {
         return d;
     };
     if (fromDb) {
-        if (!seq.load(a.pos[0], &err)) die(err);
+        if (!seq.load(inputs[0], &err)) die(err);
         dbtype = seq.dbtype;
         laps.lap("DB files mapped");
     } else if (paired) {
-        if (readPairs("ancient_reads_loop", std::vector<std::string>(a.pos.begin(), a.pos.end() - 1), pr, prPairs) == 0) die("ancient_reads_loop: the read files hold no pair");
+        if (readPairs(module, inputs, pr, prPairs) == 0) die(mod + ": the read files hold no pair");
         laps.lap("reads files parsed");
     } else {
-        if (!readFastxAsDb(std::vector<std::string>(1, a.pos[0]), iflag(a, "--shuffle", 1) != 0, fx, &err)) die(err);
+        if (!readFastxAsDb(std::vector<std::string>(1, inputs[0]), iflag(a, "--shuffle", 1) != 0, fx, &err)) die(err);
         for (auto &l : fx.len) l -= 2;
         laps.lap("reads file parsed");
     }
@@ -1097,6 +1111,8 @@ int readsLoop(Args &a) {
         laps.lap("pairs merged into the DB");
     } else { db = uploadTo(ctx); laps.lap("sequences up"); }
     check(cdm_damage_load(ctx, a.flag.count("--ancient-damage") ? a.flag["--ancient-damage"].c_str() : ""), "Profile not 12 fields");
+    // (the selection of the assembled contigs compares with the lengths of this DB: its keys and lengths stay, its letters go with the first iteration)
+    if (keepResident) check(cdm_seqdb_index_copy(ctx, db, &E.source), "index of the source DB");
     cdm_kmer_params kp;
     kp.kmer_size = (int) iflag(a, "--k-ancient-reads", 20); kp.kmers_per_seq = (int) iflag(a, "--kmer-per-seq-ancient", 200);
     kp.kmers_per_seq_scale = fflag(a, "--kmer-per-seq-scale-ancient", 0.2f); kp.hash_shift = (uint64_t) iflag(a, "--hash-shift", 67);
@@ -1112,7 +1128,7 @@ int readsLoop(Args &a) {
     // ancient_correction, ancient_contig_merge, and the script's cyclecheck() (:19-60; --cycle-check / --chop-cycle, both on by default
     // as setNuclAssemblerWorkflowDefaults has them): circular contigs leave the loop, cut at their split diagonal, and join the output
     // at the end (concatdbs, :204-212)
-    const long total = std::max(iters, iflag(a, "--num-iterations", iters));
+    const long total = std::max(iters, iflag(a, "--num-iterations", defaultTotal < 0 ? iters : defaultTotal));
     cdm_kmer_params kc = kp;
     kc.kmer_size = (int) iflag(a, "--k-ancient-contigs", 22); kc.include_only_extendable = (int) iflag(a, "--include-only-extendable-ancient-contigs", 1);
     const float mergeThr = fflag(a, "--min-merge-seq-id", 0.99f);
@@ -1121,7 +1137,14 @@ int readsLoop(Args &a) {
     cdm_rescore_params rc = rp; cdm_ancient_params ac = ap;
     rc.seq_id_thr = ac.seq_id_thr = fflag(a, "--min-seqid-corr-contigs", 0.9f);
     const bool cycleCheck = iflag(a, "--cycle-check", 1) != 0, chopCycle = iflag(a, "--chop-cycle", 1) != 0;
-    OutChunk cyclic;
+    OutChunk &cyclic = E.cyclic;
+    // the circular contigs an iteration set aside: to the host, or kept on the device for the caller
+    auto setAside = [&](cdm_ctx *c, cdm_seqdb *cyc) {
+        if (cdm_seqdb_size(cyc)) fprintf(stderr, "         %llu circular contigs set aside\n", (unsigned long long) cdm_seqdb_size(cyc));
+        if (keepResident && cdm_seqdb_size(cyc)) { E.cyclicDev.push_back(cyc); return; }
+        appendEntries(c, cyc, cyclic);
+        cdm_seqdb_free(cyc);
+    };
     // --gpus N: the read iterations over N ranks = N host threads of this process, a device each; every rank holds the whole DB and
     // the library splits the work (cdm_reads_iteration_dist: kmermatcher by k-mer range, one all-to-all of group keys, the other stages
     // on the owned queries, the new DBs all-gathered - the single-device result), the contig iterations likewise since round 5
@@ -1161,11 +1184,8 @@ int readsLoop(Args &a) {
                 if (contigs && cycleCheck) {        // every rank holds the whole merged DB: the same check, the same rest on all of them; rank 0 keeps the circular contigs
                     cdm_seqdb *cyc = NULL, *rest = NULL;
                     check(cdm_cyclecheck(c, d, (uint32_t) std::min<uint64_t>(ap.max_seq_len, 0xFFFFFFFFull), chopCycle, &cyc, &rest, NULL), "cyclecheck");
-                    if (r == 0) {
-                        if (cdm_seqdb_size(cyc)) fprintf(stderr, "         %llu circular contigs set aside\n", (unsigned long long) cdm_seqdb_size(cyc));
-                        appendEntries(c, cyc, cyclic);
-                    }
-                    cdm_seqdb_free(cyc); cdm_seqdb_free(d);
+                    if (r == 0) setAside(c, cyc); else cdm_seqdb_free(cyc);
+                    cdm_seqdb_free(d);
                     d = rest;
                 }
             }
@@ -1202,29 +1222,44 @@ int readsLoop(Args &a) {
         if (contigs && cycleCheck) {
             cdm_seqdb *cyc = NULL, *rest = NULL;
             check(cdm_cyclecheck(ctx, db, (uint32_t) std::min<uint64_t>(ap.max_seq_len, 0xFFFFFFFFull), chopCycle, &cyc, &rest, NULL), "cyclecheck");
-            if (cdm_seqdb_size(cyc)) fprintf(stderr, "         %llu circular contigs set aside\n", (unsigned long long) cdm_seqdb_size(cyc));
-            appendEntries(ctx, cyc, cyclic);
-            cdm_seqdb_free(cyc); cdm_seqdb_free(db);
+            setAside(ctx, cyc);
+            cdm_seqdb_free(db);
             db = rest;
         }
     }
     laps.lap("iterations");
-    if (cyclic.key.empty()) { writeSeqDb(ctx, db, outPath, dbtype); laps.lap("sequences down, DB written"); }
-    else {   // concatdbs --preserve-keys of the linear and the circular contigs, written in key order
-        OutChunk all; appendEntries(ctx, db, all);
-        std::vector<std::pair<uint32_t, std::pair<const OutChunk *, size_t>>> order;
-        std::vector<size_t> offA(all.key.size() + 1, 0), offC(cyclic.key.size() + 1, 0);
-        for (size_t i = 0; i < all.key.size(); i++) { offA[i + 1] = offA[i] + all.len[i]; order.push_back({all.key[i], {&all, i}}); }
-        for (size_t i = 0; i < cyclic.key.size(); i++) { offC[i + 1] = offC[i] + cyclic.len[i]; order.push_back({cyclic.key[i], {&cyclic, i}}); }
-        std::stable_sort(order.begin(), order.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-        std::vector<OutChunk> merged(1);
-        for (const auto &o : order) {
-            const OutChunk &c = *o.second.first; const size_t i = o.second.second;
-            merged[0].add(o.first, c.data.data() + (&c == &all ? offA[i] : offC[i]), c.len[i] - 1, c.ext[i]);
-        }
-        if (!mmdbWriteChunks(outPath, dbtype, merged, &err)) die(err);
+}
+// concatdbs --preserve-keys of two sets of entries (the linear and the circular contigs), in key order
+void concatByKey(const OutChunk &all, const OutChunk &cyclic, OutChunk &merged) {
+    std::vector<std::pair<uint32_t, std::pair<const OutChunk *, size_t>>> order;
+    std::vector<size_t> offA(all.key.size() + 1, 0), offC(cyclic.key.size() + 1, 0);
+    for (size_t i = 0; i < all.key.size(); i++) { offA[i + 1] = offA[i] + all.len[i]; order.push_back({all.key[i], {&all, i}}); }
+    for (size_t i = 0; i < cyclic.key.size(); i++) { offC[i + 1] = offC[i] + cyclic.len[i]; order.push_back({cyclic.key[i], {&cyclic, i}}); }
+    std::stable_sort(order.begin(), order.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    for (const auto &o : order) {
+        const OutChunk &c = *o.second.first; const size_t i = o.second.second;
+        merged.add(o.first, c.data.data() + (&c == &all ? offA[i] : offC[i]), c.len[i] - 1, c.ext[i]);
     }
-    cdm_seqdb_free(db); cdm_ctx_destroy(ctx);
+}
+int readsLoop(Args &a) {
+    if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
+    checkFlags("ancient_reads_loop", a, ANCIENT_FLAGS, LOOP_FLAGS);
+    struct stat st;
+    Laps laps;
+    const bool fromDb = stat((a.pos[0] + ".index").c_str(), &st) == 0;
+    const bool paired = !fromDb && a.pos.size() >= 3;
+    const std::string outPath = paired ? a.pos.back() : a.pos[1];
+    LoopEnd E;
+    runLoop("ancient_reads_loop", a, paired ? std::vector<std::string>(a.pos.begin(), a.pos.end() - 1) : std::vector<std::string>(1, a.pos[0]), fromDb, -1, false, E, laps);
+    std::string err;
+    if (E.cyclic.key.empty()) { writeSeqDb(E.ctx, E.db, outPath, E.dbtype); laps.lap("sequences down, DB written"); }
+    else {   // concatdbs --preserve-keys of the linear and the circular contigs, written in key order
+        OutChunk all; appendEntries(E.ctx, E.db, all);
+        std::vector<OutChunk> merged(1);
+        concatByKey(all, E.cyclic, merged[0]);
+        if (!mmdbWriteChunks(outPath, E.dbtype, merged, &err)) die(err);
+    }
+    cdm_seqdb_free(E.db); cdm_ctx_destroy(E.ctx);
     return EXIT_SUCCESS;
 }
 }  // namespace
@@ -1384,6 +1419,261 @@ int createhdb(Args &a) {
     if (createhdbModule(a.pos[0], a.pos.size() > 2 ? a.pos[1] : "", a.pos.back(), &err)) die(err);
     return EXIT_SUCCESS;
 }
+
+// ---- ancient_assemble_fused: reads to contig FASTA in this one process.  `ancient_assemble` of the reference
+// (src/workflow/GuidedNuclassembler.cpp) is three drivers that write shell scripts and start some hundred module processes; here the
+// loop above runs first, then - on the DBs it left resident - the two selections of data/nuclassemble.sh:214-233
+// (cdm_seqdb_select_assembled), and on the selected contigs what data/guidedNuclAssemble.sh:180-218 runs: linclust
+// (lib/mmseqs/data/workflow/linclust.sh with CLUSTER_PAR, GuidedNuclassembler.cpp:33-40,176-181), result2repseq, createhdb, convert2fasta.
+// Only the selected contigs leave the device; the final DB of the loop is never written.  No script, no other process: the steps of the
+// tail are the module functions of this binary, each called with the parameter string the reference's drivers build for it (recorded
+// from the reference in tests/golden/fused/calls_*.json; tests/test_fused_cli.py compares) and read through the module's own flag table.
+// Not a module of the reference: `ancient_assemble` itself stays with the reference binary (host/front.c).
+//   CDM_FUSED_DRY_RUN=1 | cycle: the steps of the tail and their parameter strings on stdout, nothing run (paths under $TMP)
+#define FUSED_REFUSED(name) {name, 'R', 0, "a flag of the reference's ancient_assemble that ancient_assemble_fused does not take"}
+const FlagSpec FUSED_FLAGS[] = {
+    // the loop's (ANCIENT_FLAGS + LOOP_FLAGS)
+    {"--min-seq-id", 'U', 0, 0}, {"--max-seq-len", 'U', 0, 0}, {"--ext-random-align", 'U', 0, 0}, {"--excess-penalty", 'U', 0, 0}, {"--min-ryseq-id-corr-reads", 'U', 0, 0},
+    {"--likelihood-ratio-threshold", 'U', 0, 0}, {"--ancient-damage", 'U', 0, 0}, {"--unsafe", 'U', 0, 0}, {"--min-cov-safe", 'U', 0, 0}, {"--min-merge-seq-id", 'U', 0, 0},
+    {"--keep-target", 'N', 0, "not read by the modules of the loop"}, {"--min-seqid-corr-reads", 'N', 0, "not read by the modules of the loop"}, {"--min-seqid-corr-contigs", 'U', 0, 0},
+    {"--rescore-mode", 'V', "3", "re-alignment of parked candidates is end-to-end ungapped (ancientReadsResults.cpp:502)"},
+    {"--k-ancient-reads", 'U', 0, 0}, {"--kmer-per-seq-ancient", 'U', 0, 0}, {"--kmer-per-seq-scale-ancient", 'U', 0, 0}, {"--hash-shift", 'U', 0, 0},
+    {"--include-only-extendable-ancient-reads", 'U', 0, 0}, {"-e", 'U', 0, 0}, {"--num-iter-reads-only", 'U', 0, 0}, {"--shuffle", 'U', 0, 0}, {"--num-iterations", 'U', 0, 0},
+    {"--k-ancient-contigs", 'U', 0, 0}, {"--include-only-extendable-ancient-contigs", 'U', 0, 0}, {"--cycle-check", 'U', 0, 0}, {"--chop-cycle", 'U', 0, 0}, {"--gpus", 'U', 0, 0},
+    // the tail's
+    {"--min-contig-len", 'U', 0, 0}, {"--clust-min-seq-id", 'U', 0, 0}, {"--clust-min-cov", 'U', 0, 0}, {"--zdrop", 'U', 0, 0}, {"--threads", 'U', 0, 0}, {"--remove-tmp-files", 'U', 0, 0},
+    {"-v", 'U', 0, 0},
+    {"--cluster-mode", 'V', "2", "the redundancy reduction clusters greedily, linclust's mode for --cov-mode 1"}, {"--cov-mode", 'V', "1", "the workflow's coverage mode throughout"},
+    {"--gap-open", 'V', "5", "gapped E-values are known for the costs 5 / 2 only"}, {"--gap-extend", 'V', "2", "gapped E-values are known for the costs 5 / 2 only"},
+    {"-a", 'V', "0", "no backtrace output"}, {"--compressed", 'V', "0", "compressed DBs are not implemented"},
+    // known to the reference's list (LocalParameters.h guidedNuclAssembleworkflow), not handled here
+    FUSED_REFUSED("--alph-size"), FUSED_REFUSED("--spaced-kmer-mode"), FUSED_REFUSED("--spaced-kmer-pattern"), FUSED_REFUSED("--mask"), FUSED_REFUSED("--mask-lower-case"),
+    FUSED_REFUSED("--split-memory-limit"), FUSED_REFUSED("--add-self-matches"), FUSED_REFUSED("--seq-id-mode"), FUSED_REFUSED("--min-aln-len"), FUSED_REFUSED("--kmer-per-seq"),
+    FUSED_REFUSED("--kmer-per-seq-scale"), FUSED_REFUSED("--adjust-kmer-len"), FUSED_REFUSED("--include-only-extendable"), FUSED_REFUSED("--ignore-multi-kmer"), FUSED_REFUSED("-k"),
+    FUSED_REFUSED("-c"), FUSED_REFUSED("--min-length"), FUSED_REFUSED("--max-length"), FUSED_REFUSED("--max-gaps"), FUSED_REFUSED("--contig-start-mode"), FUSED_REFUSED("--contig-end-mode"),
+    FUSED_REFUSED("--orf-start-mode"), FUSED_REFUSED("--forward-frames"), FUSED_REFUSED("--reverse-frames"), FUSED_REFUSED("--translation-table"), FUSED_REFUSED("--translate"),
+    FUSED_REFUSED("--use-all-table-starts"), FUSED_REFUSED("--id-offset"), FUSED_REFUSED("--dbtype"), FUSED_REFUSED("--createdb-mode"), FUSED_REFUSED("--contig-output-mode"),
+    FUSED_REFUSED("--sub-mat"), FUSED_REFUSED("--db-load-mode"), FUSED_REFUSED("--delete-tmp-inc"), FUSED_REFUSED("--mpi-runner"), FUSED_REFUSED("--create-lookup"),
+    FUSED_REFUSED("--write-lookup"), FUSED_REFUSED("--filter-hits"), FUSED_REFUSED("--sort-results"), FUSED_REFUSED("--wrapped-scoring"), FUSED_REFUSED("--db-mode"),
+    FUSED_REFUSED("--min-ryseq-id"), {0, 0, 0, 0}};
+// one module call of the tail: positional arguments and the parameter string
+struct TailStep { std::string module; std::vector<std::string> pos; std::string flags; };
+Args stepArgs(const TailStep &s) {
+    Args a; a.pos = s.pos;
+    std::vector<std::string> tok; size_t at = 0;
+    while (at < s.flags.size()) { const size_t e = std::min(s.flags.find(' ', at), s.flags.size()); if (e > at) tok.push_back(s.flags.substr(at, e - at)); at = e + 1; }
+    for (size_t i = 0; i + 1 < tok.size(); i += 2) a.flag[tok[i]] = tok[i + 1];      // (every flag of these strings takes a value)
+    return a;
+}
+// the numbers as the reference's SSTR() prints them (an ostringstream's default notation: %g)
+std::string asG(double v) { char b[40]; snprintf(b, sizeof(b), "%g", v); return b; }
+// The tail as the reference runs it for these flags: linclust's own line first (the driver whose steps follow: listed, not run), then
+// linclust.sh:24-87 and guidedNuclAssemble.sh:190-215.  T: the command's directory.
+std::vector<TailStep> fusedTail(Args &a, const std::string &T, bool withCycle) {
+    // linclust is started with CLUSTER_PAR alone (guidedNuclAssemble.sh:186), the `reduceredundancy` list (LocalParameters.h:193-209):
+    // of the user's flags --clust-min-seq-id, --clust-min-cov, --max-seq-len, --zdrop, --threads and --remove-tmp-files reach it.  What
+    // that list does not carry - -e, --hash-shift, -v - its modules get with linclust's own defaults (0.001, 67, 3), whatever the
+    // user gave the workflow; the user's -v reaches result2repseq, createhdb and convert2fasta (THREADS_PAR, VERBOSITY_PAR).
+    const std::string sid = asG(fflag(a, "--clust-min-seq-id", 0.97f)), cov = asG(fflag(a, "--clust-min-cov", 0.99f)), ev = "0.001", hashShift = "67", lv = "3";
+    const std::string maxLen = std::to_string(iflag(a, "--max-seq-len", 200000)), zdrop = std::to_string(iflag(a, "--zdrop", 200));
+    const std::string threads = std::to_string(std::max(1, omp_get_max_threads())), v = a.flag.count("-v") ? a.flag["-v"] : "3", rm = std::to_string(iflag(a, "--remove-tmp-files", 0));
+    const std::string SUB = "--sub-mat nucl:nucleotide.out,aa:blosum62.out", TCV = "--threads " + threads + " --compressed 0 -v " + lv;
+    const std::string IN = T + "/nuclassembly", C = T + "/clu_tmp", STEP = C + "/input_step_redundancy", REP = T + "/nuclassembly_rep";
+    std::vector<TailStep> t;
+    t.push_back({"linclust", {IN, T + "/clu", C}, "--alph-size nucl:5,aa:13 --cluster-mode 2 -k 20 --kmer-per-seq 200 --kmer-per-seq-scale 0.200 --ignore-multi-kmer 1 --min-seq-id " + sid +
+                 " --cov-mode 1 -c " + cov + " --max-seq-len " + maxLen + " --wrapped-scoring 1 --gap-open 5 --gap-extend 2 --zdrop " + zdrop + " --threads " + threads + " --remove-tmp-files " + rm});
+    t.push_back({"kmermatcher", {IN, C + "/pref"}, SUB + " --alph-size nucl:5,aa:13 --min-seq-id " + sid + " --kmer-per-seq 200 --spaced-kmer-mode 0 --kmer-per-seq-scale 0.200 --adjust-kmer-len 0 --mask 0 "
+                 "--mask-lower-case 0 --cov-mode 1 -k 20 -c " + cov + " --max-seq-len " + maxLen + " --hash-shift " + hashShift + " --split-memory-limit 0 --include-only-extendable 0 --ignore-multi-kmer 1 " + TCV});
+    t.push_back({"rescorediagonal", {IN, IN, C + "/pref", C + "/pref_rescore1"}, SUB + " --rescore-mode 0 --wrapped-scoring 1 --filter-hits 0 -e " + ev + " -c " + cov + " -a 0 --cov-mode 1 --min-seq-id " + sid +
+                 " --min-aln-len 0 --seq-id-mode 0 --add-self-matches 0 --sort-results 0 --db-load-mode 0 " + TCV});
+    const std::string CLUST = "--cluster-mode 2 --max-iterations 1000 --similarity-type 2 " + TCV;
+    t.push_back({"clust", {IN, C + "/pref_rescore1", C + "/pre_clust"}, CLUST});
+    t.push_back({"createsubdb", {C + "/order_redundancy", IN, STEP}, "-v " + lv + " --subdb-mode 1"});
+    t.push_back({"createsubdb", {C + "/order_redundancy", C + "/pref", C + "/pref_filter1"}, "-v " + lv + " --subdb-mode 1"});
+    t.push_back({"filterdb", {C + "/pref_filter1", C + "/pref_filter2"}, "--filter-file " + C + "/order_redundancy " + TCV});
+    t.push_back({"align", {STEP, STEP, C + "/pref_filter2", C + "/aln"}, SUB + " -a 0 --alignment-mode 2 --alignment-output-mode 0 --wrapped-scoring 1 -e " + ev + " --min-seq-id " + sid +
+                 " --min-aln-len 0 --seq-id-mode 0 --alt-ali 0 -c " + cov + " --cov-mode 1 --max-seq-len " + maxLen + " --comp-bias-corr 1 --max-rejected 2147483647 --max-accept 2147483647 --add-self-matches 0 "
+                 "--db-load-mode 0 --pca 1 --pcb 1.5 --score-bias 0 --realign 0 --realign-score-bias -0.2 --realign-max-seqs 2147483647 --gap-open 5 --gap-extend 2 --zdrop " + zdrop + " " + TCV});
+    t.push_back({"clust", {STEP, C + "/aln", C + "/clust"}, CLUST});
+    t.push_back({"mergeclusters", {IN, T + "/clu", C + "/pre_clust", C + "/clust"}, TCV});
+    t.push_back({"result2repseq", {IN, T + "/clu", REP}, "--threads " + threads + " -v " + v});
+    if (withCycle) t.push_back({"createhdb", {REP, REP + "_cycle", REP}, "-v " + v});
+    else t.push_back({"createhdb", {REP, REP}, "-v " + v});
+    t.push_back({"convert2fasta", {REP, REP + ".fasta"}, "-v " + v});
+    return t;
+}
+// the first column of every line of an index file
+bool indexKeys(const std::string &path, std::vector<std::string> &lines, std::vector<uint32_t> &keys) {
+    FILE *f = fopen(path.c_str(), "r");
+    if (!f) return false;
+    char *line = NULL; size_t cap = 0;
+    while (getline(&line, &cap, f) != -1) { lines.push_back(line); keys.push_back((uint32_t) strtoul(line, NULL, 10)); }
+    free(line); fclose(f);
+    return true;
+}
+bool writeText(const std::string &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    return fclose(f) == 0 && ok;
+}
+// the command's own directory and what it holds (--remove-tmp-files 1): plain files and links, one level of sub-directories
+void removeOwnDir(const std::string &dir, int depth = 0) {
+    if (DIR *d = opendir(dir.c_str())) {
+        while (struct dirent *e = readdir(d)) {
+            const std::string nm = e->d_name;
+            if (nm == "." || nm == "..") continue;
+            const std::string p = dir + "/" + nm;
+            struct stat st;
+            if (lstat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) { if (depth < 1) removeOwnDir(p, depth + 1); }
+            else unlink(p.c_str());
+        }
+        closedir(d);
+    }
+    rmdir(dir.c_str());
+}
+int assembleFused(Args &a) {
+    static const char *const USAGE = "Usage: carpedeam ancient_assemble_fused <reads.fast(a|q)[.gz]> <o:fastaFile> <tmpDir> [flags]\n"
+                                     "       carpedeam ancient_assemble_fused <R1> <R2> [<R1> <R2> ...] <o:fastaFile> <tmpDir> [flags]";
+    if (a.pos.empty()) die(USAGE);
+    checkFlags("ancient_assemble_fused", a, FUSED_FLAGS);
+    // GuidedNuclassembler.cpp:85-99: the file names count the output and the directory
+    if (a.pos.size() < 3) die(std::string("Too few input files provided.\n") + USAGE);
+    if ((a.pos.size() - 2) % 2 != 0 && a.pos.size() != 3) die(std::string("Too many input files provided.\nFor paired-end input provide READSETA_1.fastq READSETA_2.fastq ... OUTPUT.fasta tmpDir\n"
+                                                                          "For single input use READSET.fast(q|a) OUTPUT.fasta tmpDir"));
+    const std::vector<std::string> inputs(a.pos.begin(), a.pos.end() - 2);
+    const std::string outFile = a.pos[a.pos.size() - 2], tmpDir = a.pos.back();
+    // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
+    if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
+    if (const char *dry = getenv("CDM_FUSED_DRY_RUN")) {        // "cycle": the tail as it runs with circular contigs among the selection
+        for (const TailStep &s : fusedTail(a, "$TMP", !strcmp(dry, "cycle"))) {
+            printf("%s", s.module.c_str());
+            for (const std::string &p : s.pos) printf(" %s", p.c_str());
+            printf(" %s\n", s.flags.c_str());
+        }
+        return EXIT_SUCCESS;
+    }
+    struct stat st;
+    if (stat(outFile.c_str(), &st) == 0) die(outFile + " exists already!");                         // guidedNuclAssemble.sh:24
+    if (stat(tmpDir.c_str(), &st) != 0 && mkdir(tmpDir.c_str(), 0777) != 0) die("Can not create tmp directory " + tmpDir);
+    std::string T = tmpDir + "/ancient_assemble_fused_XXXXXX";
+    if (!mkdtemp(&T[0])) die("Can not create a directory under " + tmpDir);
+    if (mkdir((T + "/clu_tmp").c_str(), 0777) != 0) die("Can not create " + T + "/clu_tmp");
+    Laps laps;
+    LoopEnd E;
+    runLoop("ancient_assemble_fused", a, inputs, false, 10, true, E, laps);       // the workflow's defaults: --num-iterations 10 (GuidedNuclassembler.cpp:12), --num-iter-reads-only 5
+    cdm_ctx *ctx = E.ctx;
+    // ---- "select only assembled sequences" / "... fullfilling a minimum length threshold" (nuclassemble.sh:214-224) on the final DB
+    // and on the circular contigs the iterations set aside (the script concatenates them first: the keys of the two are disjoint, and what
+    // the selection keeps is brought into key order below, as concatdbs --preserve-keys + createsubdb leave it)
+    const uint32_t minLen = (uint32_t) std::min<long>(std::max<long>(iflag(a, "--min-contig-len", 500), 0), 0xFFFFFFFEl);       // LocalParameters.h:288
+    cdm_seqdb *selected = NULL; uint64_t kept = 0;
+    check(cdm_seqdb_select_assembled(ctx, E.db, E.source, minLen, &selected, &kept), "selection of the assembled contigs");
+    cdm_seqdb_free(E.db);
+    OutChunk linear, circular, both;
+    appendEntries(ctx, selected, linear);
+    for (cdm_seqdb *c : E.cyclicDev) {
+        cdm_seqdb *s = NULL;
+        check(cdm_seqdb_select_assembled(ctx, c, E.source, minLen, &s, NULL), "selection of the assembled contigs");
+        appendEntries(ctx, s, circular);
+        cdm_seqdb_free(s); cdm_seqdb_free(c);
+    }
+    cdm_seqdb_free(E.source);
+    fprintf(stderr, "%llu assembled contigs of at least %u letters (%llu circular)\n", (unsigned long long) (linear.key.size() + circular.key.size()), minLen, (unsigned long long) circular.key.size());
+    laps.lap("assembled contigs selected");
+    const bool removeTmp = iflag(a, "--remove-tmp-files", 0) != 0;
+    if (linear.key.empty() && circular.key.empty()) {
+        // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
+        cdm_seqdb_free(selected); cdm_ctx_destroy(ctx);
+        if (!writeText(outFile, "")) die("Could not write " + outFile);
+        if (removeTmp) removeOwnDir(T);
+        return EXIT_SUCCESS;
+    }
+    std::string err;
+    const std::vector<TailStep> tail = fusedTail(a, T, !circular.key.empty());
+    const std::string IN = T + "/nuclassembly", C = T + "/clu_tmp", REP = T + "/nuclassembly_rep";
+    {
+        concatByKey(linear, circular, both);
+        std::vector<OutChunk> one(1); one[0] = std::move(both);
+        if (!mmdbWriteChunks(IN, E.dbtype, one, &err)) die(err);
+        if (!circular.key.empty()) {      // nuclassemble.sh:231: the index lines of the selected circular contigs
+            std::vector<uint32_t> ck(circular.key.begin(), circular.key.end()); std::sort(ck.begin(), ck.end());
+            std::vector<std::string> lines; std::vector<uint32_t> keys; std::string text;
+            if (!indexKeys(IN + ".index", lines, keys)) die("Could not read " + IN + ".index");
+            for (size_t i = 0; i < keys.size(); i++) if (std::binary_search(ck.begin(), ck.end(), keys[i])) text += lines[i];
+            if (!writeText(IN + "_cycle.index", text)) die("Could not write " + IN + "_cycle.index");
+        }
+    }
+    MmDb asmDb; if (!asmDb.load(IN, &err)) die(err);
+    // the DB linclust's device stages run on: the selection as it stands on the device; with circular contigs among it, the few
+    // selected contigs in their key order, uploaded
+    cdm_seqdb *db = selected;
+    if (!circular.key.empty()) { cdm_seqdb_free(selected); db = uploadSeqDb(ctx, asmDb); }
+    {
+        std::vector<uint32_t> keys(asmDb.size());
+        check(cdm_seqdb_meta(ctx, db, NULL, keys.data(), NULL), "meta");
+        if (cdm_seqdb_size(db) != asmDb.size() || !std::equal(keys.begin(), keys.end(), asmDb.key.begin())) die("ancient_assemble_fused: the selected contigs are not in key order on the device");
+    }
+    cdm_hits *hits = NULL;
+    for (const TailStep &s : tail) {
+        Args sa = stepArgs(s);
+        if (s.module == "linclust") continue;
+        if (s.module == "kmermatcher") {
+            checkFlags("kmermatcher", sa, KMERMATCHER_FLAGS);
+            const cdm_kmer_params p = kmerParams(sa);
+            check(cdm_kmermatch(ctx, db, &p, &hits), "kmermatcher");
+            HVec<uint64_t> off(asmDb.size() + 1); HVec<cdm_hit> rec(cdm_hits_count(hits));
+            check(cdm_hits_download(ctx, hits, off.data(), rec.data()), "download");
+            std::vector<OutChunk> chunks;
+            formatPrefDb(asmDb, off.data(), rec.data(), chunks);
+            if (!mmdbWriteChunks(s.pos[1], 14, chunks, &err, true)) die(err);
+        } else if (s.module == "rescorediagonal") {     // linclust's Hamming pre-clustering, on the hits as they stand on the device
+            checkFlags("rescorediagonal", sa, RESCORE_HAMMING_FLAGS);
+            MmDb pref; if (!pref.load(s.pos[2], &err)) die(err);
+            const cdm_hamming_params p = hammingParams(sa, (pref.dbtype & 0x7FFFFFFF) == 14);
+            cdm_hits *keptHits = NULL;
+            check(cdm_rescore_hamming(ctx, db, hits, &p, &keptHits), "rescorediagonal");
+            HVec<uint64_t> koff(asmDb.size() + 1); HVec<cdm_hit> krec(cdm_hits_count(keptHits));
+            check(cdm_hits_download(ctx, keptHits, koff.data(), krec.data()), "download");
+            std::vector<OutChunk> chunks;
+            formatRescoredPrefDb(asmDb, pref, koff.data(), krec.data(), chunks);
+            if (!mmdbWriteChunks(s.pos[3], pref.dbtype, chunks, &err, true)) die(err);
+            // the device's part is done: everything after this works on cluster lists and the contig DB's files
+            cdm_hits_free(keptHits); cdm_hits_free(hits); hits = NULL; cdm_seqdb_free(db); db = NULL; cdm_ctx_destroy(ctx); ctx = NULL;
+            laps.lap("linclust: kmermatcher, Hamming rescore");
+        } else if (s.module == "createhdb") {
+            if (s.pos.size() > 2) {     // guidedNuclAssemble.sh:197-199: the representatives that are circular contigs
+                std::vector<std::string> cl, rl; std::vector<uint32_t> ckeys, rkeys; std::string text;
+                if (!indexKeys(IN + "_cycle.index", cl, ckeys) || !indexKeys(REP + ".index", rl, rkeys)) die("Could not read " + REP + ".index");
+                std::sort(ckeys.begin(), ckeys.end());
+                for (size_t i = 0; i < rkeys.size(); i++) if (std::binary_search(ckeys.begin(), ckeys.end(), rkeys[i])) text += rl[i];
+                if (!writeText(REP + "_cycle.index", text)) die("Could not write " + REP + "_cycle.index");
+            }
+            createhdb(sa);
+        } else if (s.module == "convert2fasta") convert2fasta(sa);
+        else {
+            clusterModules(s.module, sa);
+            if (s.module == "clust" && s.pos[2] == C + "/pre_clust") {      // linclust.sh:39: awk '{ print $1 }' pre_clust.index > order_redundancy
+                std::vector<std::string> lines; std::vector<uint32_t> keys; std::string text;
+                if (!indexKeys(s.pos[2] + ".index", lines, keys)) die("Could not read " + s.pos[2] + ".index");
+                for (uint32_t k : keys) text += std::to_string(k) + "\n";
+                if (!writeText(C + "/order_redundancy", text)) die("Could not write " + C + "/order_redundancy");
+            }
+        }
+    }
+    laps.lap("linclust's tail, representatives, headers, FASTA");
+    if (rename((REP + ".fasta").c_str(), outFile.c_str()) != 0) {       // (another file system: copied)
+        FILE *in = fopen((REP + ".fasta").c_str(), "rb"), *out = fopen(outFile.c_str(), "wb");
+        if (!in || !out) die("Could not move result to " + outFile);
+        char buf[1 << 16]; size_t n; bool ok = true;
+        while ((n = fread(buf, 1, sizeof(buf), in)) > 0) ok = ok && fwrite(buf, 1, n, out) == n;
+        fclose(in);
+        if (fclose(out) != 0 || !ok) die("Could not move result to " + outFile);
+        unlink((REP + ".fasta").c_str());
+    }
+    if (removeTmp) removeOwnDir(T);
+    return EXIT_SUCCESS;
+}
 }  // namespace
 
 // see reportDone(): true in the process that goes on with the work
@@ -1405,8 +1695,9 @@ static bool workInChild() {
     _exit(WEXITSTATUS(st));
 }
 int main(int argc, char **argv) {
-    workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
+    if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -1423,6 +1714,7 @@ int main(int argc, char **argv) {
     else if (cmd == "ancient_read_assemble") rc = ancientModule(a, 1);
     else if (cmd == "ancient_contig_merge") rc = ancientModule(a, 2);
     else if (cmd == "ancient_reads_loop") rc = readsLoop(a);
+    else if (cmd == "ancient_assemble_fused") rc = assembleFused(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

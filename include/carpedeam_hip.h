@@ -101,6 +101,15 @@ void cdm_seqdb_free(cdm_seqdb *db);
  * Packed form: codes = 16 bases per uint32 (A,C,G,T = 0..3), every sequence starting on a word boundary, nmask = one
  * uint16 per code word (bit j = base j is 'N'), lengths and keys one uint32 per sequence. */
 int cdm_seqdb_select_ext(cdm_ctx *ctx, const cdm_seqdb *db, cdm_seqdb **out);
+/* The workflow's selection of the assembled contigs (data/nuclassemble.sh:214-233) on resident DBs: of `result` (the final DB of the
+ * loop) the entries that are longer than the entry of the same key in `source` (the DB the loop started from; a key `source` does
+ * not hold is dropped) and at least min_len letters long (--min-contig-len), in their order, with their keys, wasExtended flags, N
+ * and original letters.  The keys of `source` must ascend strictly (CDM_ERR_INVALID otherwise); only its keys and lengths are read
+ * (cdm_seqdb_index_copy).  *n_kept (may be NULL) = cdm_seqdb_size(*out); nothing kept is a valid, empty DB. */
+/* keys, lengths and wasExtended flags of db as a DB WITHOUT letters: good for cdm_seqdb_meta / cdm_seqdb_size and as the `source` of
+ * cdm_seqdb_select_assembled, for nothing that reads sequences. */
+int cdm_seqdb_index_copy(cdm_ctx *ctx, const cdm_seqdb *db, cdm_seqdb **out);
+int cdm_seqdb_select_assembled(cdm_ctx *ctx, const cdm_seqdb *result, const cdm_seqdb *source, uint32_t min_len, cdm_seqdb **out, uint64_t *n_kept);
 uint64_t cdm_seqdb_words(const cdm_seqdb *db);
 int cdm_seqdb_copy_packed(cdm_ctx *ctx, const cdm_seqdb *db, void *dev_codes, void *dev_nmask16, void *dev_lengths, void *dev_keys);
 int cdm_seqdb_from_packed(cdm_ctx *ctx, const void *dev_codes, const void *dev_nmask16, const void *dev_lengths, const void *dev_keys,
