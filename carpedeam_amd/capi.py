@@ -75,6 +75,11 @@ class AncientParams(C.Structure):
         return cls(0.9, 0.99, 0.99, 0.85, 0.0625, 0.5, 0, 5, 200000)
 
 
+class PileupParams(C.Structure):
+    """cdm_pileup_params: positions counted from either end of a read, the records' identity threshold, reads only as targets"""
+    _fields_ = [("ends", C.c_int32), ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -86,6 +91,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
+    "cdm_pileup_profile", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -199,6 +205,10 @@ def lib():
         l.cdm_dev_copy.argtypes = [vp, vp, vp, C.c_uint64]
         l.cdm_seqdb_from_packed_ext.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
         l.cdm_seqdb_copy_ext.argtypes = [vp, vp, vp]
+        l.cdm_pileup_profile.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(PileupParams), vp, vp, vp]
+        l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
+        l.cdm_pileup_chunk_records.argtypes = []
+        l.cdm_pileup_chunk_records.restype = C.c_uint32
         l.cdm_contig_merge.argtypes = [vp, vp, vp, C.POINTER(AncientParams), C.c_float, C.POINTER(vp)]
         l.cdm_cyclecheck.argtypes = [vp, vp, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(vp), vp]
         if hasattr(l, "cdm_comm_create_ops"):
@@ -231,6 +241,11 @@ def lib():
 
 
 _env_seen = None
+
+
+def pileup_chunk_records():
+    """records per work item of cdm_pileup_profile's kernel as the next call cuts them (CDM_PILEUP_CHUNK; tests)"""
+    return int(lib().cdm_pileup_chunk_records())
 
 
 def pool_stats():
@@ -606,6 +621,23 @@ class Ctx:
         h = C.c_void_p()
         _check(lib().cdm_correct(self.h, db.h, alns.h, C.byref(par), C.byref(h)))
         return SeqDb(self, h)
+
+    def concat(self, a, b, ext_a, ext_b):
+        """a's entries, then b's, as one resident DB: keys 0 .. n_a + n_b - 1, the wasExtended flags of the parts set to ext_a / ext_b"""
+        h = C.c_void_p()
+        _check(lib().cdm_seqdb_concat(self.h, a.h, b.h, int(ext_a), int(ext_b), C.byref(h)))
+        return SeqDb(self, h)
+
+    def pileup_profile(self, db, alns, queries, ends=16, min_seq_id=0.0, skip_extended_targets=False):
+        """coverage and damage tables of the listed queries (cdm_pileup_profile) -> (counts[nq, 2, ends, 4, 4] - 5' table, 3' table, each
+        [distance from that end of the read][query base as the read's strand sees it][read base] -, reads[nq], columns[nq]), uint64"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        shape = (nq, 2, max(int(ends), 0), 4, 4)
+        counts, reads, columns = np.zeros(shape, np.uint64), np.zeros(nq, np.uint64), np.zeros(nq, np.uint64)
+        par = PileupParams(int(ends), float(min_seq_id), int(bool(skip_extended_targets)))
+        _check(lib().cdm_pileup_profile(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(counts), _ptr(reads), _ptr(columns)))
+        return counts, reads, columns
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

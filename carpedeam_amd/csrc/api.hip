@@ -106,7 +106,7 @@ extern "C" void cdm_ctx_destroy(cdm_ctx *c) {
 }
 extern "C" int cdm_ctx_sync(cdm_ctx *c) { CDM_HIP(hipSetDevice(c->device)); CDM_HIP(hipStreamSynchronize(c->stream)); return CDM_OK; }
 extern "C" void *cdm_ctx_stream(cdm_ctx *c) { return (void *) c->stream; }
-extern "C" float cdm_ctx_last_kernel_ms(cdm_ctx *c, int which) { return (which >= 0 && which < 16) ? c->lastMs[which] : -1.f; }
+extern "C" float cdm_ctx_last_kernel_ms(cdm_ctx *c, int which) { return (which >= 0 && which < 17) ? c->lastMs[which] : -1.f; }
 
 extern "C" int cdm_damage_load(cdm_ctx *c, const char *prefix) {
     std::string err;
@@ -760,6 +760,56 @@ extern "C" int cdm_seqdb_from_packed_ext(cdm_ctx *ctx, const void *codes, const 
             cdm_seqdb_free(o); cdm_set_error("cdm_seqdb_from_packed_ext: copying the wasExtended flags failed"); return CDM_ERR_HIP;
         }
     }
+    *out = o;
+    return CDM_OK;
+}
+
+// ---- two resident DBs as one: a's entries, then b's.  Every sequence starts on a code word, and the N bits and the raw plane are
+// indexed by code word too (16 bits / 16 bytes per word): the three planes of the result are the parts' planes back to back, and only
+// b's word offsets move.  Keys 0 .. n - 1, the flags of the parts set by the caller.
+namespace {
+__global__ void k_concat_meta(const cdm_seqdb a, const cdm_seqdb b, uint8_t extA, uint8_t extB, cdm_seqdb o) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x, n = a.n + b.n;
+    if (i > n) return;
+    if (i == n) { o.woff[n] = (uint32_t) (a.words + b.words); return; }
+    const bool inA = i < a.n;
+    const cdm_seqdb &src = inA ? a : b;
+    const uint64_t j = inA ? i : i - a.n;
+    o.woff[i] = src.woff[j] + (inA ? 0u : (uint32_t) a.words);
+    o.len[i] = src.len[j]; o.key[i] = (uint32_t) i; o.ext[i] = inA ? extA : extB; o.hasN[i] = src.hasN[j];
+}
+}  // namespace
+extern "C" int cdm_seqdb_concat(cdm_ctx *ctx, const cdm_seqdb *a, const cdm_seqdb *b, uint8_t ext_a, uint8_t ext_b, cdm_seqdb **out) {
+    if (!ctx || !a || !b || !out) { cdm_set_error("cdm_seqdb_concat: NULL argument"); return CDM_ERR_INVALID; }
+    if ((a->residues && !a->codes) || (b->residues && !b->codes)) { cdm_set_error("cdm_seqdb_concat: a part holds no letters (an index copy)"); return CDM_ERR_INVALID; }
+    const uint64_t n = a->n + b->n, words = a->words + b->words;
+    if (n >= 0xFFFFFFFFull) { cdm_set_error("cdm_seqdb_concat: more than 2^32-1 sequences"); return CDM_ERR_UNSUPPORTED; }
+    if (words >= 0xFFFFFF00ull) { cdm_set_error("cdm_seqdb_concat: more than 2^32 code words (68 G bases) in one DB"); return CDM_ERR_UNSUPPORTED; }
+    CDM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    cdm_seqdb *o = nullptr;
+    int rc = cdm_seqdb_alloc(ctx, n, &o);
+    if (rc == CDM_OK) rc = seqdb_alloc_codes(o, words);
+    if (rc == CDM_OK && (a->raw || b->raw)) rc = cdm_seqdb_alloc_raw(o);
+    if (rc != CDM_OK) { if (o) cdm_seqdb_free(o); return rc; }
+    o->residues = a->residues + b->residues; o->maxLen = std::max(a->maxLen, b->maxLen); o->nCount = a->nCount + b->nCount;
+    hipError_t e = hipMemsetAsync(o->nmask, 0, ((words * 16 + 31) / 32 + 1) * 4, s);
+    const cdm_seqdb *part[2] = {a, b}; uint64_t at = 0;
+    for (int k = 0; k < 2 && e == hipSuccess; k++) {
+        const cdm_seqdb *p = part[k];
+        if (p->words) {
+            e = hipMemcpyAsync(o->codes + at, p->codes, p->words * 4, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(reinterpret_cast<uint16_t *>(o->nmask) + at, p->nmask, p->words * 2, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && p->raw) e = hipMemcpyAsync(o->raw + at * 16, p->raw, p->words * 16, hipMemcpyDeviceToDevice, s);
+        }
+        at += p->words;
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_concat_meta, CDM_GRID((n + 256) / 256, 256), dim3(256), 0, s, *a, *b, ext_a, ext_b, *o);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { cdm_seqdb_free(o); cdm_set_error("cdm_seqdb_concat: %s", hipGetErrorString(e)); return CDM_ERR_HIP; }
     *out = o;
     return CDM_OK;
 }

@@ -32,6 +32,8 @@
 
 static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_correction", "ancient_read_assemble", "ancient_contig_merge", "cyclecheck",
                                     "createdb", "createhdb", "convert2fasta", "ancient_reads_loop", "ancient_assemble_fused", "mergereads",
+                                    /* coverage and damage tables of contigs from the read pile-up: not a module of the reference */
+                                    "contig_damage",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

@@ -329,7 +329,9 @@ std::string baseName(const std::string &p) { const size_t s = p.find_last_of('/'
 
 // parsed reads in createdb's order as an in-memory sequence DB: keys 0..n-1, wasExtended 0.  The blob stays in input order - the
 // shuffle is a permutation of the offsets, nothing is copied a second time.
-bool readFastxAsDb(const std::vector<std::string> &files, bool shuffle, FastxDb &out, std::string *err) {
+bool readFastxAsDb(const std::vector<std::string> &files, bool shuffle, FastxDb &out, std::string *err) { return readFastxNamed(files, shuffle, out, NULL, err); }
+// the same with the entries' names (the header up to the first white space), in the order of the entries
+bool readFastxNamed(const std::vector<std::string> &files, bool shuffle, FastxDb &out, std::vector<std::string> *names, std::string *err) {
     Entries e;
     if (!parseAll(files, e, err)) return false;
     const std::vector<uint32_t> order = entryOrder(e.seqOff.size(), shuffle);
@@ -337,6 +339,14 @@ bool readFastxAsDb(const std::vector<std::string> &files, bool shuffle, FastxDb 
     out.key.resize(n); out.off.resize(n); out.len.resize(n);
 #pragma omp parallel for schedule(static)
     for (size_t j = 0; j < n; j++) { const uint32_t i = order[j]; out.key[j] = (uint32_t) j; out.off[j] = e.seqOff[i]; out.len[j] = e.seqLen[i]; }
+    if (names) {
+        names->resize(n);
+        for (size_t j = 0; j < n; j++) {
+            const char *h = e.hdrBlob.data() + e.hdrOff[order[j]];
+            size_t len = 0; while (h[len] && !isspace((unsigned char) h[len])) len++;
+            (*names)[j].assign(h, len);
+        }
+    }
     out.blob.swap(e.seqBlob);
     return true;
 }

@@ -1039,7 +1039,9 @@ const char *const LOOP_FLAGS[] = {"--k-ancient-reads", "--kmer-per-seq-ancient",
 // host (`cyclic`), or, for a caller that goes on with them on the device (keepResident), as the device DBs of the iterations that found
 // them (`cyclicDev`) together with the keys and lengths of the DB the loop started from (`source`: the createdb / mergereads result,
 // without its letters - cdm_seqdb_index_copy).
-struct LoopEnd { cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL, *source = NULL; OutChunk cyclic; std::vector<cdm_seqdb *> cyclicDev; int dbtype = 1; };
+// keepReads (ancient_assemble_fused --damage-report): the DB the loop started from stays resident WITH its letters (`reads`) instead of
+// going with the first iteration.
+struct LoopEnd { cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL, *source = NULL, *reads = NULL; bool keepReads = false; OutChunk cyclic; std::vector<cdm_seqdb *> cyclicDev; int dbtype = 1; };
 // The loop itself, shared by ancient_reads_loop and ancient_assemble_fused: input parsing or pair merging, the read and contig
 // iterations, the script's cyclecheck step and --gpus.  inputs: a sequence DB (fromDb), one reads file, or R1 R2 [R1 R2 ...];
 // defaultTotal: --num-iterations where the flag is not given (< 0: the read iterations only).
@@ -1113,6 +1115,8 @@ void runLoop(const char *module, Args &a, const std::vector<std::string> &inputs
     check(cdm_damage_load(ctx, a.flag.count("--ancient-damage") ? a.flag["--ancient-damage"].c_str() : ""), "Profile not 12 fields");
     // (the selection of the assembled contigs compares with the lengths of this DB: its keys and lengths stay, its letters go with the first iteration)
     if (keepResident) check(cdm_seqdb_index_copy(ctx, db, &E.source), "index of the source DB");
+    cdm_seqdb *const firstDb = db;
+    auto releaseInput = [&](cdm_seqdb *d) { if (d == firstDb && E.keepReads && !E.reads) E.reads = d; else cdm_seqdb_free(d); };      // an iteration's input DB once its result stands
     cdm_kmer_params kp;
     kp.kmer_size = (int) iflag(a, "--k-ancient-reads", 20); kp.kmers_per_seq = (int) iflag(a, "--kmer-per-seq-ancient", 200);
     kp.kmers_per_seq_scale = fflag(a, "--kmer-per-seq-scale-ancient", 0.2f); kp.hash_shift = (uint64_t) iflag(a, "--hash-shift", 67);
@@ -1179,7 +1183,7 @@ void runLoop(const char *module, Args &a, const std::vector<std::string> &inputs
                                     it, (unsigned long long) cdm_seqdb_size(d), (unsigned long long) cdm_seqdb_residues(d), (unsigned long long) cdm_seqdb_residues(next),
                                     (unsigned long long) cdm_alns_count(alns), std::chrono::duration<double>(std::chrono::steady_clock::now() - tIt).count(), gpus,
                                     threadsTransport ? ", in-process transport on one device" : standin ? ", the RCCL transport over its in-process stand-in, one device" : ", RCCL");
-                cdm_alns_free(alns); cdm_seqdb_free(d);
+                cdm_alns_free(alns); releaseInput(d);
                 d = next;
                 if (contigs && cycleCheck) {        // every rank holds the whole merged DB: the same check, the same rest on all of them; rank 0 keeps the circular contigs
                     cdm_seqdb *cyc = NULL, *rest = NULL;
@@ -1217,7 +1221,7 @@ void runLoop(const char *module, Args &a, const std::vector<std::string> &inputs
                 it, (unsigned long long) cdm_seqdb_size(db), (unsigned long long) cdm_seqdb_residues(db), (unsigned long long) cdm_seqdb_residues(next), (unsigned long long) cdm_alns_count(alns),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tIt).count(), cdm_ctx_last_kernel_ms(ctx, 8), cdm_ctx_last_kernel_ms(ctx, 9), cdm_ctx_last_kernel_ms(ctx, 10),
                 contigs ? "contig statistics" : "ancient_read_assemble", cdm_ctx_last_kernel_ms(ctx, contigs ? 12 : 11));
-        cdm_alns_free(alns); cdm_seqdb_free(corr); cdm_seqdb_free(db);
+        cdm_alns_free(alns); cdm_seqdb_free(corr); releaseInput(db);
         db = next;
         if (contigs && cycleCheck) {
             cdm_seqdb *cyc = NULL, *rest = NULL;
@@ -1240,6 +1244,109 @@ void concatByKey(const OutChunk &all, const OutChunk &cyclic, OutChunk &merged) 
         const OutChunk &c = *o.second.first; const size_t i = o.second.second;
         merged.add(o.first, c.data.data() + (&c == &all ? offA[i] : offC[i]), c.len[i] - 1, c.ext[i]);
     }
+}
+// ---- contig_damage: per-contig coverage and damage tables from the read pile-up (not a module of the reference).  The contigs and
+// the reads become one DB (contigs first, wasExtended 1; reads behind them, 0), kmermatcher and rescorediagonal run on it with the reads
+// loop's flags, and cdm_pileup_profile counts, per contig, the overlaps of the reads that seed on it: coverage by seeded UNGAPPED
+// overlaps at the identity threshold, not a gapped mapping; a read counts on the longest sequence of each k-mer group it falls into
+// (kmermatcher's representative rule), possibly on several contigs.  One TSV line per contig, integers only.
+bool writeText(const std::string &path, const std::string &text);
+const FlagSpec DAMAGE_FLAGS[] = {{"--damage-ends", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+long damageEnds(Args &a, const char *module) {
+    const long e = iflag(a, "--damage-ends", 16);
+    if (e < 1 || e > 64) unsupported(std::string(module) + ": --damage-ends " + a.flag["--damage-ends"] + " is not supported by the MI355X path (the tables hold 1 to 64 positions from either end of a read)");
+    return e;
+}
+// a set of sequences on the device with the names and keys its TSV lines carry
+struct DamageInput { cdm_seqdb *db = NULL; std::vector<std::string> names; std::vector<uint32_t> keys; };
+// path: a sequence DB (names from its header DB where it has one) or FASTA/FASTQ[.gz] (shuffle: createdb's order, as the loop lays its
+// reads out).  false: the input holds no sequence.
+bool loadDamageInput(cdm_ctx *ctx, const std::string &path, bool shuffle, bool wantNames, DamageInput &in) {
+    struct stat st; std::string err;
+    if (stat((path + ".index").c_str(), &st) == 0) {
+        MmDb seq; if (!seq.load(path, &err)) die(err);
+        if (seq.size() == 0) return false;
+        in.db = uploadSeqDb(ctx, seq);
+        in.keys.assign(seq.key.begin(), seq.key.end());
+        if (wantNames) {
+            MmDb hdr;
+            const bool haveHdr = stat((path + "_h.index").c_str(), &st) == 0 && hdr.load(path + "_h", &err);
+            in.names.resize(seq.size());
+            for (size_t i = 0; i < seq.size(); i++) {
+                const int64_t h = haveHdr ? hdr.idOf(seq.key[i]) : -1;
+                if (h >= 0) { const char *p = hdr.entry((size_t) h); size_t l = 0; while (l + 1 < hdr.len[(size_t) h] && p[l] && !isspace((unsigned char) p[l])) l++; in.names[i].assign(p, l); }
+                if (in.names[i].empty()) in.names[i] = std::to_string(seq.key[i]);
+            }
+        }
+        return true;
+    }
+    if (stat(path.c_str(), &st) != 0) die("Cannot open " + path);
+    if (st.st_size == 0) return false;
+    FastxDb fx;
+    if (!readFastxNamed(std::vector<std::string>(1, path), shuffle, fx, wantNames ? &in.names : NULL, &err)) die(err);
+    for (auto &l : fx.len) l -= 2;
+    check(cdm_seqdb_upload(ctx, fx.blob.data(), fx.off.data(), fx.len.data(), fx.key.data(), NULL, fx.key.size(), &in.db), "Can not load the sequences");
+    in.keys.assign(fx.key.begin(), fx.key.end());
+    for (size_t i = 0; i < in.names.size(); i++) if (in.names[i].empty()) in.names[i] = std::to_string(in.keys[i]);
+    return true;
+}
+// the four steps and the TSV; contigs == NULL: the header line alone.  Neither DB is freed here.
+void damageReport(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, long ends, int kmerSize, float minSeqId, const std::string &outPath, Laps &laps) {
+    std::string text = "name\tkey\tlength\treads\tcolumns";
+    for (long d = 1; d <= ends; d++) { const std::string n = std::to_string(d); text += "\t5p_C_" + n + "\t5p_CT_" + n + "\t3p_G_" + n + "\t3p_GA_" + n; }
+    text += "\n";
+    if (contigs && contigs->db && cdm_seqdb_size(contigs->db)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        cdm_seqdb *both = NULL; cdm_hits *hits = NULL; cdm_alns *alns = NULL;
+        check(cdm_seqdb_concat(ctx, contigs->db, reads, 1, 0, &both), "contigs and reads as one DB");
+        cdm_kmer_params kp;         // the reads loop's kmermatcher flags (stageflags.K_FLAGS)
+        kp.kmer_size = kmerSize; kp.kmers_per_seq = 200; kp.kmers_per_seq_scale = 0.2f; kp.hash_shift = 67; kp.ignore_multi_kmer = 1; kp.include_only_extendable = 0; kp.cov_mode = 1; kp.cov_thr = 0.0f;
+        cdm_rescore_params rp;      // its rescorediagonal flags (R_FLAGS)
+        rp.seq_id_thr = minSeqId; rp.eval_thr = 0.001; rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
+        check(cdm_kmermatch(ctx, both, &kp, &hits), "kmermatcher");
+        check(cdm_rescore(ctx, both, hits, &rp, &alns), "rescorediagonal");
+        cdm_hits_free(hits);
+        laps.lap("damage report: kmermatcher, rescorediagonal");
+        std::vector<uint32_t> q(nc), lens(nc);
+        std::iota(q.begin(), q.end(), 0u);
+        const size_t cells = (size_t) 2 * (size_t) ends * 16;
+        std::vector<uint64_t> counts(nc * cells), nReads(nc), nCols(nc);
+        cdm_pileup_params pp; pp.ends = (int32_t) ends; pp.min_seq_id = 0.0f; pp.skip_extended_targets = 1;
+        check(cdm_pileup_profile(ctx, both, alns, q.data(), nc, &pp, counts.data(), nReads.data(), nCols.data()), "pile-up profile");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  damage report: %llu records, pile-up kernel %.3f ms\n", (unsigned long long) cdm_alns_count(alns), cdm_ctx_last_kernel_ms(ctx, 16));
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        cdm_alns_free(alns); cdm_seqdb_free(both);
+        char num[32];
+        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        for (uint64_t i = 0; i < nc; i++) {
+            text += i < contigs->names.size() ? contigs->names[i] : std::to_string(contigs->keys[i]);
+            put(contigs->keys[i]); put(lens[i]); put(nReads[i]); put(nCols[i]);
+            const uint64_t *c5 = counts.data() + i * cells, *c3 = c5 + (size_t) ends * 16;
+            for (long d = 0; d < ends; d++) {       // [d][x][y], A,C,G,T = 0..3: C under any read base / under T; G under any / under A
+                const uint64_t *c = c5 + d * 16 + 1 * 4, *g = c3 + d * 16 + 2 * 4;
+                put(c[0] + c[1] + c[2] + c[3]); put(c[3]); put(g[0] + g[1] + g[2] + g[3]); put(g[0]);
+            }
+            text.push_back('\n');
+        }
+        laps.lap("damage report: pile-up, table");
+    }
+    if (!writeText(outPath, text)) die("Could not write " + outPath);
+}
+int contigDamage(Args &a) {
+    if (a.pos.size() < 3) die("Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]");
+    checkFlags("contig_damage", a, DAMAGE_FLAGS);
+    const long ends = damageEnds(a, "contig_damage");
+    Laps laps;
+    cdm_ctx *ctx = openCtx();
+    DamageInput contigs, reads;
+    const bool haveContigs = loadDamageInput(ctx, a.pos[0], false, true, contigs);
+    if (haveContigs && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
+    laps.lap("inputs read, sequences up");
+    damageReport(ctx, haveContigs ? &contigs : NULL, reads.db, ends, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), a.pos[2], laps);
+    if (contigs.db) cdm_seqdb_free(contigs.db);
+    if (reads.db) cdm_seqdb_free(reads.db);
+    cdm_ctx_destroy(ctx);
+    return EXIT_SUCCESS;
 }
 int readsLoop(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
@@ -1441,6 +1548,7 @@ const FlagSpec FUSED_FLAGS[] = {
     {"--include-only-extendable-ancient-reads", 'U', 0, 0}, {"-e", 'U', 0, 0}, {"--num-iter-reads-only", 'U', 0, 0}, {"--shuffle", 'U', 0, 0}, {"--num-iterations", 'U', 0, 0},
     {"--k-ancient-contigs", 'U', 0, 0}, {"--include-only-extendable-ancient-contigs", 'U', 0, 0}, {"--cycle-check", 'U', 0, 0}, {"--chop-cycle", 'U', 0, 0}, {"--gpus", 'U', 0, 0},
     // the tail's
+    {"--damage-report", 'U', 0, 0}, {"--damage-ends", 'U', 0, 0},
     {"--min-contig-len", 'U', 0, 0}, {"--clust-min-seq-id", 'U', 0, 0}, {"--clust-min-cov", 'U', 0, 0}, {"--zdrop", 'U', 0, 0}, {"--threads", 'U', 0, 0}, {"--remove-tmp-files", 'U', 0, 0},
     {"-v", 'U', 0, 0},
     {"--cluster-mode", 'V', "2", "the redundancy reduction clusters greedily, linclust's mode for --cov-mode 1"}, {"--cov-mode", 'V', "1", "the workflow's coverage mode throughout"},
@@ -1543,6 +1651,11 @@ int assembleFused(Args &a) {
                                                                           "For single input use READSET.fast(q|a) OUTPUT.fasta tmpDir"));
     const std::vector<std::string> inputs(a.pos.begin(), a.pos.end() - 2);
     const std::string outFile = a.pos[a.pos.size() - 2], tmpDir = a.pos.back();
+    // --damage-report <file>: after the FASTA, the per-contig coverage and damage tables of the final representatives against the reads the
+    // loop started from (contig_damage's four steps on the resident reads); without the flag nothing is kept resident and no call is made
+    const bool report = a.flag.count("--damage-report") != 0;
+    const std::string reportFile = report ? a.flag["--damage-report"] : "";
+    const long reportEnds = damageEnds(a, "ancient_assemble_fused");
     // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
     if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
     if (const char *dry = getenv("CDM_FUSED_DRY_RUN")) {        // "cycle": the tail as it runs with circular contigs among the selection
@@ -1561,6 +1674,7 @@ int assembleFused(Args &a) {
     if (mkdir((T + "/clu_tmp").c_str(), 0777) != 0) die("Can not create " + T + "/clu_tmp");
     Laps laps;
     LoopEnd E;
+    E.keepReads = report;
     runLoop("ancient_assemble_fused", a, inputs, false, 10, true, E, laps);       // the workflow's defaults: --num-iterations 10 (GuidedNuclassembler.cpp:12), --num-iter-reads-only 5
     cdm_ctx *ctx = E.ctx;
     // ---- "select only assembled sequences" / "... fullfilling a minimum length threshold" (nuclassemble.sh:214-224) on the final DB
@@ -1569,7 +1683,9 @@ int assembleFused(Args &a) {
     const uint32_t minLen = (uint32_t) std::min<long>(std::max<long>(iflag(a, "--min-contig-len", 500), 0), 0xFFFFFFFEl);       // LocalParameters.h:288
     cdm_seqdb *selected = NULL; uint64_t kept = 0;
     check(cdm_seqdb_select_assembled(ctx, E.db, E.source, minLen, &selected, &kept), "selection of the assembled contigs");
-    cdm_seqdb_free(E.db);
+    if (report && !E.reads) E.reads = E.db;        // (a loop of no iteration: its DB is the reads)
+    else cdm_seqdb_free(E.db);
+    cdm_ctx *const reportCtx = report ? ctx : NULL;
     OutChunk linear, circular, both;
     appendEntries(ctx, selected, linear);
     for (cdm_seqdb *c : E.cyclicDev) {
@@ -1584,8 +1700,10 @@ int assembleFused(Args &a) {
     const bool removeTmp = iflag(a, "--remove-tmp-files", 0) != 0;
     if (linear.key.empty() && circular.key.empty()) {
         // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
-        cdm_seqdb_free(selected); cdm_ctx_destroy(ctx);
+        cdm_seqdb_free(selected);
         if (!writeText(outFile, "")) die("Could not write " + outFile);
+        if (report) { damageReport(ctx, NULL, NULL, reportEnds, 20, 0.9f, reportFile, laps); cdm_seqdb_free(E.reads); }
+        cdm_ctx_destroy(ctx);
         if (removeTmp) removeOwnDir(T);
         return EXIT_SUCCESS;
     }
@@ -1639,7 +1757,8 @@ int assembleFused(Args &a) {
             formatRescoredPrefDb(asmDb, pref, koff.data(), krec.data(), chunks);
             if (!mmdbWriteChunks(s.pos[3], pref.dbtype, chunks, &err, true)) die(err);
             // the device's part is done: everything after this works on cluster lists and the contig DB's files
-            cdm_hits_free(keptHits); cdm_hits_free(hits); hits = NULL; cdm_seqdb_free(db); db = NULL; cdm_ctx_destroy(ctx); ctx = NULL;
+            cdm_hits_free(keptHits); cdm_hits_free(hits); hits = NULL; cdm_seqdb_free(db); db = NULL; if (!report) cdm_ctx_destroy(ctx);      // (the report's reads stay, with the context)
+            ctx = NULL;
             laps.lap("linclust: kmermatcher, Hamming rescore");
         } else if (s.module == "createhdb") {
             if (s.pos.size() > 2) {     // guidedNuclAssemble.sh:197-199: the representatives that are circular contigs
@@ -1671,6 +1790,13 @@ int assembleFused(Args &a) {
         if (fclose(out) != 0 || !ok) die("Could not move result to " + outFile);
         unlink((REP + ".fasta").c_str());
     }
+    if (report) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
+        DamageInput contigs;
+        const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
+        damageReport(reportCtx, have ? &contigs : NULL, E.reads, reportEnds, 20, 0.9f, reportFile, laps);
+        if (contigs.db) cdm_seqdb_free(contigs.db);
+        cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);
+    }
     if (removeTmp) removeOwnDir(T);
     return EXIT_SUCCESS;
 }
@@ -1697,7 +1823,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -1715,6 +1841,7 @@ int main(int argc, char **argv) {
     else if (cmd == "ancient_contig_merge") rc = ancientModule(a, 2);
     else if (cmd == "ancient_reads_loop") rc = readsLoop(a);
     else if (cmd == "ancient_assemble_fused") rc = assembleFused(a);
+    else if (cmd == "contig_damage") rc = contigDamage(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

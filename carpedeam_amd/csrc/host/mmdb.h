@@ -89,6 +89,8 @@ bool mmdbWritePiece(int fd, const char *data, uint64_t offset, uint64_t bytes);
 // host/ingest.cpp: FASTA/FASTQ[.gz] reads as an in-memory sequence DB (what createdb would write, without the files)
 struct FastxDb { HVec<char> blob; HVec<uint32_t> key, len; HVec<uint64_t> off; };     // entry j: blob[off[j] .. off[j] + len[j]) = "SEQ\n\0"
 bool readFastxAsDb(const std::vector<std::string> &files, bool shuffle, FastxDb &out, std::string *err);
+// the same, and names[j] = the header of entry j up to its first white space (names may be NULL)
+bool readFastxNamed(const std::vector<std::string> &files, bool shuffle, FastxDb &out, std::vector<std::string> *names, std::string *err);
 // host/ingest.cpp: the two FASTQ[.gz] files of a read pair (mergereads).  Record i: seq[off[i] .. off[i] + len[i]), its quality string at
 // the same offsets in qual when hasQual[i] (a FASTA record has none), header hdr[hoff[i] .. + hlen[i]) = "name[ comment]\n\0"
 struct FastqReads { HVec<char> seq, qual, hdr; HVec<uint64_t> off, hoff; HVec<uint32_t> len, hlen; HVec<uint8_t> hasQual; };

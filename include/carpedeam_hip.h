@@ -56,7 +56,7 @@ void *cdm_ctx_stream(cdm_ctx *ctx);
  * 8..11: the WHOLE stage call (everything it launched, host round trips between kernels included) of kmermatcher, rescorediagonal,
  * ancient_correction, ancient_read_assemble; 13: the radix PASS launches of sort 1 on the k-mer slots alone, summed, 14: how many
  * launches that sum covers, 15: the bytes those launches move at the least, in GB - every pair or tuple they sort read once and
- * written once per launch (bench.py's roofline figure).
+ * written once per launch (bench.py's roofline figure); 16: cdm_pileup_profile's counting kernel.
  * Returns a negative value when that stage has not run. */
 float cdm_ctx_last_kernel_ms(cdm_ctx *ctx, int which);
 
@@ -131,6 +131,11 @@ int cdm_seqdb_copy_ext(cdm_ctx *ctx, const cdm_seqdb *db, void *dev_ext);
  * the text DB again (lib/mmseqs/src/commons/DBReader.cpp:108-133, DBWriter.cpp:322-427 stay the format every reference module reads).
  * nmask16 / raw / raw_flags may be NULL: export - not wanted; import - no letter beyond ACGT / no raw plane.  raw_flags of an export:
  * one byte per sequence, bit 0 = the sequence has a letter beyond ACGT, bit 1 = its row of the raw plane counts. */
+/* a's entries, then b's, as one DB on the device: keys 0 .. n_a + n_b - 1, the wasExtended flags of the two parts set to ext_a and
+ * ext_b, N and original letters carried along (a raw plane in either part gives the result one).  What a caller runs kmermatcher /
+ * rescorediagonal on to lay one set of sequences over another (contigs and the reads they were built from: cdm_pileup_profile).
+ * Both parts must hold their letters (not a cdm_seqdb_index_copy); fewer than 2^32 - 1 sequences and 2^32 code words in all. */
+int cdm_seqdb_concat(cdm_ctx *ctx, const cdm_seqdb *a, const cdm_seqdb *b, uint8_t ext_a, uint8_t ext_b, cdm_seqdb **out);
 int cdm_seqdb_export_packed(cdm_ctx *ctx, const cdm_seqdb *db, void *codes, void *nmask16, void *lengths, void *keys, void *ext, void *raw, void *raw_flags);
 int cdm_seqdb_import_packed(cdm_ctx *ctx, const void *codes, const void *nmask16, const void *lengths, const void *keys, const void *ext, const void *raw,
                             const void *raw_flags, uint64_t n, uint64_t words, cdm_seqdb **out);
@@ -350,6 +355,26 @@ typedef struct cdm_ancient_params {
 } cdm_ancient_params;
 
 int cdm_correct(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const cdm_ancient_params *par, cdm_seqdb **out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Coverage and damage tables of the read pile-up (not a module of the reference; csrc/pileup.hip).  For every listed query the
+ * records of its row that ancient_correction would orient and pile up (correction.cpp:229-242) are COUNTED instead: a record r of
+ * query q counts when r.target != q, r.seq_id >= min_seq_id (float comparison; 0 takes all) and - with skip_extended_targets - the
+ * target's wasExtended flag is 0.  For each of its columns c = 0 .. qe - qs: op = ds + c is the column on the oriented target,
+ * p = rev ? tLen - 1 - op : op the position in the read's own orientation, y the read's own code at p, x the query's code at qs + c,
+ * complemented when rev (the query base as the read's strand sees it).  A column with an N on either side counts in `columns` only;
+ * any other adds one to c5[p][x][y] when p < ends and one to c3[tLen - 1 - p][x][y] when tLen - 1 - p < ends (a short read lands in
+ * both).  Letters are the mapped codes and N bits (the NucleotideMatrix view), never the raw plane.
+ *   counts   n_queries x 2 x ends x 16 uint64: per query the 5' table, then the 3' table, each [d][x][y] with A,C,G,T = 0..3
+ *   reads    n_queries uint64: records counted;  columns: n_queries uint64: sum of qe - qs + 1 over them
+ * ends in 1..64; a query index >= the DB's size or listed twice is CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched);
+ * a set with the coordinates -1 record is refused as cdm_correct refuses it.  The 5' C->T rate at distance d is
+ * c5[d][C][T] / sum_y c5[d][C][y], the 3' G->A rate c3[d][G][A] / sum_y c3[d][G][y]; the library hands out the integers.
+ * Coverage here is coverage by seeded ungapped overlaps at the set's identity threshold, not by a gapped mapping.
+ * Device time of the counting kernel: cdm_ctx_last_kernel_ms(ctx, 16). */
+typedef struct cdm_pileup_params { int32_t ends; float min_seq_id; int32_t skip_extended_targets; } cdm_pileup_params;
+int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                       const cdm_pileup_params *par, uint64_t *counts, uint64_t *reads, uint64_t *columns);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
