@@ -11,7 +11,7 @@
 
 void cdm_set_error(const char *fmt, ...);
 
-// Caching device allocator (api.hip): hipMalloc/hipFree of multi-GB buffers cost tens of ms each, and every stage call
+// Caching device allocator (pool.h, behind the shims of api.hip): hipMalloc/hipFree of multi-GB buffers cost tens of ms each, and every stage call
 // allocates its working set; freed blocks are kept per device and reused for later requests of (nearly) the same size.
 // All stage entry points synchronise their stream before they return, so a block is idle when it is handed back.
 hipError_t cdmMallocRaw(void **p, size_t bytes);
@@ -54,7 +54,6 @@ template <typename T> struct DevBuf {
 // item are launched in slices (cdmSliceItems: items per launch; the kernel adds its `first` item); kernels with a thread per item sit
 // behind size checks that keep the item count below 2^32 - CDM_GRID is the assertion that they do.
 constexpr uint64_t CDM_MAX_LAUNCH_THREADS = (1ull << 32) - 1ull;
-const char *cdmGetenv(const char *name);
 inline uint64_t cdmSliceItems(unsigned threadsPerItem) {        // CDM_LAUNCH_SLICE=<items> (tests): small inputs in several launches
     if (const char *e = cdmGetenv("CDM_LAUNCH_SLICE")) { const long long v = atoll(e); if (v > 0) return (uint64_t) v; }
     return (1ull << 31) / threadsPerItem;
@@ -103,7 +102,7 @@ struct cdm_ctx {
     int cuCount = 256;
 };
 
-// Sequence DB in HBM.  Base codes A,C,G,T = 0..3 (CarpeDeam's own order, src/assembler/correction.cpp:170-174),
+// Sequence DB in HBM (the container's code: seqdb.hip, seqdb.h).  Base codes A,C,G,T = 0..3 (CarpeDeam's own order, src/assembler/correction.cpp:170-174),
 // 16 bases per 32-bit word, little end first; every sequence starts on a word boundary.  'N' (any X-class letter)
 // is stored as code 0 plus a bit in nmask (bit index = 16 * woff[i] + pos).
 // Letters beyond upper-case ACGTN (lower case, IUPAC codes, anything else a DB may carry): codes/nmask hold what
@@ -117,21 +116,22 @@ struct cdm_seqdb {
     uint64_t words = 0;     // total code words
     uint64_t residues = 0;  // sum of lengths
     uint32_t maxLen = 0;
-    uint64_t nCount = 0;    // number of N letters in the whole DB
+    uint64_t nCount = 0;    // N letters in the whole DB - a LOWER BOUND: 0 does not prove the DB has no N; cdm_build_meta re-checks the flags.
+                            // Set by upload, from-device-text, overlay, concat, alloc-like and synth; select and from-packed leave it 0.
     uint32_t *woff = nullptr;   // [n+1] word offset of each sequence
     uint32_t *len = nullptr;    // [n]
     uint32_t *key = nullptr;    // [n]
     uint8_t *ext = nullptr;     // [n] wasExtended flag
     uint8_t *hasN = nullptr;    // [n] bit 0: sequence contains an N or any other letter beyond ACGT; bit 1: it has a row in raw
     uint32_t *codes = nullptr;  // [words]
-    uint32_t *nmask = nullptr;  // [(words*16+31)/32]
+    uint32_t *nmask = nullptr;  // 16 N bits per code word (seqdbMaskBytes, seqdb.h)
     uint8_t *raw = nullptr;     // [words*16] original bytes of the sequences with hasN bit 1, or NULL (no such sequence in the DB)
     int device = 0;
-    uint64_t serial = 0;    // unique per handle (cdm_seqdb_alloc)
+    uint64_t serial = 0;    // unique per handle (cdm_seqdb_alloc, seqdb.h)
 };
 
 // Per-sequence metadata gathered by target id in rescore / correction / extension: one 16-byte record instead of four arrays
-// (a random target then costs one cache line, not four).  Built per call from the cdm_seqdb arrays (cdm_build_meta, api.hip);
+// (a random target then costs one cache line, not four).  Built per call from the cdm_seqdb arrays (cdm_build_meta, seqdb.hip);
 // the proxies keep the kernels' `a.len[t]` spelling.
 struct SeqMeta { uint32_t woff, len, flags, key; };      // flags: 1 = has N (not plain ACGT), 2 = wasExtended, 4 = has a raw row
 // A PLAIN UNIFORM DB - every sequence of the same length, stored back to back, no flag set on any (no N, no other letter, never
@@ -161,7 +161,6 @@ struct KmerRanks {
     int (*gatherDev)(void *user, const void *send, uint64_t sendBytes, void *recv, const uint64_t *recvOff, void *stream);  // device buffers, byte offsets [world + 1]
 };
 int cdm_kmermatch_ranks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_kmer_params *par, const KmerRanks *ranks, cdm_hits **out);
-int cdm_seqdb_overlay(cdm_ctx *ctx, const cdm_seqdb *base, const cdm_seqdb *grown, const uint32_t *idxHost, const uint8_t *extHost, cdm_seqdb **out);      // api.hip
 int cdm_build_meta(cdm_ctx *ctx, const cdm_seqdb *db, SeqMeta **out, MetaUniform *uniform = nullptr);      // cdmFree the result; uniform: filled (and the stream synchronised) if asked for
 
 // (the consumers of an alignment set call this first)
@@ -186,14 +185,6 @@ struct cdm_alns {
     // mismatches per record (0xFFFF = not known, e.g. a sequence with N); only valid for the sequence DB it was computed on
     uint16_t *ryMism = nullptr; uint64_t rySerial = 0;
 };
-
-int cdm_seqdb_alloc_like(cdm_ctx *ctx, const cdm_seqdb *src, cdm_seqdb **out);  // same n/lengths/layout, codes uninitialised
-int cdm_seqdb_alloc(cdm_ctx *ctx, uint64_t n, cdm_seqdb **out);
-// entry j = text[off[j] .. off[j] + len[j]) (device pointers), key first_key + j, wasExtended ext: packed as cdm_seqdb_upload packs (api.hip)
-int cdm_seqdb_from_device_text(cdm_ctx *ctx, const char *text, const uint64_t *off, const uint32_t *len, uint64_t n, uint32_t firstKey, uint8_t ext, cdm_seqdb **out);
-int cdm_seqdb_alloc_raw(cdm_seqdb *db);      // the raw plane for db->words code words (contents undefined)
-// sub-DB: sel[i] (device) = 0xFFFFFFFF drops sequence i, else keeps its first sel[i] letters; extValue < 0 keeps the wasExtended flags
-int cdm_seqdb_select(cdm_ctx *ctx, const cdm_seqdb *db, const uint32_t *sel, int extValue, cdm_seqdb **out);
 
 // Host memory for what comes down from the device in bulk: anonymous pages, not initialised (a std::vector or std::string of that
 // size is written once by its constructor before the copy writes it again), huge pages where the system hands them out on advice.

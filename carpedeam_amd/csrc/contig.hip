@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "seqdb.h"
 #include "devutil.h"
 #include "contigqueue.h"
 

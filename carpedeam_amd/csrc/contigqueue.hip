@@ -32,7 +32,7 @@
 //   k_cq_parked  a wave per parked hit: the two counts of updateNuclAlignment / getRYSeqId over the diagonal's overlap (XOR of 2-bit
 //                windows), the new coordinates, the filter.
 // Queries leave the active list as their queue runs dry; the rounds end when it is empty.  The grown contigs are gathered into a DB
-// on the device and overlaid on the input (api.hip cdm_seqdb_overlay): nothing but a list of query indices and the flags comes down.
+// on the device and overlaid on the input (seqdb.hip cdm_seqdb_overlay): nothing but a list of query indices and the flags comes down.
 #include <algorithm>
 #include <chrono>
 #include <cstring>

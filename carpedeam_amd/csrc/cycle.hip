@@ -12,7 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "seqdb.h"
 #include "devutil.h"
 #include "scan.h"
 #include "radix.h"

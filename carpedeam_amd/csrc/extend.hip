@@ -22,7 +22,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "common.h"
+#include "seqdb.h"
 #include "devutil.h"
 
 namespace {
@@ -1005,9 +1005,8 @@ int cdm_extend_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
     if (hstats[0] / 16 + n >= 0xFFFFFFF0ull) {     // (the word offsets are 32-bit: an extended DB beyond 2^32 code words would wrap)
         cdm_seqdb_free(o); cdm_set_error("cdm_extend: the extended sequences need more than 2^32 code words (68 G bases) in one DB"); return CDM_ERR_UNSUPPORTED;
     }
-    o->words = words; o->residues = hstats[0]; o->maxLen = (uint32_t) hstats[1];
-    const uint64_t maskWords = ((uint64_t) words * 16 + 31) / 32 + 1;
-    if (cdmMalloc(&o->codes, ((size_t) words + 2) * 4) != hipSuccess || cdmMalloc(&o->nmask, maskWords * 4) != hipSuccess) { cdm_seqdb_free(o); cdm_set_error("cdm_extend: out of device memory"); return CDM_ERR_HIP; }
+    o->residues = hstats[0]; o->maxLen = (uint32_t) hstats[1];
+    if (seqdbAllocPlanes(o, words, false) != CDM_OK) { cdm_seqdb_free(o); cdm_set_error("cdm_extend: out of device memory"); return CDM_ERR_HIP; }
     hipMemcpyAsync(o->key, db->key, (size_t) n * 4, hipMemcpyDeviceToDevice, s);
     hipMemsetAsync(o->hasN, 0, n, s);
     if (words) hipLaunchKernelGGL(k_write, dim3((n + 255) / 256), dim3(256), 0, s, A, o->woff, o->len, n, o->codes, o->nmask, o->hasN);

@@ -1378,7 +1378,7 @@ const FlagSpec CREATEDB_FLAGS[] = {   // Parameters.cpp:733-737 createdb
     {"-v", 'N', 0, 0}, {"--threads", 'N', 0, 0}, {0, 0, 0, 0}};
 const FlagSpec PLAIN_FLAGS[] = {{"-v", 'N', 0, 0}, {"--threads", 'N', 0, 0}, {"--compressed", 'V', "0", "compressed DBs are not implemented"}, {"--use-fasta-header", 'V', "0", "not implemented"}, {0, 0, 0, 0}};
 // The side-car of a sequence DB straight from its text, on the host (createdb has no device): the letters packed as cdm_seqdb_upload
-// packs them (api.hip k_pack: A, C, G, T = 0..3, 16 per word, every sequence on a word boundary; 'N' = code 0 + a bit of the N mask).
+// packs them (seqdb.hip k_pack: A, C, G, T = 0..3, 16 per word, every sequence on a word boundary; 'N' = code 0 + a bit of the N mask).
 // Only for DBs of upper-case ACGTN - any other letter takes the device's mapping and its raw plane (the first module that uploads the
 // DB then writes the side-car).
 void seqSideFromText(const std::string &path) {

@@ -23,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "seqdb.h"
 #include "devutil.h"
 #include "scan.h"
 

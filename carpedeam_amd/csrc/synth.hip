@@ -1,8 +1,6 @@
 // Device-side synthetic read generator: the counter-based generator specified in carpedeam_amd/synth.py.
 // The genome is never stored: base i is a hash of (seed, i).  One thread per 16-base output word.
-#include "scan.h"
-
-#include "common.h"
+#include "seqdb.h"
 #include "devutil.h"
 
 namespace {
@@ -23,20 +21,18 @@ struct SynthArgs {
     uint64_t b0, b1, b2, b3, b4, b5;   // stream bases
     uint64_t G, first; uint32_t n, lo, hi;
 };
-__global__ void k_synth_len(SynthArgs a, uint32_t *__restrict__ len, uint32_t *__restrict__ words, uint32_t *__restrict__ key) {
+__global__ void k_synth_len(SynthArgs a, uint32_t *__restrict__ len, uint32_t *__restrict__ key) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const uint64_t r = a.first + i;
     const uint32_t L = (a.lo == a.hi) ? a.lo : a.lo + (uint32_t) (mix(a.b5 + r) % (uint64_t) (a.hi - a.lo + 1));
-    len[i] = L; words[i] = (L + 15) / 16; key[i] = i;
+    len[i] = L; key[i] = i;
 }
 __global__ __launch_bounds__(256) void k_synth(SynthArgs a, const uint32_t *__restrict__ woff, const uint32_t *__restrict__ len, uint64_t words,
                                                uint32_t *__restrict__ codes) {
     const uint64_t gw = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (gw >= words) return;
-    uint64_t lo = 0, hi = a.n;
-    while (hi - lo > 1) { uint64_t mid = (lo + hi) >> 1; if (woff[mid] <= gw) lo = mid; else hi = mid; }
-    const uint32_t i = (uint32_t) lo, w = (uint32_t) (gw - woff[i]), L = len[i];
+    const uint32_t i = (uint32_t) seqOfWord(woff, a.n, gw), w = (uint32_t) (gw - woff[i]), L = len[i];
     const uint64_t r = a.first + i;
     const uint64_t start = mix(a.b1 + r) % (a.G - L + 1);
     const bool rev = (mix(a.b2 + r) & 1ull) != 0;
@@ -68,36 +64,20 @@ int cdm_synth_impl(cdm_ctx *ctx, uint64_t nTotal, uint64_t first, uint64_t n, ui
     cdm_seqdb *db = nullptr;
     int rc = cdm_seqdb_alloc(ctx, n, &db);
     if (rc) return rc;
-    uint32_t *wordsPer = nullptr;
-    cdmscan::ScanTemp scanTmp;
-    int ret = CDM_OK;
-    do {
-        if (cdmMalloc(&wordsPer, (n + 1) * 4) != hipSuccess) { cdm_set_error("cdm_seqdb_synth: out of device memory"); ret = CDM_ERR_HIP; break; }
-        hipLaunchKernelGGL(k_synth_len, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, a, db->len, wordsPer, db->key);
-        hipMemsetAsync(wordsPer + n, 0, 4, s);
-        if ((ret = cdmscan::exclusiveScan<uint32_t>(s, scanTmp, wordsPer, db->woff, (size_t) n + 1)) != CDM_OK) break;
-        uint32_t words = 0;
-        hipMemcpyAsync(&words, db->woff + n, 4, hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) { cdm_set_error("cdm_seqdb_synth: length kernel failed"); ret = CDM_ERR_HIP; break; }
-        db->words = words;
-        const uint64_t maskWords = ((uint64_t) words * 16 + 31) / 32 + 1;
-        if (cdmMalloc(&db->codes, ((size_t) words + 2) * 4) != hipSuccess || cdmMalloc(&db->nmask, maskWords * 4) != hipSuccess) { cdm_set_error("cdm_seqdb_synth: out of device memory"); ret = CDM_ERR_HIP; break; }
-        hipMemsetAsync(db->nmask, 0, maskWords * 4, s);
+    hipLaunchKernelGGL(k_synth_len, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, a, db->len, db->key);
+    uint64_t words = 0;
+    int ret = seqdbLayout(ctx, db->len, n, db->woff, &words, false, "cdm_seqdb_synth");
+    if (ret == CDM_OK && (ret = seqdbAllocPlanes(db, words, false)) != CDM_OK) cdm_set_error("cdm_seqdb_synth: out of device memory");
+    if (ret == CDM_OK) {
+        hipMemsetAsync(db->nmask, 0, seqdbMaskBytes(words), s);
         hipMemsetAsync(db->ext, 0, n, s);
         hipMemsetAsync(db->hasN, 0, n, s);
-        hipLaunchKernelGGL(k_synth, CDM_GRID(((uint64_t) words + 255) / 256, 256), dim3(256), 0, s, a, db->woff, db->len, (uint64_t) words, db->codes);
+        hipLaunchKernelGGL(k_synth, CDM_GRID((words + 255) / 256, 256), dim3(256), 0, s, a, db->woff, db->len, words, db->codes);
         hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { cdm_set_error("cdm_seqdb_synth: generator failed: %s", hipGetErrorString(e)); ret = CDM_ERR_HIP; break; }
-        db->maxLen = hi; db->nCount = 0;
-        db->residues = (lo == hi) ? n * (uint64_t) lo : 0;
-        if (lo != hi) {   // sum of lengths
-            std::vector<uint32_t> l(n);
-            hipMemcpy(l.data(), db->len, n * 4, hipMemcpyDeviceToHost);
-            uint64_t t = 0; uint32_t mx = 0; for (uint32_t v : l) { t += v; mx = std::max(mx, v); }
-            db->residues = t; db->maxLen = mx;
-        }
-    } while (0);
-    cdmFree(wordsPer);
+        if (e != hipSuccess) { cdm_set_error("cdm_seqdb_synth: generator failed: %s", hipGetErrorString(e)); ret = CDM_ERR_HIP; }
+    }
+    db->maxLen = hi; db->nCount = 0; db->residues = n * (uint64_t) lo;
+    if (ret == CDM_OK && lo != hi) ret = seqdbLenStats(ctx, db);      // sum and maximum of the drawn lengths
     if (ret != CDM_OK) { cdm_seqdb_free(db); return ret; }
     *out = db;
     return CDM_OK;

@@ -1,9 +1,10 @@
 // Test-only harness over the device primitives of carpedeam_amd/csrc (radix.h, scan.h, bucket.h, devutil.h): one extern "C" entry
-// point per primitive and type combination the product instantiates.  Every entry point takes HOST pointers, allocates with the
+// point per primitive and type combination the product instantiates, and two for the sequence DB constructors that have no C-ABI
+// entry (prim_seqdb_select, prim_seqdb_overlay: opaque handles of the library in and out).  Every entry point takes HOST pointers, allocates with the
 // library's allocator, copies in, runs the primitive on the stream handed in, synchronises, copies out and returns the primitive's
 // own status.  Built by tests/primkit.py into tests/_build/libcdm_primitives.so and linked against libcarpedeam_hip.so (cdmMallocRaw,
-// cdmFree, cdm_set_error, cdmGetenv); never loaded by the package or by bench.py.
-#include "common.h"
+// cdmFree, cdm_set_error, cdmGetenv, cdm_seqdb_select, cdm_seqdb_overlay); never loaded by the package or by bench.py.
+#include "seqdb.h"
 #include "devutil.h"
 #include "scan.h"
 #include "radix.h"
@@ -280,4 +281,17 @@ extern "C" int prim_windows16(void *stream, const u32 *codes, u32 L, int mode, u
     CDM_HIP(hipGetLastError());
     CDM_HIP(hipStreamSynchronize(s));
     return down(out, o.p, L);
+}
+
+// ---------------------------------------------------------------------------------------------- sequence DB constructors without an ABI entry
+// sel: one value per sequence of db (host)
+extern "C" int prim_seqdb_select(cdm_ctx *ctx, const cdm_seqdb *db, const u32 *sel, int extValue, cdm_seqdb **out) {
+    CDM_HIP(hipSetDevice(ctx->device));
+    DevBuf<u32> d;
+    TRY(up(d, sel, (size_t) db->n));
+    return cdm_seqdb_select(ctx, db, d.p, extValue, out);
+}
+// grown (and idx) may be NULL: nothing replaced; idx: one entry of base per sequence of grown, ext: one flag per sequence of base (host)
+extern "C" int prim_seqdb_overlay(cdm_ctx *ctx, const cdm_seqdb *base, const cdm_seqdb *grown, const u32 *idx, const u8 *ext, cdm_seqdb **out) {
+    return cdm_seqdb_overlay(ctx, base, grown, idx, ext, out);
 }

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "primitives.hip")
 OUT_DIR = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libcdm_primitives.so")
-NEEDS = ("cdmMallocRaw", "cdmFree", "cdm_set_error", "cdmGetenv")      # what the harness takes from libcarpedeam_hip.so
+NEEDS = ("cdmMallocRaw", "cdmFree", "cdm_set_error", "cdmGetenv", "cdm_seqdb_select", "cdm_seqdb_overlay")      # what the harness takes from libcarpedeam_hip.so
 
 CDM_OK, CDM_ERR_INVALID = 0, -3        # include/carpedeam_hip.h
 
@@ -64,6 +64,7 @@ SIGNATURES = {
     "prim_wave_append": _BLOCK, "prim_block_append": _BLOCK,
     "prim_bitop16": [_vp, _vp, _u64, _i, _vp],
     "prim_windows16": [_vp, _vp, _u32, _i, _vp],
+    "prim_seqdb_select": [_vp, _vp, _vp, _i, C.POINTER(_vp)], "prim_seqdb_overlay": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
 }
 DTYPES = {"u64": np.uint64, "u32": np.uint32, "u8": np.uint8}
 _libs = {}
@@ -204,6 +205,27 @@ class Prims:
         out = np.empty(L, np.uint32)
         self._call("prim_windows16", _p(codes), L, {"plain": 0, "forward": 1, "reverse": 2}[mode], _p(out))
         return out
+
+    def _seqdb(self, name, *args):
+        """the two sequence DB constructors: the context itself, not its stream, goes in; -> capi.SeqDb"""
+        self.capi.lib()
+        h = C.c_void_p()
+        rc = getattr(self.l, name)(self.ctx.h, *args, C.byref(h))
+        if rc != 0:
+            raise PrimError(rc, self.capi.lib().cdm_last_error().decode())
+        return self.capi.SeqDb(self.ctx, h)
+
+    def seqdb_select(self, db, sel, ext_value):
+        """cdm_seqdb_select: sel[i] = 0xFFFFFFFF drops sequence i, else its first sel[i] letters stay"""
+        sel = _arr(sel, np.uint32)
+        assert sel.size == db.n
+        return self._seqdb("prim_seqdb_select", db.h, _p(sel), int(ext_value))
+
+    def seqdb_overlay(self, base, grown, idx, ext):
+        """cdm_seqdb_overlay: base with sequence idx[j] replaced by grown's sequence j (grown None: none), wasExtended flags ext"""
+        idx, ext = _arr(idx, np.uint32), _arr(ext, np.uint8)
+        assert ext.size == base.n and idx.size == (grown.n if grown is not None else 0)
+        return self._seqdb("prim_seqdb_overlay", base.h, grown.h if grown is not None else None, _p(idx) if grown is not None else None, _p(ext))
 
 
 # ====================================================================================================== reference models
