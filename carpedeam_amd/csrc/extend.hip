@@ -156,22 +156,41 @@ __device__ void consensusAt(const ExtArgs &A, const VQuery &Q, const ConsList &L
     if (isN) code = 0;
 }
 
-// identical / same-RY-class columns of q[q0..q0+n) vs t[t0..t0+n), 16 bases per XOR (neither sequence has an N)
-__device__ __forceinline__ void countMatchesWords(const ExtArgs &A, uint32_t q, uint32_t q0, uint32_t t, uint32_t t0, uint32_t n, int &idCnt, int &idRy) {
-    const uint32_t qw = A.woff[q], tw = A.woff[t];
-    const uint32_t qLast = (A.len[q] + 15) / 16 - 1, tLast = (A.len[t] + 15) / 16 - 1;
-    uint32_t mm = 0, ry = 0;
-    for (uint32_t k = 0; k < n; k += 16) {
-        const uint32_t x = cdm_window16(A.codes, qw, q0 + k, qLast) ^ cdm_window16(A.codes, tw, t0 + k, tLast);
-        uint32_t any = (x | (x >> 1)) & 0x55555555u, lowbit = x & 0x55555555u;
-        const uint32_t rem = n - k;
-        if (rem < 16) { const uint32_t m = (1u << (2 * rem)) - 1u; any &= m; lowbit &= m; }
-        mm += __popc(any); ry += __popc(lowbit);
-    }
-    idCnt = (int) (n - mm); idRy = (int) (n - ry);
+// ---------------------------------------------------------------------------------- the rules both kernel forms share, each stated once
+
+// the end-overlap tests of the reference, on the coordinates as they stand (:204-213, nuclassembleUtil.cpp:383-384)
+__device__ __forceinline__ bool rightStarts(int ds, int qe, uint32_t qLen) { return (uint32_t) ds == 0 && (uint32_t) qe == (qLen - 1); }
+__device__ __forceinline__ bool leftStarts(int qs, int de, uint32_t dbLen) { return (uint32_t) qs == 0 && (uint32_t) de == (dbLen - 1); }
+
+// Geometry of a candidate's end overlap with the query at its current length qLen.  The reference pads the target against
+// N^L query N^L; the columns where both are defined are the overlap itself: ncol columns from q0 in the query and t0 in the
+// target.  Where both tests hold the left one decides.  (q0, t0, ncol mean nothing when neither holds: callers test the sides.)
+struct Overlap { bool left, right; uint32_t q0, t0, ncol; };
+__device__ __forceinline__ Overlap endOverlap(const Cand &c, uint32_t qLen) {
+    Overlap o;
+    o.right = rightStarts(c.ds, c.qe, qLen); o.left = leftStarts(c.qs, c.de, c.dbLen);
+    const uint32_t offset = c.dbLen - c.alnLen;
+    if (o.left) { o.t0 = offset; o.q0 = 0; o.ncol = min(c.dbLen - offset, qLen); }
+    else { o.t0 = 0; o.q0 = qLen - c.alnLen; o.ncol = min(c.alnLen, c.dbLen); }
+    return o;
+}
+// the longest overlap per side (maxAlnLeft / maxAlnRight, nuclassembleUtil.cpp:493-499), from the tot columns counted for a candidate
+__device__ __forceinline__ void noteOverlap(const Overlap &o, uint32_t tot, uint32_t &maxLeft, uint32_t &maxRight) {
+    if (o.left && tot > maxLeft) maxLeft = tot; else if (o.right && tot > maxRight) maxRight = tot;
+}
+// Longest overlap of a plain candidate: an end overlap of two sequences without N whose target id is not the query's key (the
+// candidate test compares those two).  updateSeqIdConsensusReads would count the very columns the candidate test just counted, so
+// seqId / rySeqId stand and only the longest overlap per side is updated.
+__device__ __forceinline__ void plainOverlapMax(const Cand &c, uint32_t qLen, uint32_t &maxLeft, uint32_t &maxRight) {
+    const Overlap o = endOverlap(c, qLen);
+    noteOverlap(o, o.ncol, maxLeft, maxRight);
 }
 
-// the same on metadata the caller holds already (no gather of the two sequences' records)
+// damage class of target position ti, the row of the likelihood table: the first five positions, the middle (5), the last five
+__device__ __forceinline__ uint32_t damageClass(uint32_t ti, uint32_t dbLen) { return ti < 5 ? ti : (ti >= dbLen - 5 ? 6 + (ti - (dbLen - 5)) : 5); }
+
+// identical / same-RY-class columns of q[q0..q0+n) vs t[t0..t0+n), 16 bases per XOR (neither sequence has an N), on metadata the
+// caller holds (word offsets, last word index)
 __device__ __forceinline__ void countMatchesWordsAt(const uint32_t *__restrict__ codes, uint32_t qw, uint32_t qLast, uint32_t q0, uint32_t tw, uint32_t tLast, uint32_t t0, uint32_t n, int &idCnt, int &idRy) {
     uint32_t mm = 0, ry = 0;
     for (uint32_t k = 0; k < n; k += 16) {
@@ -183,20 +202,48 @@ __device__ __forceinline__ void countMatchesWordsAt(const uint32_t *__restrict__
     }
     idCnt = (int) (n - mm); idRy = (int) (n - ry);
 }
+// the same letter by letter, for sequences with N or other letters (:282-287): letters are compared, so N == N; N maps to purine
+// (0) in ryMap
+__device__ __forceinline__ void countMatchesLetters(const ExtArgs &A, uint32_t q, uint32_t qw, uint32_t q0, uint32_t t, uint32_t tw, uint32_t t0, uint32_t n, int &idCnt, int &idRy) {
+    idCnt = 0; idRy = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t qc, tc; bool qn, tn;
+        letterOf(A, q, qw, q0 + i, qc, qn); letterOf(A, t, tw, t0 + i, tc, tn);
+        idCnt += ((qn ? 4u : qc) == (tn ? 4u : tc));
+        idRy += (ryClass(qn ? 0u : qc) == ryClass(tn ? 0u : tc));
+    }
+}
+
+// The columns of a plain end overlap (no pieces, no N in either sequence: the target position is the column's index in the target)
+// in order, 16-base windows of the two sequences at a time, the next windows on their way while these are worked on:
+// f(damage class, query base, target base) per column.
+template <typename F>
+__device__ __forceinline__ void walkPlainColumns(const ExtArgs &A, const VQuery &Q, const Cand &c, const Overlap &o, F f) {
+    const uint32_t qw = Q.qw, tw = A.woff[c.target];
+    const uint32_t qLast = (Q.qLen0 + 15) / 16 - 1, tLast = (c.dbLen + 15) / 16 - 1;
+    uint32_t qNext = cdm_window16(A.codes, qw, o.q0, qLast), tNext = cdm_window16(A.codes, tw, o.t0, tLast);
+    for (uint32_t k = 0; k < o.ncol; k += 16) {
+        uint32_t qwin = qNext, twin = tNext;
+        if (k + 16 < o.ncol) { qNext = cdm_window16(A.codes, qw, o.q0 + k + 16, qLast); tNext = cdm_window16(A.codes, tw, o.t0 + k + 16, tLast); }
+        const uint32_t m = min(16u, o.ncol - k);
+        for (uint32_t j = 0; j < m; j++) {
+            f(damageClass(o.t0 + k + j, c.dbLen), qwin & 3u, twin & 3u);
+            qwin >>= 2; twin >>= 2;
+        }
+    }
+}
 
 // updateSeqIdConsensusReads for one candidate on the current query (nuclassembleUtil.cpp:377-500, safe-mode consensus)
 __device__ void updateIds(const ExtArgs &A, const VQuery &Q, Cand &c, uint32_t &maxLeft, uint32_t &maxRight, const ConsList *cons = nullptr) {
     const uint32_t qLen = Q.total;
-    const bool rightStart = (uint32_t) c.ds == 0 && (uint32_t) c.qe == (qLen - 1);
-    const bool leftStart = (uint32_t) c.qs == 0 && (uint32_t) c.de == (c.dbLen - 1);
+    const Overlap o = endOverlap(c, qLen);
     int idCnt = 0, idRy = 0; uint32_t tot = 0;
-    if (cons && (leftStart || rightStart)) {
+    if (cons && (o.left || o.right)) {
         // unsafe mode: the padded target against the whole consensus, overhang included (:389-437); target letter j sits at
-        // consensus index c0 + j
-        const uint32_t offset = c.dbLen - c.alnLen;
-        if (offset > qLen) A.flags[0] = 1u;         // the reference pads with qLen - offset letters: undefined
+        // consensus index c0 + j (the query is the middle third: column q0 of the query lies under target letter t0)
+        if (c.dbLen - c.alnLen > qLen) A.flags[0] = 1u;         // the reference pads with qLen - offset letters: undefined
         else {
-            const uint32_t c0 = leftStart ? (qLen - offset) : (2 * qLen - c.alnLen);
+            const uint32_t c0 = qLen + o.q0 - o.t0;
             for (uint32_t j = 0; j < c.dbLen && c0 + j < 3 * qLen; j++) {
                 uint32_t qc, tc; bool qn, tn;
                 consensusAt(A, Q, *cons, c0 + j, qc, qn); targetBaseAt(A, c.target, j, tc, tn);
@@ -205,41 +252,35 @@ __device__ void updateIds(const ExtArgs &A, const VQuery &Q, Cand &c, uint32_t &
             }
         }
     } else
-    if (leftStart || rightStart) {
-        // padded target against N^L query N^L: the columns where both are defined are the overlap itself
-        const uint32_t offset = c.dbLen - c.alnLen;
-        uint32_t q0, t0, ncol;
-        if (leftStart) { t0 = offset; q0 = 0; ncol = min(c.dbLen - offset, qLen); }
-        else { t0 = 0; q0 = qLen - c.alnLen; ncol = min(c.alnLen, c.dbLen); }
-        if (Q.plain && !A.hasN[c.target]) { countMatchesWords(A, Q.q, q0, c.target, t0, ncol, idCnt, idRy); tot = ncol; }
-        else
-        for (uint32_t i = 0; i < ncol; i++) {
+    if (o.left || o.right) {
+        if (Q.plain && !A.hasN[c.target]) {
+            countMatchesWordsAt(A.codes, Q.qw, (Q.qLen0 + 15) / 16 - 1, o.q0, A.woff[c.target], (c.dbLen + 15) / 16 - 1, o.t0, o.ncol, idCnt, idRy);
+            tot = o.ncol;
+        } else
+        for (uint32_t i = 0; i < o.ncol; i++) {
             uint32_t qc, tc; bool qn, tn;
-            Q.baseAt(q0 + i, qc, qn); targetBaseAt(A, c.target, t0 + i, tc, tn);
+            Q.baseAt(o.q0 + i, qc, qn); targetBaseAt(A, c.target, o.t0 + i, tc, tn);
             if (qn || tn) continue;
             idCnt += (qc == tc); idRy += (ryClass(qc) == ryClass(tc)); tot++;
         }
     }
     if (tot != 0) { c.seqId = static_cast<float>(idCnt) / tot; c.rySeqId = static_cast<float>(idRy) / tot; }
-    if (leftStart && tot > maxLeft) maxLeft = tot; else if (rightStart && tot > maxRight) maxRight = tot;
+    noteOverlap(o, tot, maxLeft, maxRight);
 }
 
 // calcLikelihoodConsensus via r_s_pair; returns sRatio > threshold, sets c.sLenNorm
 __device__ bool scoreCand(const ExtArgs &A, const VQuery &Q, Cand &c, uint32_t maxLeft, uint32_t maxRight, const double *logLik /* [11][4][4] fwd */,
                           const ConsList *cons = nullptr, const X87 *logLikX = nullptr /* the same table, converted once */) {
     const uint32_t qLen = Q.total;
-    uint32_t maxAln = maxRight;
-    if ((uint32_t) c.qs == 0 && (uint32_t) c.de == (c.dbLen - 1)) maxAln = maxLeft;
-    const bool rightStart = (uint32_t) c.ds == 0 && (uint32_t) c.qe == (qLen - 1);
-    const bool leftStart = (uint32_t) c.qs == 0 && (uint32_t) c.de == (c.dbLen - 1);
+    const Overlap o = endOverlap(c, qLen);
+    const uint32_t maxAln = o.left ? maxLeft : maxRight;
     X87 lik = x87_zero();
     uint32_t alnCount = 0;
-    if (cons && (leftStart || rightStart)) {
+    if (cons && (o.left || o.right)) {
         // unsafe mode: every target letter against the consensus letter above it (:225-330), flanks included
-        const uint32_t offset = c.dbLen - c.alnLen;
-        if (offset > qLen) A.flags[0] = 1u;
+        if (c.dbLen - c.alnLen > qLen) A.flags[0] = 1u;
         else {
-            const uint32_t c0 = leftStart ? (qLen - offset) : (2 * qLen - c.alnLen);
+            const uint32_t c0 = qLen + o.q0 - o.t0;
             uint32_t tIdx = 0;
             for (uint32_t j = 0; j < c.dbLen && c0 + j < 3 * qLen; j++) {
                 uint32_t qc, tc; bool qn, tn;
@@ -249,62 +290,29 @@ __device__ bool scoreCand(const ExtArgs &A, const VQuery &Q, Cand &c, uint32_t m
                 consensusAt(A, Q, *cons, c0 + j, qc, qn);
                 if (qn) continue;
                 alnCount++;
-                const uint32_t ti = tIdx - 1;
-                const uint32_t cls = ti < 5 ? ti : (ti >= c.dbLen - 5 ? 6 + (ti - (c.dbLen - 5)) : 5);
-                lik = x87_add(lik, x87_from_double(logLik[(cls * 4 + fwdBase(qc)) * 4 + fwdBase(tc)]));
+                lik = x87_add(lik, x87_from_double(logLik[(damageClass(tIdx - 1, c.dbLen) * 4 + fwdBase(qc)) * 4 + fwdBase(tc)]));
             }
         }
     } else
-    if (leftStart || rightStart) {
-        const uint32_t offset = c.dbLen - c.alnLen;
-        uint32_t q0, t0, ncol;
-        if (leftStart) { t0 = offset; q0 = 0; ncol = min(c.dbLen - offset, qLen); }
-        else { t0 = 0; q0 = qLen - c.alnLen; ncol = min(c.alnLen, c.dbLen); }
-        // tIdx counts the non-N target letters up to and including the column (pad letters are 'N'); before the overlap
-        // the left-start target contributes its own prefix t[0..offset)
-        uint32_t tIdx = 0;
+    if (o.left || o.right) {
         if (Q.plain && !A.hasN[c.target]) {
-            // no N anywhere: tIdx - 1 is the target position itself; walk the two sequences a 16-base word at a time
-            const uint32_t qw = A.woff[Q.q], tw = A.woff[c.target];
-            const uint32_t qLast = (Q.qLen0 + 15) / 16 - 1, tLast = (c.dbLen + 15) / 16 - 1;
-            const uint32_t tailFrom = c.dbLen - 5;
-            if (logLikX) {
-            uint32_t qNext = cdm_window16(A.codes, qw, q0, qLast), tNext = cdm_window16(A.codes, tw, t0, tLast);
-            for (uint32_t k = 0; k < ncol; k += 16) {
-                uint32_t qwin = qNext, twin = tNext;          // (the next 16 columns are on their way while these are summed)
-                if (k + 16 < ncol) { qNext = cdm_window16(A.codes, qw, q0 + k + 16, qLast); tNext = cdm_window16(A.codes, tw, t0 + k + 16, tLast); }
-                const uint32_t m = min(16u, ncol - k);
-                for (uint32_t j = 0; j < m; j++) {
-                    const uint32_t ti = t0 + k + j;
-                    const uint32_t cls = ti < 5 ? ti : (ti >= tailFrom ? 6 + (ti - tailFrom) : 5);
-                    lik = x87_acc(lik, logLikX[(cls * 4 + (qwin & 3u)) * 4 + (twin & 3u)]);
-                    qwin >>= 2; twin >>= 2;
-                }
-            }
-            } else
-            for (uint32_t k = 0; k < ncol; k += 16) {
-                uint32_t qwin = cdm_window16(A.codes, qw, q0 + k, qLast), twin = cdm_window16(A.codes, tw, t0 + k, tLast);
-                const uint32_t m = min(16u, ncol - k);
-                for (uint32_t j = 0; j < m; j++) {
-                    const uint32_t ti = t0 + k + j;
-                    const uint32_t cls = ti < 5 ? ti : (ti >= tailFrom ? 6 + (ti - tailFrom) : 5);
-                    lik = x87_acc(lik, x87_from_double(logLik[(cls * 4 + (qwin & 3u)) * 4 + (twin & 3u)]));
-                    qwin >>= 2; twin >>= 2;
-                }
-            }
-            alnCount = ncol;
+            // no N anywhere: the sum runs over the target positions themselves, a 16-base word of the two sequences at a time
+            if (logLikX) walkPlainColumns(A, Q, c, o, [&](uint32_t cls, uint32_t qb, uint32_t tb) { lik = x87_acc(lik, logLikX[(cls * 4 + qb) * 4 + tb]); });
+            else walkPlainColumns(A, Q, c, o, [&](uint32_t cls, uint32_t qb, uint32_t tb) { lik = x87_acc(lik, x87_from_double(logLik[(cls * 4 + qb) * 4 + tb])); });
+            alnCount = o.ncol;
         } else {
-        if (leftStart) for (uint32_t j = 0; j < t0; j++) { uint32_t tc; bool tn; targetBaseAt(A, c.target, j, tc, tn); tIdx += !tn; }
-        for (uint32_t i = 0; i < ncol; i++) {
-            uint32_t qc, tc; bool qn, tn;
-            Q.baseAt(q0 + i, qc, qn); targetBaseAt(A, c.target, t0 + i, tc, tn);
-            if (!tn) tIdx++;
-            if (qn || tn) continue;
-            alnCount++;
-            const uint32_t ti = tIdx - 1;
-            const uint32_t cls = ti < 5 ? ti : (ti >= c.dbLen - 5 ? 6 + (ti - (c.dbLen - 5)) : 5);
-            lik = x87_add(lik, x87_from_double(logLik[(cls * 4 + fwdBase(qc)) * 4 + fwdBase(tc)]));
-        }
+            // tIdx counts the non-N target letters up to and including the column (pad letters are 'N'); before the overlap
+            // the left-start target contributes its own prefix t[0..offset)
+            uint32_t tIdx = 0;
+            if (o.left) for (uint32_t j = 0; j < o.t0; j++) { uint32_t tc; bool tn; targetBaseAt(A, c.target, j, tc, tn); tIdx += !tn; }
+            for (uint32_t i = 0; i < o.ncol; i++) {
+                uint32_t qc, tc; bool qn, tn;
+                Q.baseAt(o.q0 + i, qc, qn); targetBaseAt(A, c.target, o.t0 + i, tc, tn);
+                if (!tn) tIdx++;
+                if (qn || tn) continue;
+                alnCount++;
+                lik = x87_add(lik, x87_from_double(logLik[(damageClass(tIdx - 1, c.dbLen) * 4 + fwdBase(qc)) * 4 + fwdBase(tc)]));
+            }
         }
     }
     const uint32_t excess = maxAln - alnCount;
@@ -326,39 +334,80 @@ __device__ bool scoreCand(const ExtArgs &A, const VQuery &Q, Cand &c, uint32_t m
 // twice that.  Returns 1 / 0 when randAln - sum lies outside ratioLogit +- bound (scoreCand's answer is then the same), -1 when not;
 // sLenNorm = the plain sum, bound as above.
 __device__ int scoreCandApprox(const ExtArgs &A, const VQuery &Q, const Cand &c, uint32_t maxLeft, uint32_t maxRight, const double *logLik, double &sLenNorm, float &bound) {
-    const uint32_t qLen = Q.total;
-    const bool leftStart = (uint32_t) c.qs == 0 && (uint32_t) c.de == (c.dbLen - 1);
-    const uint32_t maxAln = leftStart ? maxLeft : maxRight;
-    const uint32_t offset = c.dbLen - c.alnLen;
-    uint32_t q0, t0, ncol;
-    if (leftStart) { t0 = offset; q0 = 0; ncol = min(c.dbLen - offset, qLen); }
-    else { t0 = 0; q0 = qLen - c.alnLen; ncol = min(c.alnLen, c.dbLen); }
-    const uint32_t qw = A.woff[Q.q], tw = A.woff[c.target];
-    const uint32_t qLast = (Q.qLen0 + 15) / 16 - 1, tLast = (c.dbLen + 15) / 16 - 1, tailFrom = c.dbLen - 5;
+    const Overlap o = endOverlap(c, Q.total);
+    const uint32_t maxAln = o.left ? maxLeft : maxRight;
     double sum = 0.0, mag = 0.0;
-    uint32_t qNext = cdm_window16(A.codes, qw, q0, qLast), tNext = cdm_window16(A.codes, tw, t0, tLast);
-    for (uint32_t k = 0; k < ncol; k += 16) {
-        uint32_t qwin = qNext, twin = tNext;
-        if (k + 16 < ncol) { qNext = cdm_window16(A.codes, qw, q0 + k + 16, qLast); tNext = cdm_window16(A.codes, tw, t0 + k + 16, tLast); }
-        const uint32_t m = min(16u, ncol - k);
-        for (uint32_t j = 0; j < m; j++) {
-            const uint32_t ti = t0 + k + j;
-            const uint32_t cls = ti < 5 ? ti : (ti >= tailFrom ? 6 + (ti - tailFrom) : 5);
-            const double t = logLik[(cls * 4 + (qwin & 3u)) * 4 + (twin & 3u)];
-            sum = __dadd_rn(sum, t); mag = __dadd_rn(mag, fabs(t));
-            qwin >>= 2; twin >>= 2;
-        }
-    }
-    const uint32_t excess = maxAln - ncol;
+    walkPlainColumns(A, Q, c, o, [&](uint32_t cls, uint32_t qb, uint32_t tb) {
+        const double t = logLik[(cls * 4 + qb) * 4 + tb];
+        sum = __dadd_rn(sum, t); mag = __dadd_rn(mag, fabs(t));
+    });
+    const uint32_t excess = maxAln - o.ncol;
     const double pen = (double) ((float) excess * A.excessLog);
     sum = __dadd_rn(sum, pen); mag = __dadd_rn(mag, fabs(pen));
     const double randAln = (double) ((float) maxAln * A.randLog);
-    const double b = fmax((double) (ncol + 8u) * 0x1p-52 * (mag + fabs(randAln)) * (double) A.marginScale, A.ratioWindow);       // (inside the window the exact sum is taken, and flags the call)
+    const double b = fmax((double) (o.ncol + 8u) * 0x1p-52 * (mag + fabs(randAln)) * (double) A.marginScale, A.ratioWindow);       // (inside the window the exact sum is taken, and flags the call)
     sLenNorm = sum; bound = (float) b * 1.0000002f + 1e-37f;       // (rounded up: the float is what the queue's near-tie test adds)
     const double x = __dadd_rn(randAln, -sum);
     if (x < A.ratioLogit - b) return 1;
     if (x > A.ratioLogit + b) return 0;
     return -1;
+}
+
+// ---- A-C for one record of query q: the end-overlap test, the strand test, the identities recomputed on the corrected sequences
+// and the candidate gate ("notContig", :202-315).  qm / tm: the metadata of the query and of the record's target, which the
+// caller has fetched (when it does so is the caller's business).  seqId / rySeqId are set for a candidate only.
+struct CandTest { bool ok, left, right; uint32_t alnLen; float seqId, rySeqId; };
+__device__ __forceinline__ uint32_t recAlnLen(const AlnRec &rec) { return (uint32_t) max(abs(rec.qEnd - rec.qStart), abs(rec.dbEnd - rec.dbStart)) + 1u; }
+__device__ __forceinline__ CandTest candidateTest(const ExtArgs &A, const AlnRec &rec, uint32_t q, const SeqMeta &qm, const SeqMeta &tm) {
+    CandTest T; T.ok = false; T.alnLen = 0; T.seqId = rec.seqId; T.rySeqId = 0.f;
+    T.right = rightStarts(rec.dbStart, rec.qEnd, qm.len); T.left = leftStarts(rec.qStart, rec.dbEnd, tm.len);
+    if (!T.right && !T.left) return T;
+    if (rec.qStart > rec.qEnd) return T;   // cannot happen given the test above; reverse strand never extends
+    T.alnLen = recAlnLen(rec);
+    if (rec.target != qm.key) {   // the reference compares the target's *id* with the query's *key* (:264)
+        int idCnt, idRy;
+        const uint32_t n = (uint32_t) (rec.qEnd - rec.qStart + 1);
+        if (((qm.flags | tm.flags) & 1u) == 0) countMatchesWordsAt(A.codes, qm.woff, (qm.len + 15) / 16 - 1, (uint32_t) rec.qStart, tm.woff, (tm.len + 15) / 16 - 1, (uint32_t) rec.dbStart, n, idCnt, idRy);
+        else countMatchesLetters(A, q, qm.woff, (uint32_t) rec.qStart, rec.target, tm.woff, (uint32_t) rec.dbStart, n, idCnt, idRy);
+        T.seqId = static_cast<float>(idCnt) / T.alnLen; T.rySeqId = static_cast<float>(idRy) / T.alnLen;
+    }
+    const bool wasExtended = (tm.flags >> 1) & 1u, noOffset = (tm.len - T.alnLen) == 0;
+    T.ok = !wasExtended && T.alnLen >= 30 && T.seqId >= A.seqIdThr && !noOffset;
+    return T;
+}
+__device__ __forceinline__ void candFill(Cand &c, const AlnRec &rec, uint32_t alnLen, const SeqMeta &tm, uint32_t qLen0, float seqId, float rySeqId, uint32_t r) {
+    const uint32_t tLen = tm.len; c.tKey = tm.key;
+    c.qs = rec.qStart; c.qe = rec.qEnd; c.ds = rec.dbStart; c.de = rec.dbEnd; c.target = rec.target; c.alnLen = alnLen; c.dbLen = tLen;
+    c.qLen = qLen0; c.seqId = seqId; c.rySeqId = rySeqId; c.sLenNorm = 0; c.pieceStart = r; c.pieceLen = 0;   // pieceStart keeps the record index until used
+}
+
+// D's gate (:351-357): which candidates of the first round are scored at all.  It needs nothing of the query's other records.
+__device__ __forceinline__ bool scoredAtAll(const ExtArgs &A, const Cand &c, uint32_t qKey) {
+    const bool notInside = c.dbLen != c.alnLen, rightStart = c.ds == 0, leftStart = c.qs == 0, notId = c.tKey != qKey;
+    return (rightStart || leftStart) && notInside && notId && c.rySeqId >= A.rySeqIdThr && c.seqId >= A.seqIdThr;
+}
+
+// ---- a query's four slices of `lists` (r0 = its first record, nRec = its records), and the one place that fills a VQuery
+struct QLists { uint32_t *heap, *park, *left, *right; };
+__device__ __forceinline__ QLists queryLists(const ExtArgs &A, uint64_t r0, uint32_t nRec) {
+    QLists L; L.heap = A.lists + 4 * r0; L.park = L.heap + nRec; L.left = L.park + nRec; L.right = L.left + nRec;
+    return L;
+}
+// The query as the algorithm starts on it; L = nullptr where no piece is ever looked up (the record form's scoring).  grown: as
+// extendLoop() left it (the pieces recorded in nLeft / nRight / leftTotal / newLen), for the kernels that write the output.
+__device__ __forceinline__ void queryView(VQuery &Q, const ExtArgs &A, uint32_t q, const SeqMeta &qm, const Cand *cand = nullptr, const QLists *L = nullptr, bool grown = false) {
+    Q.a = &A; Q.q = q; Q.qLen0 = qm.len; Q.qw = qm.woff; Q.cand = cand; Q.leftL = L ? L->left : nullptr; Q.rightL = L ? L->right : nullptr;
+    Q.nL = grown ? A.nLeft[q] : 0; Q.nR = grown ? A.nRight[q] : 0; Q.leftTotal = grown ? A.leftTotal[q] : 0;
+    Q.total = grown ? A.newLen[q] : qm.len; Q.plain = !grown && (qm.flags & 1u) == 0;
+}
+
+// the likelihood table into LDS (and, where asked for, converted to X87 once); the caller's next barrier publishes it
+__device__ __forceinline__ void loadLogLik(const ExtArgs &A, double *sLogLik, X87 *sLogLikX = nullptr) {
+    for (int i = threadIdx.x; i < 11 * 16; i += blockDim.x) {
+        const double v = (&A.lut->logLik[0][0][0][0])[i];
+        sLogLik[i] = v;
+        if (sLogLikX) sLogLikX[i] = x87_from_double(v);
+    }
 }
 
 // ---- std::priority_queue<scorePerRes, vector, CompareNuclResultByScoreReads> on candidate indices (libstdc++ heap order)
@@ -387,8 +436,9 @@ struct Heap {
 
 // ---- E: the extension loop of one query (ancientReadsResults.cpp:374-546) on its heap of scored candidates; writes the query's
 // result (new length, piece lists).  Shared by the two forms of the kernel below.
-__device__ void extendLoop(const ExtArgs &A, VQuery &Q, Cand *cand, Heap &heap, uint32_t *parkL, uint32_t *leftL, uint32_t *rightL,
-                           uint32_t maxLeft, uint32_t maxRight, const double *sLogLik, uint32_t qKey, uint32_t q) {
+__device__ void extendLoop(const ExtArgs &A, VQuery &Q, Cand *cand, Heap &heap, const QLists &L, uint32_t maxLeft, uint32_t maxRight,
+                           const double *sLogLik, uint32_t qKey, uint32_t q) {
+    uint32_t *const parkL = L.park, *const leftL = L.left, *const rightL = L.right;
     bool couldExtend = false;
     while (heap.n > 0) {
         uint32_t leftOff = 0, rightOff = 0, nPark = 0;
@@ -474,6 +524,7 @@ __device__ void extendLoop(const ExtArgs &A, VQuery &Q, Cand *cand, Heap &heap, 
         for (uint32_t i = 0; i < nPark; i++) updateIds(A, Q, cand[parkL[i]], maxLeft, maxRight, cons1);
         for (uint32_t i = 0; i < nPark; i++) {
             Cand &c = cand[parkL[i]];
+            // the re-queue gate (:516-521) is not scoredAtAll() (:351-357): the reference tests no rySeqId here
             const bool notInside = c.dbLen != c.alnLen;
             const bool rightStart = c.ds == 0, leftStart = c.qs == 0, notId = c.tKey != qKey;
             if (c.seqId >= A.seqIdThr && (rightStart || leftStart) && notId && notInside) {
@@ -490,58 +541,30 @@ template <int MINW, bool RAW = false>
 __global__ __launch_bounds__(64, MINW) void k_extend(ExtArgs A) {
     if (!RAW) A.raw = nullptr;
     __shared__ double sLogLik[11 * 16];
-    for (int i = threadIdx.x; i < 11 * 16; i += blockDim.x) sLogLik[i] = (&A.lut->logLik[0][0][0][0])[i];
+    loadLogLik(A, sLogLik);
     __syncthreads();
     const unsigned int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= *A.nActive) return;
     const uint32_t q = A.active[item];
     const uint64_t r0 = A.aoff[q], r1 = A.aoff[q + 1];
     const uint32_t nRec = (uint32_t) (r1 - r0);
-    const uint32_t qLen0 = A.len[q], qKey = A.key[q];
+    const SeqMeta *meta = A.len.m;
+    const SeqMeta qm = meta[q];
+    const uint32_t qLen0 = qm.len, qKey = qm.key;
     Cand *cand = A.cand + r0;
-    uint32_t *heapL = A.lists + 4 * r0, *parkL = heapL + nRec, *leftL = parkL + nRec, *rightL = leftL + nRec;
-    VQuery Q; Q.a = &A; Q.q = q; Q.qLen0 = qLen0; Q.qw = A.woff[q]; Q.cand = cand; Q.leftL = leftL; Q.rightL = rightL;
-    Q.nL = 0; Q.nR = 0; Q.leftTotal = 0; Q.total = qLen0; Q.plain = A.hasN[q] == 0;
+    const QLists L = queryLists(A, r0, nRec);
+    VQuery Q; queryView(Q, A, q, qm, cand, &L);
 
     // ---- A-C: candidates ("notContig"), in record order.  The loop is a chain of dependent gathers - record, the target's metadata,
     // its letters - per lane: the next record and its target's metadata are fetched while the current one is worked on.
     uint32_t nCand = 0;   // candidate k lives at cand[k] (compacted), keeping the record index for the score output
-    const SeqMeta *meta = A.len.m;
-    const uint32_t qLastW = (qLen0 + 15) / 16 - 1;
     AlnRec recN = A.rec[r0]; SeqMeta tmN = meta[recN.target];
     for (uint32_t r = 0; r < nRec; r++) {
         const AlnRec rec = recN; const SeqMeta tm = tmN;
         if (r + 1 < nRec) { recN = A.rec[r0 + r + 1]; tmN = meta[recN.target]; }
         if (A.scores) A.scores[r0 + r] = NAN;
-        const uint32_t tLen = tm.len;
-        const uint32_t ds = (uint32_t) rec.dbStart, de = (uint32_t) rec.dbEnd, qs = (uint32_t) rec.qStart, qe = (uint32_t) rec.qEnd;
-        const bool rightStart = ds == 0 && qe == (qLen0 - 1);
-        const bool leftStart = qs == 0 && de == (tLen - 1);
-        if (!rightStart && !leftStart) continue;
-        if (rec.qStart > rec.qEnd) continue;   // cannot happen given the test above; reverse strand never extends
-        const uint32_t alnLen = (uint32_t) max(abs(rec.qEnd - rec.qStart), abs(rec.dbEnd - rec.dbStart)) + 1u;
-        float seqId = rec.seqId, rySeqId = 0.f;
-        if (rec.target != qKey) {   // the reference compares the target's *id* with the query's *key* (:264)
-            int idCnt = 0, idRy = 0;
-            if (Q.plain && !(tm.flags & 1u)) countMatchesWordsAt(A.codes, Q.qw, qLastW, (uint32_t) rec.qStart, tm.woff, (tLen + 15) / 16 - 1, (uint32_t) rec.dbStart, (uint32_t) (rec.qEnd - rec.qStart + 1), idCnt, idRy);
-            else
-            for (int i = rec.qStart; i <= rec.qEnd; i++) {
-                uint32_t qc, tc; bool qn, tn;
-                Q.baseAt((uint32_t) i, qc, qn); targetBaseAt(A, rec.target, (uint32_t) (rec.dbStart + (i - rec.qStart)), tc, tn);
-                // letters are compared: N == N; N maps to purine (0) in ryMap
-                const uint32_t ql = qn ? 4u : qc, tl = tn ? 4u : tc;
-                idCnt += (ql == tl);
-                idRy += (ryClass(qn ? 0u : qc) == ryClass(tn ? 0u : tc));
-            }
-            seqId = static_cast<float>(idCnt) / alnLen; rySeqId = static_cast<float>(idRy) / alnLen;
-        }
-        const bool noOffset = (tLen - alnLen) == 0;
-        if (((tm.flags >> 1) & 1u) == 0 && alnLen >= 30 && seqId >= A.seqIdThr && !noOffset) {
-            Cand c; c.qs = rec.qStart; c.qe = rec.qEnd; c.ds = rec.dbStart; c.de = rec.dbEnd; c.target = rec.target; c.alnLen = alnLen; c.dbLen = tLen;
-            c.qLen = qLen0; c.seqId = seqId; c.rySeqId = rySeqId; c.sLenNorm = 0; c.pieceStart = r; c.pieceLen = 0;   // pieceStart keeps the record index until used
-            c.tKey = tm.key;
-            cand[nCand++] = c;
-        }
+        const CandTest T = candidateTest(A, rec, q, qm, tm);
+        if (T.ok) candFill(cand[nCand++], rec, T.alnLen, tm, qLen0, T.seqId, T.rySeqId, r);
     }
     if (nCand == 0) { A.newLen[q] = 0; return; }
     uint32_t maxLeft = 0, maxRight = 0;
@@ -550,30 +573,21 @@ __global__ __launch_bounds__(64, MINW) void k_extend(ExtArgs A) {
     for (uint32_t k = 0; k < nCand; k++) {
         Cand &c = cand[k];
         if (A.unsafe) updateIds(A, Q, c, maxLeft, maxRight, cons0);
-        else if (Q.plain && !A.hasN[c.target] && c.target != qKey) {      // (the candidate pass compares the target id with the query key)
-            // updateSeqIdConsensusReads would count the very columns the candidate pass above just counted (an end overlap of
-            // two sequences without N): seqId / rySeqId stand, only the longest overlap per side is updated
-            const bool rightStart = (uint32_t) c.ds == 0 && (uint32_t) c.qe == (qLen0 - 1);
-            const bool leftStart = (uint32_t) c.qs == 0 && (uint32_t) c.de == (c.dbLen - 1);
-            const uint32_t offset = c.dbLen - c.alnLen;
-            const uint32_t tot = leftStart ? min(c.dbLen - offset, qLen0) : (rightStart ? min(c.alnLen, c.dbLen) : 0u);
-            if (leftStart && tot > maxLeft) maxLeft = tot; else if (rightStart && tot > maxRight) maxRight = tot;
-        } else updateIds(A, Q, c, maxLeft, maxRight);
+        else if (Q.plain && !A.hasN[c.target] && c.target != qKey) plainOverlapMax(c, qLen0, maxLeft, maxRight);
+        else updateIds(A, Q, c, maxLeft, maxRight);
     }
     // ---- D
-    Heap heap; heap.h = heapL; heap.n = 0; heap.cand = cand;
+    Heap heap; heap.h = L.heap; heap.n = 0; heap.cand = cand;
     for (uint32_t k = 0; k < nCand; k++) {
         Cand &c = cand[k];
-        const bool notInside = c.dbLen != c.alnLen;
-        const bool rightStart = c.ds == 0, leftStart = c.qs == 0, notId = c.tKey != qKey;
-        if ((rightStart || leftStart) && notInside && notId && c.rySeqId >= A.rySeqIdThr && c.seqId >= A.seqIdThr) {
+        if (scoredAtAll(A, c, qKey)) {
             const bool pass = scoreCand(A, Q, c, maxLeft, maxRight, sLogLik, cons0);
             if (A.scores) A.scores[r0 + c.pieceStart] = c.sLenNorm;
             if (pass) heap.push(k);
         }
     }
     // ---- E
-    extendLoop(A, Q, cand, heap, parkL, leftL, rightL, maxLeft, maxRight, sLogLik, qKey, q);
+    extendLoop(A, Q, cand, heap, L, maxLeft, maxRight, sLogLik, qKey, q);
 }
 
 // ---------------------------------------------------------------------------------------------- A-D, one thread per RECORD
@@ -588,7 +602,9 @@ __global__ __launch_bounds__(64, MINW) void k_extend(ExtArgs A) {
 //                  records that enter the queue to sLen[]; queries with at least one such record to the work list
 //   k_xr_extend    one thread per query of the work list: queue in record order (the push order of the reference), extendLoop()
 // Same arithmetic, same order of pushes; a candidate that is a left AND a right overlap at once (whose contribution to the two
-// maxima depends on the order of the records in the reference) sets X.fallback and the call is redone by k_extend.
+// maxima depends on the order of the records in the reference) sets X.fallback and the call is redone by k_extend.  No ungapped
+// record can be one - a left and a right start together mean qLen == tLen == alnLen, which the candidate gate's noOffset rejects:
+// the fallback guards alignment sets uploaded through the C ABI.
 constexpr int XR_NT = 512, XR_T = 448, XR_QCAP = 512, XR_LCAP = 1024, XR_BINS = 32;
 struct XrArgs {
     const uint32_t *winQ;      // [windows + 1] first query of every window
@@ -608,17 +624,6 @@ __global__ void k_xr_windows(const uint64_t *__restrict__ aoff, uint32_t n, uint
     while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (aoff[mid] < x) lo = mid + 1; else hi = mid; }
     winQ[b] = lo;
 }
-__device__ __forceinline__ void xrFill(Cand &c, const AlnRec &rec, uint32_t alnLen, const SeqMeta &tm, uint32_t qLen0, float seqId, float rySeqId, uint32_t r) {
-    const uint32_t tLen = tm.len; c.tKey = tm.key;
-    c.qs = rec.qStart; c.qe = rec.qEnd; c.ds = rec.dbStart; c.de = rec.dbEnd; c.target = rec.target; c.alnLen = alnLen; c.dbLen = tLen;
-    c.qLen = qLen0; c.seqId = seqId; c.rySeqId = rySeqId; c.sLenNorm = 0; c.pieceStart = r; c.pieceLen = 0;
-}
-__device__ __forceinline__ uint32_t xrAlnLen(const AlnRec &rec) { return (uint32_t) max(abs(rec.qEnd - rec.qStart), abs(rec.dbEnd - rec.dbStart)) + 1u; }
-__device__ __forceinline__ void xrQuery(VQuery &Q, const ExtArgs &A, uint32_t q, const SeqMeta &qm) {
-    Q.a = &A; Q.q = q; Q.qLen0 = qm.len; Q.qw = qm.woff; Q.cand = nullptr; Q.leftL = nullptr; Q.rightL = nullptr;
-    Q.nL = 0; Q.nR = 0; Q.leftTotal = 0; Q.total = qm.len; Q.plain = (qm.flags & 1u) == 0;
-}
-
 #ifndef CDM_XRS_MINB
 #define CDM_XRS_MINB 3      // blocks per CU the record kernel's registers leave room for (1 / 3 / 4: 21.1 / 20.85 / 20.95 ms)
 #endif
@@ -632,7 +637,7 @@ __global__ __launch_bounds__(XR_NT, CDM_XRS_MINB) void k_xr_score(ExtArgs A, XrA
     __shared__ uint32_t sListA[XR_LCAP], sListB[XR_LCAP];
     __shared__ uint8_t sBinOf[XR_LCAP];
     __shared__ unsigned int sElig, sBinCnt[XR_BINS], sBinBase[XR_BINS];
-    for (int i = threadIdx.x; i < 11 * 16; i += XR_NT) { const double v = (&A.lut->logLik[0][0][0][0])[i]; sLogLik[i] = v; sLogLikX[i] = x87_from_double(v); }
+    loadLogLik(A, sLogLik, sLogLikX);
     const uint32_t qFirst = X.winQ[blockIdx.x], qEnd = X.winQ[blockIdx.x + 1];
     const SeqMeta *meta = A.len.m;
     for (uint32_t qb = qFirst; qb < qEnd; qb += XR_QCAP) {      // (more than XR_QCAP queries in a window: only when some have no record)
@@ -655,56 +660,26 @@ __global__ __launch_bounds__(XR_NT, CDM_XRS_MINB) void k_xr_score(ExtArgs A, XrA
             float2 out = make_float2(NAN, 0.f);
             if (sOff[ord + 1] - sOff[ord] > 1) {
                 const AlnRec rec = A.rec[ra + i]; const SeqMeta qm = meta[q];
-                const uint32_t qLen0 = qm.len, qKey = qm.key;
-                const uint32_t ds = (uint32_t) rec.dbStart, de = (uint32_t) rec.dbEnd, qs = (uint32_t) rec.qStart, qe = (uint32_t) rec.qEnd;
-                const bool rightStart = ds == 0 && qe == (qLen0 - 1);
                 // (the target's metadata - a random 16-byte read - only for a record that can still be an end overlap: forward strand, and
                 // either a right start or a query start at 0, which a left start needs)
-                SeqMeta tm = {0, 0, 0, 0};
-                const bool maybe = !(rec.qStart > rec.qEnd) && (rightStart || qs == 0);
-                if (maybe) tm = meta[rec.target];
-                const uint32_t tLen = tm.len;
-                const bool leftStart = maybe && qs == 0 && de == (tLen - 1);
-                if (maybe && (rightStart || leftStart)) {
-                    const uint32_t alnLen = xrAlnLen(rec);
-                    const bool plain = (qm.flags & 1u) == 0 && (tm.flags & 1u) == 0;
-                    float seqId = rec.seqId, rySeqId = 0.f;
-                    if (rec.target != qKey) {
-                        int idCnt = 0, idRy = 0;
-                        if (plain) countMatchesWordsAt(A.codes, qm.woff, (qLen0 + 15) / 16 - 1, (uint32_t) rec.qStart, tm.woff, (tLen + 15) / 16 - 1, (uint32_t) rec.dbStart, (uint32_t) (rec.qEnd - rec.qStart + 1), idCnt, idRy);
-                        else
-                        for (int j = rec.qStart; j <= rec.qEnd; j++) {
-                            uint32_t qc, tc; bool qn, tn;
-                            letterOf(A, q, qm.woff, (uint32_t) j, qc, qn); letterOf(A, rec.target, tm.woff, (uint32_t) (rec.dbStart + (j - rec.qStart)), tc, tn);
-                            const uint32_t ql = qn ? 4u : qc, tl = tn ? 4u : tc;
-                            idCnt += (ql == tl);
-                            idRy += (ryClass(qn ? 0u : qc) == ryClass(tn ? 0u : tc));
-                        }
-                        seqId = static_cast<float>(idCnt) / alnLen; rySeqId = static_cast<float>(idRy) / alnLen;
-                    }
-                    const bool noOffset = (tLen - alnLen) == 0;
-                    if (((tm.flags >> 1) & 1u) == 0 && alnLen >= 30 && seqId >= A.seqIdThr && !noOffset) {
-                        if (leftStart && rightStart) X.fallback[0] = 1u;
+                const bool rightStart = rightStarts(rec.dbStart, rec.qEnd, qm.len);
+                const bool maybe = !(rec.qStart > rec.qEnd) && (rightStart || rec.qStart == 0);
+                if (maybe) {
+                    const SeqMeta tm = meta[rec.target];
+                    const CandTest T = candidateTest(A, rec, q, qm, tm);
+                    if (T.ok) {
+                        Cand c; candFill(c, rec, T.alnLen, tm, qm.len, T.seqId, T.rySeqId, i);
+                        if (T.left && T.right) X.fallback[0] = 1u;
                         uint32_t mL = 0, mR = 0;
-                        if (plain && rec.target != qKey) {
-                            const uint32_t offset = tLen - alnLen;
-                            const uint32_t tot = leftStart ? min(tLen - offset, qLen0) : min(alnLen, tLen);
-                            if (leftStart) mL = tot; else mR = tot;
-                        } else {
-                            Cand c; xrFill(c, rec, alnLen, tm, qLen0, seqId, rySeqId, i);
-                            VQuery Q; xrQuery(Q, A, q, qm);
-                            updateIds(A, Q, c, mL, mR);
-                            seqId = c.seqId; rySeqId = c.rySeqId;
-                        }
+                        if (((qm.flags | tm.flags) & 1u) == 0 && rec.target != qm.key) plainOverlapMax(c, qm.len, mL, mR);
+                        else { VQuery Q; queryView(Q, A, q, qm); updateIds(A, Q, c, mL, mR); }
                         if (mL) atomicMax(&sMaxL[ord], mL);
                         if (mR) atomicMax(&sMaxR[ord], mR);
-                        out = make_float2(seqId, rySeqId);
-                        // D's gate (:317-330) needs nothing of the other records: the scored ones go to the block's list
-                        const bool notInside = tLen != alnLen, notId = tm.key != qKey;
-                        if ((rec.dbStart == 0 || rec.qStart == 0) && notInside && notId && rySeqId >= A.rySeqIdThr && seqId >= A.seqIdThr) {
+                        out = make_float2(c.seqId, c.rySeqId);
+                        if (scoredAtAll(A, c, qm.key)) {          // the scored ones go to the block's list
                             const uint32_t slot = atomicAdd(&sElig, 1u);
                             if (slot < XR_LCAP) {
-                                const uint32_t bin = min((uint32_t) XR_BINS - 1u, alnLen >> 3);
+                                const uint32_t bin = min((uint32_t) XR_BINS - 1u, T.alnLen >> 3);
                                 sListA[slot] = i; sBinOf[slot] = (uint8_t) bin; atomicAdd(&sBinCnt[bin], 1u);
                             } else X.elig[ra + slot] = i;
                         }
@@ -728,8 +703,8 @@ __global__ __launch_bounds__(XR_NT, CDM_XRS_MINB) void k_xr_score(ExtArgs A, XrA
             const uint32_t ord = lo, q = qb + ord;
             const float2 l = X.lite[ra + i];
             const AlnRec rec = A.rec[ra + i]; const SeqMeta tm = meta[rec.target], qm = meta[q];
-            Cand c; xrFill(c, rec, xrAlnLen(rec), tm, qm.len, l.x, l.y, i);
-            VQuery Q; xrQuery(Q, A, q, qm);
+            Cand c; candFill(c, rec, recAlnLen(rec), tm, qm.len, l.x, l.y, i);
+            VQuery Q; queryView(Q, A, q, qm);
             // the plain-double sum decides unless it lies within its error bound of the threshold (or the scores are asked for)
             bool pass; float bnd = 0.f;
             int quick = -1;
@@ -759,7 +734,7 @@ __global__ __launch_bounds__(XR_NT, CDM_XRS_MINB) void k_xr_score(ExtArgs A, XrA
 __global__ __launch_bounds__(64, CDM_XRE_MINW) void k_xr_extend(ExtArgs A, XrArgs X) {
     A.raw = nullptr;
     __shared__ double sLogLik[11 * 16];
-    for (int i = threadIdx.x; i < 11 * 16; i += blockDim.x) sLogLik[i] = (&A.lut->logLik[0][0][0][0])[i];
+    loadLogLik(A, sLogLik);
     __syncthreads();
     const unsigned int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= *X.nWork) return;
@@ -769,9 +744,9 @@ __global__ __launch_bounds__(64, CDM_XRE_MINW) void k_xr_extend(ExtArgs A, XrArg
     const uint64_t r0 = A.aoff[q];
     const uint32_t nRec = (uint32_t) (A.aoff[q + 1] - r0);
     Cand *cand = A.cand + r0;
-    uint32_t *heapL = A.lists + 4 * r0, *parkL = heapL + nRec, *leftL = parkL + nRec, *rightL = leftL + nRec;
-    VQuery Q; xrQuery(Q, A, q, qm); Q.cand = cand; Q.leftL = leftL; Q.rightL = rightL;
-    Heap heap; heap.h = heapL; heap.n = 0; heap.cand = cand;
+    const QLists L = queryLists(A, r0, nRec);
+    VQuery Q; queryView(Q, A, q, qm, cand, &L);
+    Heap heap; heap.h = L.heap; heap.n = 0; heap.cand = cand;
     uint32_t nCand = 0;
     const uint32_t maxL0 = X.qMax[2 * (size_t) q], maxR0 = X.qMax[2 * (size_t) q + 1];
     for (uint64_t w = r0 >> 5; w <= (r0 + nRec - 1) >> 5; w++) {          // the records that enter the queue, in record order
@@ -783,7 +758,7 @@ __global__ __launch_bounds__(64, CDM_XRE_MINW) void k_xr_extend(ExtArgs A, XrArg
             bits &= bits - 1u;
             const uint64_t ri = (w << 5) + b;
             const AlnRec rec = A.rec[ri]; const float2 l = X.lite[ri];
-            Cand c; xrFill(c, rec, xrAlnLen(rec), meta[rec.target], qm.len, l.x, l.y, (uint32_t) (ri - r0));
+            Cand c; candFill(c, rec, recAlnLen(rec), meta[rec.target], qm.len, l.x, l.y, (uint32_t) (ri - r0));
             c.sLenNorm = X.sLen[ri];
             c.pieceLen = __float_as_uint(X.sBound[ri]);                  // (until the queue is built)
             cand[nCand++] = c;
@@ -806,7 +781,7 @@ __global__ __launch_bounds__(64, CDM_XRE_MINW) void k_xr_extend(ExtArgs A, XrArg
             if (cand[i].pieceLen & 0x80000000u) { Cand c = cand[i]; c.pieceLen = 0; (void) scoreCand(A, Q, c, maxL0, maxR0, sLogLik); cand[i].sLenNorm = c.sLenNorm; }
     }
     for (uint32_t k = 0; k < nCand; k++) { cand[k].pieceLen = 0; heap.push(k); }
-    extendLoop(A, Q, cand, heap, parkL, leftL, rightL, maxL0, maxR0, sLogLik, qm.key, q);
+    extendLoop(A, Q, cand, heap, L, maxL0, maxR0, sLogLik, qm.key, q);
 }
 
 __global__ void k_mark_active2(const uint64_t *__restrict__ aoff, uint32_t n, uint32_t *__restrict__ active, unsigned int *__restrict__ nActive,
@@ -852,9 +827,9 @@ __global__ __launch_bounds__(256) void k_write(ExtArgs A, const uint32_t *__rest
         const uint16_t *iN16 = reinterpret_cast<const uint16_t *>(A.nmask);
         for (uint32_t w = 0; w < nw; w++) { const uint32_t nb = iN16[ib + w]; oCodes[ob + w] = A.codes[ib + w]; oN16[ob + w] = (uint16_t) nb; anyN |= nb; }
     } else {
-        const uint64_t r0 = A.aoff[q]; const uint32_t nRec = (uint32_t) (A.aoff[q + 1] - r0);
-        VQuery Q; Q.a = &A; Q.q = q; Q.qLen0 = A.len[q]; Q.qw = A.woff[q]; Q.cand = A.cand + r0;
-        Q.leftL = A.lists + 4 * r0 + 2 * (uint64_t) nRec; Q.rightL = Q.leftL + nRec; Q.nL = A.nLeft[q]; Q.nR = A.nRight[q]; Q.leftTotal = A.leftTotal[q]; Q.total = L; Q.plain = false;
+        const uint64_t r0 = A.aoff[q];
+        const QLists Ls = queryLists(A, r0, (uint32_t) (A.aoff[q + 1] - r0));
+        VQuery Q; queryView(Q, A, q, A.len.m[q], A.cand + r0, &Ls, true);
         for (uint32_t w = 0; w < nw; w++) {
             const uint32_t cnt = min(16u, L - w * 16u);
             uint32_t code = 0, nb = 0;
@@ -888,12 +863,9 @@ __global__ __launch_bounds__(256) void k_write_raw(ExtArgs A, const uint32_t *__
     if (q >= n) return;
     const uint32_t L = oLen[q];
     uint8_t *o = oRaw + (uint64_t) oWoff[q] * 16u;
-    VQuery Q; Q.a = &A; Q.q = q; Q.qLen0 = A.len[q]; Q.qw = A.woff[q]; Q.nL = 0; Q.nR = 0; Q.leftTotal = 0; Q.total = L; Q.plain = false;
-    Q.cand = nullptr; Q.leftL = Q.rightL = nullptr;
-    if (A.newLen[q] != 0) {
-        const uint64_t r0 = A.aoff[q]; const uint32_t nRec = (uint32_t) (A.aoff[q + 1] - r0);
-        Q.cand = A.cand + r0; Q.leftL = A.lists + 4 * r0 + 2 * (uint64_t) nRec; Q.rightL = Q.leftL + nRec; Q.nL = A.nLeft[q]; Q.nR = A.nRight[q]; Q.leftTotal = A.leftTotal[q];
-    }
+    const uint64_t r0 = A.aoff[q];
+    const QLists Ls = queryLists(A, r0, (uint32_t) (A.aoff[q + 1] - r0));
+    VQuery Q; queryView(Q, A, q, A.len.m[q], A.cand + r0, &Ls, A.newLen[q] != 0);      // (not extended: no pieces, the lists are not looked at)
     bool any = false;
     for (uint32_t p = 0; p < L;) { uint32_t t, tp, run; Q.spanAt(p, t, tp, run); any = any || A.hasRaw[t]; p += run; }
     if (!any) return;
@@ -948,11 +920,7 @@ int cdm_extend_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
     A.maxSeqLen = par->max_seq_len;
     A.unsafe = par->unsafe ? 1 : 0; A.minCov = (uint32_t) std::max(0, par->min_cov_safe); A.flags = flags.p;
     hipEventRecord(ctx->ev0, s);
-    const char *padEnv = cdmGetenv("CDM_LDS_PAD");          // experiments: dynamic LDS that lowers the occupancy
-    const char *wEnv = cdmGetenv("CDM_EXTEND_WAVES");        // experiments: waves per SIMD the register allocation leaves room for
     const char *formEnv = cdmGetenv("CDM_EXTEND");           // "queries": k_extend (one lane per query) for every call
-    const int minW = wEnv ? atoi(wEnv) : 8;
-    const unsigned padB = padEnv ? (unsigned) atoi(padEnv) : 0u;
     // one thread per record for A-D (k_xr_*) where that form applies: the default mode, no raw plane
     bool perRecord = hAct && !db->raw && !A.unsafe && alns->count < 0xFFFFFFFFull / 2 && !(formEnv && !strcmp(formEnv, "queries"));
     DevBuf<uint32_t> winQ, qMax, work, elig, pushBits; DevBuf<float2> lite; DevBuf<double> sLen; DevBuf<float> sBound;
@@ -970,13 +938,11 @@ int cdm_extend_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
         hipMemcpyAsync(&fb, flags.p + 1, 4, hipMemcpyDeviceToHost, s);
         if (hipStreamSynchronize(s) != hipSuccess) { cdm_set_error("cdm_extend: scoring kernel failed"); return CDM_ERR_HIP; }
         if (fb) perRecord = false;          // a candidate that overlaps on both sides at once: the maxima depend on the record order
-        else hipLaunchKernelGGL(k_xr_extend, dim3((hAct + 63) / 64), dim3(64), padB, s, A, X);
+        else hipLaunchKernelGGL(k_xr_extend, dim3((hAct + 63) / 64), dim3(64), 0, s, A, X);
     }
     if (perRecord) {}
-    else if (hAct && db->raw) hipLaunchKernelGGL((k_extend<8, true>), dim3((hAct + 63) / 64), dim3(64), padB, s, A);
-    else if (hAct && minW == 8) hipLaunchKernelGGL(k_extend<8>, dim3((hAct + 63) / 64), dim3(64), padB, s, A);
-    else if (hAct && minW == 6) hipLaunchKernelGGL(k_extend<6>, dim3((hAct + 63) / 64), dim3(64), padB, s, A);
-    else if (hAct) hipLaunchKernelGGL(k_extend<5>, dim3((hAct + 63) / 64), dim3(64), padB, s, A);
+    else if (hAct && db->raw) hipLaunchKernelGGL((k_extend<8, true>), dim3((hAct + 63) / 64), dim3(64), 0, s, A);
+    else if (hAct) hipLaunchKernelGGL((k_extend<8, false>), dim3((hAct + 63) / 64), dim3(64), 0, s, A);
     hipEventRecord(ctx->ev1, s);
     // ---- output DB
     cdm_seqdb *o = nullptr;

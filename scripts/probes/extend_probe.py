@@ -1,4 +1,4 @@
-"""Extension kernel time on a synthetic read set, under the environment's CDM_EXTEND / CDM_XR_* switches: scripts/probes/extend_probe.py [reads]"""
+"""Extension kernel time on a synthetic read set, under the environment's CDM_EXTEND / CDM_EXTEND_MARGIN switches: scripts/probes/extend_probe.py [reads]"""
 import os
 import sys
 import tempfile
