@@ -80,6 +80,12 @@ class PileupParams(C.Structure):
     _fields_ = [("ends", C.c_int32), ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
 
 
+class DepthParams(C.Structure):
+    """cdm_depth_params: positions left out of the statistics window at either end of a contig, the records' identity threshold, reads
+    only as targets"""
+    _fields_ = [("edge", C.c_int32), ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -91,7 +97,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -206,6 +212,7 @@ def lib():
         l.cdm_seqdb_from_packed_ext.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
         l.cdm_seqdb_copy_ext.argtypes = [vp, vp, vp]
         l.cdm_pileup_profile.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(PileupParams), vp, vp, vp]
+        l.cdm_pileup_depth.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(DepthParams), vp, vp]
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -638,6 +645,26 @@ class Ctx:
         par = PileupParams(int(ends), float(min_seq_id), int(bool(skip_extended_targets)))
         _check(lib().cdm_pileup_profile(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(counts), _ptr(reads), _ptr(columns)))
         return counts, reads, columns
+
+    def pileup_depth(self, db, alns, queries, edge=0, min_seq_id=0.0, skip_extended_targets=False, track=False):
+        """depth statistics of the listed queries (cdm_pileup_depth) -> stats[nq, 8] uint64: reads, columns, breadth, window, covered,
+        sum, sumsq, max; with track also the depth at every position, a list of uint32 arrays, one per listed query"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 8), np.uint64)
+        lens, depth = None, None
+        if track:
+            if nq and int(q.max()) < db.n:         # (an index beyond the DB is the library's to refuse: nothing is written then)
+                lens = db.meta()[0][q].astype(np.int64)
+            else:
+                lens = np.zeros(nq, np.int64)
+            depth = np.zeros(max(int(lens.sum()), 1), np.uint32)
+        par = DepthParams(int(edge), float(min_seq_id), int(bool(skip_extended_targets)))
+        _check(lib().cdm_pileup_depth(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(depth)))
+        if not track:
+            return stats
+        ends = np.cumsum(lens)
+        return stats, [depth[int(e - l):int(e)].copy() for l, e in zip(lens, ends)]
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

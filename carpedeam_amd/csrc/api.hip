@@ -106,7 +106,7 @@ extern "C" void cdm_ctx_destroy(cdm_ctx *c) {
 }
 extern "C" int cdm_ctx_sync(cdm_ctx *c) { CDM_HIP(hipSetDevice(c->device)); CDM_HIP(hipStreamSynchronize(c->stream)); return CDM_OK; }
 extern "C" void *cdm_ctx_stream(cdm_ctx *c) { return (void *) c->stream; }
-extern "C" float cdm_ctx_last_kernel_ms(cdm_ctx *c, int which) { return (which >= 0 && which < 17) ? c->lastMs[which] : -1.f; }
+extern "C" float cdm_ctx_last_kernel_ms(cdm_ctx *c, int which) { return (which >= 0 && which < 18) ? c->lastMs[which] : -1.f; }
 
 extern "C" int cdm_damage_load(cdm_ctx *c, const char *prefix) {
     std::string err;

@@ -98,7 +98,7 @@ struct cdm_ctx {
     long double mats[2][11][4][4];
     DamageLut lutHost;
     DamageLut *lutDev = nullptr;
-    float lastMs[17] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // [16]: cdm_pileup_profile's kernel
+    float lastMs[18] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // [16]: cdm_pileup_profile's kernel, [17]: cdm_pileup_depth's kernels
     int cuCount = 256;
 };
 

@@ -34,6 +34,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "createdb", "createhdb", "convert2fasta", "ancient_reads_loop", "ancient_assemble_fused", "mergereads",
                                     /* coverage and damage tables of contigs from the read pile-up: not a module of the reference */
                                     "contig_damage",
+                                    /* per-contig depth, breadth and depth variance from the same pile-up: not a module of the reference either */
+                                    "contig_depth",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

@@ -1039,7 +1039,7 @@ const char *const LOOP_FLAGS[] = {"--k-ancient-reads", "--kmer-per-seq-ancient",
 // host (`cyclic`), or, for a caller that goes on with them on the device (keepResident), as the device DBs of the iterations that found
 // them (`cyclicDev`) together with the keys and lengths of the DB the loop started from (`source`: the createdb / mergereads result,
 // without its letters - cdm_seqdb_index_copy).
-// keepReads (ancient_assemble_fused --damage-report): the DB the loop started from stays resident WITH its letters (`reads`) instead of
+// keepReads (ancient_assemble_fused --damage-report / --depth-report): the DB the loop started from stays resident WITH its letters (`reads`) instead of
 // going with the first iteration.
 struct LoopEnd { cdm_ctx *ctx = NULL; cdm_seqdb *db = NULL, *source = NULL, *reads = NULL; bool keepReads = false; OutChunk cyclic; std::vector<cdm_seqdb *> cyclicDev; int dbtype = 1; };
 // The loop itself, shared by ancient_reads_loop and ancient_assemble_fused: input parsing or pair merging, the read and contig
@@ -1290,36 +1290,43 @@ bool loadDamageInput(cdm_ctx *ctx, const std::string &path, bool shuffle, bool w
     for (size_t i = 0; i < in.names.size(); i++) if (in.names[i].empty()) in.names[i] = std::to_string(in.keys[i]);
     return true;
 }
-// the four steps and the TSV; contigs == NULL: the header line alone.  Neither DB is freed here.
-void damageReport(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, long ends, int kmerSize, float minSeqId, const std::string &outPath, Laps &laps) {
+// The three library calls the pile-up reports share: the contigs (wasExtended 1) and the reads (0) as one DB, kmermatcher and
+// rescorediagonal on it with the reads loop's flags.  The caller frees both results.
+struct PileSet { cdm_seqdb *both = NULL; cdm_alns *alns = NULL; };
+PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId) {
+    PileSet p; cdm_hits *hits = NULL;
+    check(cdm_seqdb_concat(ctx, contigs, reads, 1, 0, &p.both), "contigs and reads as one DB");
+    cdm_kmer_params kp;         // the reads loop's kmermatcher flags (stageflags.K_FLAGS)
+    kp.kmer_size = kmerSize; kp.kmers_per_seq = 200; kp.kmers_per_seq_scale = 0.2f; kp.hash_shift = 67; kp.ignore_multi_kmer = 1; kp.include_only_extendable = 0; kp.cov_mode = 1; kp.cov_thr = 0.0f;
+    cdm_rescore_params rp;      // its rescorediagonal flags (R_FLAGS)
+    rp.seq_id_thr = minSeqId; rp.eval_thr = 0.001; rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
+    check(cdm_kmermatch(ctx, p.both, &kp, &hits), "kmermatcher");
+    check(cdm_rescore(ctx, p.both, hits, &rp, &p.alns), "rescorediagonal");
+    cdm_hits_free(hits);
+    return p;
+}
+void freePileSet(PileSet &p) { if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
+bool haveContigs(const DamageInput *contigs) { return contigs && contigs->db && cdm_seqdb_size(contigs->db); }
+const std::string &contigName(const DamageInput &c, uint64_t i, std::string &tmp) { if (i < c.names.size()) return c.names[i]; tmp = std::to_string(c.keys[i]); return tmp; }
+// the damage TSV from the alignments of a PileSet; no contigs: the header line alone
+void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, long ends, const std::string &outPath, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns";
     for (long d = 1; d <= ends; d++) { const std::string n = std::to_string(d); text += "\t5p_C_" + n + "\t5p_CT_" + n + "\t3p_G_" + n + "\t3p_GA_" + n; }
     text += "\n";
-    if (contigs && contigs->db && cdm_seqdb_size(contigs->db)) {
+    if (haveContigs(contigs)) {
         const uint64_t nc = cdm_seqdb_size(contigs->db);
-        cdm_seqdb *both = NULL; cdm_hits *hits = NULL; cdm_alns *alns = NULL;
-        check(cdm_seqdb_concat(ctx, contigs->db, reads, 1, 0, &both), "contigs and reads as one DB");
-        cdm_kmer_params kp;         // the reads loop's kmermatcher flags (stageflags.K_FLAGS)
-        kp.kmer_size = kmerSize; kp.kmers_per_seq = 200; kp.kmers_per_seq_scale = 0.2f; kp.hash_shift = 67; kp.ignore_multi_kmer = 1; kp.include_only_extendable = 0; kp.cov_mode = 1; kp.cov_thr = 0.0f;
-        cdm_rescore_params rp;      // its rescorediagonal flags (R_FLAGS)
-        rp.seq_id_thr = minSeqId; rp.eval_thr = 0.001; rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
-        check(cdm_kmermatch(ctx, both, &kp, &hits), "kmermatcher");
-        check(cdm_rescore(ctx, both, hits, &rp, &alns), "rescorediagonal");
-        cdm_hits_free(hits);
-        laps.lap("damage report: kmermatcher, rescorediagonal");
         std::vector<uint32_t> q(nc), lens(nc);
         std::iota(q.begin(), q.end(), 0u);
         const size_t cells = (size_t) 2 * (size_t) ends * 16;
         std::vector<uint64_t> counts(nc * cells), nReads(nc), nCols(nc);
         cdm_pileup_params pp; pp.ends = (int32_t) ends; pp.min_seq_id = 0.0f; pp.skip_extended_targets = 1;
-        check(cdm_pileup_profile(ctx, both, alns, q.data(), nc, &pp, counts.data(), nReads.data(), nCols.data()), "pile-up profile");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  damage report: %llu records, pile-up kernel %.3f ms\n", (unsigned long long) cdm_alns_count(alns), cdm_ctx_last_kernel_ms(ctx, 16));
+        check(cdm_pileup_profile(ctx, ps.both, ps.alns, q.data(), nc, &pp, counts.data(), nReads.data(), nCols.data()), "pile-up profile");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  damage report: %llu records, pile-up kernel %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 16));
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        cdm_alns_free(alns); cdm_seqdb_free(both);
-        char num[32];
+        char num[32]; std::string tmp;
         auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
         for (uint64_t i = 0; i < nc; i++) {
-            text += i < contigs->names.size() ? contigs->names[i] : std::to_string(contigs->keys[i]);
+            text += contigName(*contigs, i, tmp);
             put(contigs->keys[i]); put(lens[i]); put(nReads[i]); put(nCols[i]);
             const uint64_t *c5 = counts.data() + i * cells, *c3 = c5 + (size_t) ends * 16;
             for (long d = 0; d < ends; d++) {       // [d][x][y], A,C,G,T = 0..3: C under any read base / under T; G under any / under A
@@ -1332,6 +1339,87 @@ void damageReport(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, lo
     }
     if (!writeText(outPath, text)) die("Could not write " + outPath);
 }
+// ---- contig_depth: per-contig depth, breadth and depth variance from the same pile-up (not a module of the reference).  Per read set
+// the three calls above, then cdm_pileup_depth over the contigs: as with the damage tables, coverage by seeded UNGAPPED overlaps at the
+// identity threshold, not a gapped mapping.  One TSV line per contig, integers only: the caller divides (mean = sum / window,
+// variance = (sumsq - sum^2 / window) / (window - 1)).
+const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+long depthEdge(Args &a, const char *module) {
+    const long e = iflag(a, "--depth-edge", 0);
+    if (e < 0 || e > 1048576) unsupported(std::string(module) + ": --depth-edge " + a.flag["--depth-edge"] + " is not supported by the MI355X path (0 to 1048576 positions are left out at either end of a contig)");
+    return e;
+}
+// one read set's statistics (nc x 8) and, when asked for, the depth of every contig position back to back
+void depthSample(cdm_ctx *ctx, const DamageInput &contigs, const PileSet &ps, long edge, std::vector<uint64_t> &stats, std::vector<uint32_t> *track) {
+    const uint64_t nc = cdm_seqdb_size(contigs.db);
+    std::vector<uint32_t> q(nc);
+    std::iota(q.begin(), q.end(), 0u);
+    stats.assign(nc * 8, 0);
+    if (track) track->assign(cdm_seqdb_residues(contigs.db) + 1, 0);
+    cdm_depth_params dp; dp.edge = (int32_t) edge; dp.min_seq_id = 0.0f; dp.skip_extended_targets = 1;
+    check(cdm_pileup_depth(ctx, ps.both, ps.alns, q.data(), nc, &dp, stats.data(), track ? track->data() : NULL), "pile-up depth");
+    if (getenv("CDM_TIMING")) fprintf(stderr, "  depth report: %llu records, depth kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 17));
+}
+// the depth TSV of `samples` read sets; no contigs: the header line alone
+void depthTable(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<std::vector<uint64_t>> &stats, size_t samples, const std::string &outPath) {
+    std::string text = "name\tkey\tlength\twindow";
+    static const char *const COLS[7] = {"reads", "columns", "breadth", "covered", "sum", "sumsq", "max"};
+    static const int AT[7] = {0, 1, 2, 4, 5, 6, 7};
+    for (size_t s = 1; s <= samples; s++) for (const char *c : COLS) text += std::string("\t") + c + "_" + std::to_string(s);
+    text += "\n";
+    if (haveContigs(contigs)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        std::vector<uint32_t> lens(nc);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        char num[32]; std::string tmp;
+        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        for (uint64_t i = 0; i < nc; i++) {
+            text += contigName(*contigs, i, tmp);
+            put(contigs->keys[i]); put(lens[i]); put(stats[0][i * 8 + 3]);
+            for (size_t s = 0; s < samples; s++) for (int c : AT) put(stats[s][i * 8 + c]);
+            text.push_back('\n');
+        }
+    }
+    if (!writeText(outPath, text)) die("Could not write " + outPath);
+}
+// bedGraph of the runs of equal depth, zero runs included: name, start, end (0-based, half-open), depth
+void depthTrackFile(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<uint32_t> &track, const std::string &outPath) {
+    std::string text;
+    if (haveContigs(contigs)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        std::vector<uint32_t> lens(nc);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        char num[32]; std::string tmp;
+        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        uint64_t at = 0;
+        for (uint64_t i = 0; i < nc; at += lens[i], i++) {
+            const std::string &name = contigName(*contigs, i, tmp);
+            const uint32_t *d = track.data() + at;
+            for (uint32_t start = 0, p = 1; p <= lens[i]; p++)
+                if (p == lens[i] || d[p] != d[start]) { text += name; put(start); put(p); put(d[start]); text.push_back('\n'); start = p; }
+        }
+    }
+    if (!writeText(outPath, text)) die("Could not write " + outPath);
+}
+// Both reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
+// alignment set.  damageOut / depthOut: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
+void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const std::string *damageOut, long ends, const std::string *depthOut, long edge,
+                 const std::string *trackOut, Laps &laps) {
+    PileSet ps;
+    if (haveContigs(contigs)) {
+        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
+        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : "depth report: kmermatcher, rescorediagonal");
+    }
+    if (damageOut) damageTable(ctx, contigs, ps, ends, *damageOut, laps);
+    if (depthOut) {
+        std::vector<std::vector<uint64_t>> stats(1); std::vector<uint32_t> track;
+        if (haveContigs(contigs)) depthSample(ctx, *contigs, ps, edge, stats[0], trackOut ? &track : NULL);
+        depthTable(ctx, contigs, stats, 1, *depthOut);
+        if (trackOut) depthTrackFile(ctx, contigs, track, *trackOut);
+        laps.lap("depth report: depth, table");
+    }
+    freePileSet(ps);
+}
 int contigDamage(Args &a) {
     if (a.pos.size() < 3) die("Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]");
     checkFlags("contig_damage", a, DAMAGE_FLAGS);
@@ -1339,12 +1427,42 @@ int contigDamage(Args &a) {
     Laps laps;
     cdm_ctx *ctx = openCtx();
     DamageInput contigs, reads;
-    const bool haveContigs = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (haveContigs && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
+    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
+    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
     laps.lap("inputs read, sequences up");
-    damageReport(ctx, haveContigs ? &contigs : NULL, reads.db, ends, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), a.pos[2], laps);
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
     if (reads.db) cdm_seqdb_free(reads.db);
+    cdm_ctx_destroy(ctx);
+    return EXIT_SUCCESS;
+}
+int contigDepth(Args &a) {
+    if (a.pos.size() < 3) die("Usage: carpedeam contig_depth <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> [<i:reads> ...] <o:tsvFile> [--depth-edge 0] [--min-seq-id 0.9] [-k 20] [--depth-track <bedGraph>]");
+    checkFlags("contig_depth", a, DEPTH_FLAGS);
+    const long edge = depthEdge(a, "contig_depth");
+    const size_t samples = a.pos.size() - 2;
+    const bool wantTrack = a.flag.count("--depth-track") != 0;
+    if (wantTrack && samples > 1) unsupported("contig_depth: --depth-track with " + std::to_string(samples) + " read sets is not supported by the MI355X path (the track is written for one read set)");
+    const int k = (int) iflag(a, "-k", 20); const float minSeqId = fflag(a, "--min-seq-id", 0.9f);
+    Laps laps;
+    cdm_ctx *ctx = openCtx();
+    DamageInput contigs;
+    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
+    laps.lap("contigs read, sequences up");
+    std::vector<std::vector<uint64_t>> stats(samples); std::vector<uint32_t> track;
+    for (size_t s = 0; have && s < samples; s++) {      // each read set is freed before the next
+        DamageInput reads;
+        if (!loadDamageInput(ctx, a.pos[1 + s], true, false, reads)) die("contig_depth: " + a.pos[1 + s] + " holds no reads");
+        PileSet ps = pileupAlignments(ctx, contigs.db, reads.db, k, minSeqId);
+        laps.lap("depth report: reads up, kmermatcher, rescorediagonal");
+        depthSample(ctx, contigs, ps, edge, stats[s], wantTrack ? &track : NULL);
+        freePileSet(ps); cdm_seqdb_free(reads.db);
+        laps.lap("depth report: depth");
+    }
+    depthTable(ctx, have ? &contigs : NULL, stats, samples, a.pos.back());
+    if (wantTrack) depthTrackFile(ctx, have ? &contigs : NULL, track, a.flag["--depth-track"]);
+    laps.lap("depth report: table");
+    if (contigs.db) cdm_seqdb_free(contigs.db);
     cdm_ctx_destroy(ctx);
     return EXIT_SUCCESS;
 }
@@ -1548,7 +1666,7 @@ const FlagSpec FUSED_FLAGS[] = {
     {"--include-only-extendable-ancient-reads", 'U', 0, 0}, {"-e", 'U', 0, 0}, {"--num-iter-reads-only", 'U', 0, 0}, {"--shuffle", 'U', 0, 0}, {"--num-iterations", 'U', 0, 0},
     {"--k-ancient-contigs", 'U', 0, 0}, {"--include-only-extendable-ancient-contigs", 'U', 0, 0}, {"--cycle-check", 'U', 0, 0}, {"--chop-cycle", 'U', 0, 0}, {"--gpus", 'U', 0, 0},
     // the tail's
-    {"--damage-report", 'U', 0, 0}, {"--damage-ends", 'U', 0, 0},
+    {"--damage-report", 'U', 0, 0}, {"--damage-ends", 'U', 0, 0}, {"--depth-report", 'U', 0, 0}, {"--depth-edge", 'U', 0, 0},
     {"--min-contig-len", 'U', 0, 0}, {"--clust-min-seq-id", 'U', 0, 0}, {"--clust-min-cov", 'U', 0, 0}, {"--zdrop", 'U', 0, 0}, {"--threads", 'U', 0, 0}, {"--remove-tmp-files", 'U', 0, 0},
     {"-v", 'U', 0, 0},
     {"--cluster-mode", 'V', "2", "the redundancy reduction clusters greedily, linclust's mode for --cov-mode 1"}, {"--cov-mode", 'V', "1", "the workflow's coverage mode throughout"},
@@ -1656,6 +1774,12 @@ int assembleFused(Args &a) {
     const bool report = a.flag.count("--damage-report") != 0;
     const std::string reportFile = report ? a.flag["--damage-report"] : "";
     const long reportEnds = damageEnds(a, "ancient_assemble_fused");
+    // --depth-report <file>: likewise contig_depth's table of the final representatives against those reads; with both flags the two
+    // reductions read one alignment set
+    const bool depthRep = a.flag.count("--depth-report") != 0;
+    const std::string depthFile = depthRep ? a.flag["--depth-report"] : "";
+    const long reportEdge = depthEdge(a, "ancient_assemble_fused");
+    const bool anyReport = report || depthRep;
     // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
     if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
     if (const char *dry = getenv("CDM_FUSED_DRY_RUN")) {        // "cycle": the tail as it runs with circular contigs among the selection
@@ -1674,7 +1798,7 @@ int assembleFused(Args &a) {
     if (mkdir((T + "/clu_tmp").c_str(), 0777) != 0) die("Can not create " + T + "/clu_tmp");
     Laps laps;
     LoopEnd E;
-    E.keepReads = report;
+    E.keepReads = anyReport;
     runLoop("ancient_assemble_fused", a, inputs, false, 10, true, E, laps);       // the workflow's defaults: --num-iterations 10 (GuidedNuclassembler.cpp:12), --num-iter-reads-only 5
     cdm_ctx *ctx = E.ctx;
     // ---- "select only assembled sequences" / "... fullfilling a minimum length threshold" (nuclassemble.sh:214-224) on the final DB
@@ -1683,9 +1807,9 @@ int assembleFused(Args &a) {
     const uint32_t minLen = (uint32_t) std::min<long>(std::max<long>(iflag(a, "--min-contig-len", 500), 0), 0xFFFFFFFEl);       // LocalParameters.h:288
     cdm_seqdb *selected = NULL; uint64_t kept = 0;
     check(cdm_seqdb_select_assembled(ctx, E.db, E.source, minLen, &selected, &kept), "selection of the assembled contigs");
-    if (report && !E.reads) E.reads = E.db;        // (a loop of no iteration: its DB is the reads)
+    if (anyReport && !E.reads) E.reads = E.db;        // (a loop of no iteration: its DB is the reads)
     else cdm_seqdb_free(E.db);
-    cdm_ctx *const reportCtx = report ? ctx : NULL;
+    cdm_ctx *const reportCtx = anyReport ? ctx : NULL;
     OutChunk linear, circular, both;
     appendEntries(ctx, selected, linear);
     for (cdm_seqdb *c : E.cyclicDev) {
@@ -1702,7 +1826,7 @@ int assembleFused(Args &a) {
         // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
         cdm_seqdb_free(selected);
         if (!writeText(outFile, "")) die("Could not write " + outFile);
-        if (report) { damageReport(ctx, NULL, NULL, reportEnds, 20, 0.9f, reportFile, laps); cdm_seqdb_free(E.reads); }
+        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, laps); cdm_seqdb_free(E.reads); }
         cdm_ctx_destroy(ctx);
         if (removeTmp) removeOwnDir(T);
         return EXIT_SUCCESS;
@@ -1757,7 +1881,7 @@ int assembleFused(Args &a) {
             formatRescoredPrefDb(asmDb, pref, koff.data(), krec.data(), chunks);
             if (!mmdbWriteChunks(s.pos[3], pref.dbtype, chunks, &err, true)) die(err);
             // the device's part is done: everything after this works on cluster lists and the contig DB's files
-            cdm_hits_free(keptHits); cdm_hits_free(hits); hits = NULL; cdm_seqdb_free(db); db = NULL; if (!report) cdm_ctx_destroy(ctx);      // (the report's reads stay, with the context)
+            cdm_hits_free(keptHits); cdm_hits_free(hits); hits = NULL; cdm_seqdb_free(db); db = NULL; if (!anyReport) cdm_ctx_destroy(ctx);      // (the reports' reads stay, with the context)
             ctx = NULL;
             laps.lap("linclust: kmermatcher, Hamming rescore");
         } else if (s.module == "createhdb") {
@@ -1790,10 +1914,10 @@ int assembleFused(Args &a) {
         if (fclose(out) != 0 || !ok) die("Could not move result to " + outFile);
         unlink((REP + ".fasta").c_str());
     }
-    if (report) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
+    if (anyReport) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
         DamageInput contigs;
         const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
-        damageReport(reportCtx, have ? &contigs : NULL, E.reads, reportEnds, 20, 0.9f, reportFile, laps);
+        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, laps);
         if (contigs.db) cdm_seqdb_free(contigs.db);
         cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);
     }
@@ -1823,7 +1947,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -1842,6 +1966,7 @@ int main(int argc, char **argv) {
     else if (cmd == "ancient_reads_loop") rc = readsLoop(a);
     else if (cmd == "ancient_assemble_fused") rc = assembleFused(a);
     else if (cmd == "contig_damage") rc = contigDamage(a);
+    else if (cmd == "contig_depth") rc = contigDepth(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

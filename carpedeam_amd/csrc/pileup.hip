@@ -1,4 +1,5 @@
-// Per-query coverage and damage tables of the read pile-up (cdm_pileup_profile; not a module of the reference).
+// Per-query coverage and damage tables of the read pile-up (cdm_pileup_profile) and the depth at every position of a query with its
+// statistics (cdm_pileup_depth, in the second half of this file); neither is a module of the reference.
 //
 // ancient_correction orients every record of a query and piles the targets up column by column (correct.hip: orient(), targetBase());
 // this unit walks the same columns and COUNTS: for the first and the last `ends` positions of every read, which query base stands
@@ -58,6 +59,22 @@ __device__ __forceinline__ Oriented orient(const AlnRec &r, uint32_t dbLen) {
     return o;
 }
 
+// The records that count on query q of qLen letters (the rule of cdm_pileup_profile and cdm_pileup_depth, include/carpedeam_hip.h):
+// true with the oriented record, its target's length and word offset.
+__device__ __forceinline__ bool countedRecord(const SeqMeta *__restrict__ meta, uint32_t n, uint32_t skipExt, float minSeqId, uint32_t q, uint32_t qLen, const AlnRec &rec,
+                                              Oriented &o, uint32_t &tLen, uint32_t &tw) {
+    const uint32_t t = rec.target;
+    if (t == q || t >= n) return false;               // the identity record is not a read on the query
+    if (!(rec.seqId >= minSeqId)) return false;
+    const SeqMeta tm = meta[t];
+    if (skipExt && (tm.flags & 2u)) return false;
+    tLen = tm.len; tw = tm.woff;
+    o = orient(rec, tLen);
+    // (every record of a set went through cdm_alns_upload's checks or came from cdm_rescore; a record that does not fit its two
+    // sequences all the same is left out here, not followed out of bounds)
+    return !(o.qs < 0 || o.ds < 0 || o.qe < o.qs || (uint32_t) o.qe >= qLen || (uint32_t) o.de >= tLen || o.qe - o.qs != o.de - o.ds);
+}
+
 __device__ __forceinline__ void waveLdsSync() {     // LDS traffic of this wave's lanes in front of the call is visible to all of them behind it
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
@@ -83,16 +100,8 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_pileup(PileupArgs a, uint64_t
     unsigned int nReads = 0; unsigned long long nCols = 0;
     for (uint64_t r = r0 + lane; r < r1; r += 64) {
         const AlnRec rec = a.rec[r];
-        const uint32_t t = rec.target;
-        if (t == q || t >= a.n) continue;             // the identity record is not a read on the query
-        if (!(rec.seqId >= a.minSeqId)) continue;
-        const SeqMeta tm = a.meta[t];
-        if (a.skipExt && (tm.flags & 2u)) continue;
-        const uint32_t tLen = tm.len, tw = tm.woff;
-        const Oriented o = orient(rec, tLen);
-        // (every record of a set went through cdm_alns_upload's checks or came from cdm_rescore; a record that does not fit its two
-        // sequences all the same is left out here, not followed out of bounds)
-        if (o.qs < 0 || o.ds < 0 || o.qe < o.qs || (uint32_t) o.qe >= qLen || (uint32_t) o.de >= tLen || o.qe - o.qs != o.de - o.ds) continue;
+        Oriented o; uint32_t tLen, tw;
+        if (!countedRecord(a.meta, a.n, a.skipExt, a.minSeqId, q, qLen, rec, o, tLen, tw)) continue;
         const uint32_t L = (uint32_t) (o.qe - o.qs) + 1u;
         nReads++; nCols += L;
         // the overlap on the read as stored: positions [pLo, pHi]
@@ -121,6 +130,116 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_pileup(PileupArgs a, uint64_t
     const unsigned int rd = (unsigned int) cdm_wave_sum((int) nReads);      // (at most 2^20 records per item)
     const unsigned long long cl = cdm_wave_incl_sum<unsigned long long>(nCols);
     if (lane == 63 && rd) { atomicAdd(&a.reads[qi], (unsigned long long) rd); atomicAdd(&a.columns[qi], cl); }
+}
+
+// ---------------------------------------------------------------------------------------------- cdm_pileup_depth
+// Depth at every position of the listed queries, and its statistics (include/carpedeam_hip.h).  k_pileup touches at most 2 x ends
+// columns of a record; depth touches all of them, so the records are not walked column by column: a counted record MARKS its two ends
+// in a 32-bit cell array (+1 at qs, -1 behind qe; len + 1 cells per listed query, the last one its closing cell), every query's cells
+// sum to zero, and ONE device-wide prefix sum over the batch's cells turns the marks into depths - no segmented scan.  A third kernel
+// walks the positions in tiles and reduces the statistics.  The cells live modulo 2^32: a depth is below the query's record count,
+// and a query with 2^32 records or more is refused.
+constexpr int DP_NT = 256, DP_PER = 8, DP_TILE = DP_NT * DP_PER;       // positions per statistics item
+constexpr uint64_t DP_CELLS_DEFAULT = 1ull << 28, DP_CELLS_MAX = 1ull << 32;
+
+uint64_t depthCells() {     // CDM_DEPTH_CELLS=<cells> (tests): small inputs in several batches
+    if (const char *e = cdmGetenv("CDM_DEPTH_CELLS")) { const long long v = atoll(e); if (v > 0) return std::min<uint64_t>((uint64_t) v, DP_CELLS_MAX); }
+    return DP_CELLS_DEFAULT;
+}
+
+struct DepthArgs {
+    const SeqMeta *meta; const uint64_t *aoff; const AlnRec *rec;
+    const uint32_t *queries;        // [nq] the listed queries of this call's batch
+    const uint64_t *itemOff;        // [nq + 1] first marking item (chunk of records) of each listed query
+    const uint64_t *tileOff;        // [nq + 1] first statistics item (tile of positions) of each
+    const uint64_t *base;           // [nq + 1] first cell of each
+    uint32_t n, nq, chunk, skipExt, edge; float minSeqId;
+    uint32_t *cells;                // [base[nq]]
+    unsigned long long *stats;      // [nq][8]
+    uint32_t *track;                // NULL, or [base[nq] - nq]: the depths without the closing cells
+};
+
+// length and record count of every listed query
+__global__ void k_depth_sizes(const SeqMeta *__restrict__ meta, const uint64_t *__restrict__ aoff, const uint32_t *__restrict__ queries, uint64_t nq, uint32_t *__restrict__ len,
+                              uint64_t *__restrict__ recs) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const uint32_t q = queries[i];
+    len[i] = meta[q].len; recs[i] = aoff[q + 1] - aoff[q];
+}
+
+__device__ __forceinline__ unsigned long long waveSum64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v += ((unsigned long long) (unsigned int) __shfl_xor((int) (v >> 32), o, 64) << 32) | (unsigned int) __shfl_xor((int) (unsigned int) v, o, 64);
+    return v;
+}
+
+// marks: one wave per item (listed query, chunk of its records) of this launch's slice, lanes take records
+__global__ __launch_bounds__(64 * PU_WAVES) void k_depth_marks(DepthArgs a, uint64_t first, uint64_t nThis) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
+    if (local >= nThis) return;
+    const uint64_t item = first + local;
+    uint32_t lo = 0, hi = a.nq;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.itemOff[mid] <= item) lo = mid; else hi = mid; }
+    const uint32_t qi = lo, q = a.queries[qi];
+    const uint64_t r0 = a.aoff[q] + (item - a.itemOff[qi]) * a.chunk, r1 = min((uint64_t) a.aoff[q + 1], r0 + a.chunk);
+    const uint32_t qLen = a.meta[q].len;
+    uint32_t *cell = a.cells + a.base[qi];
+    unsigned int nReads = 0; unsigned long long nCols = 0;
+    for (uint64_t r = r0 + lane; r < r1; r += 64) {
+        const AlnRec rec = a.rec[r];
+        Oriented o; uint32_t tLen, tw;
+        if (!countedRecord(a.meta, a.n, a.skipExt, a.minSeqId, q, qLen, rec, o, tLen, tw)) continue;
+        nReads++; nCols += (uint32_t) (o.qe - o.qs) + 1u;
+        atomicAdd(&cell[(uint32_t) o.qs], 1u);                        // (results unused: atomics without return)
+        atomicAdd(&cell[(uint32_t) o.qe + 1u], 0xFFFFFFFFu);          // qe < qLen: at the most the query's closing cell
+    }
+    const unsigned int rd = (unsigned int) cdm_wave_sum((int) nReads);
+    const unsigned long long cl = waveSum64(nCols);
+    if (lane == 0 && rd) { atomicAdd(&a.stats[(uint64_t) qi * 8], (unsigned long long) rd); atomicAdd(&a.stats[(uint64_t) qi * 8 + 1], cl); }
+}
+
+// statistics: one block per item (listed query, tile of DP_TILE positions) of this launch's slice, on the scanned cells:
+// depth[p] = the exclusive prefix at cell p + 1
+__global__ __launch_bounds__(DP_NT) void k_depth_stats(DepthArgs a, uint64_t first) {
+    __shared__ unsigned long long sRed[DP_NT / 64][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t item = first + blockIdx.x;
+    uint32_t lo = 0, hi = a.nq;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.tileOff[mid] <= item) lo = mid; else hi = mid; }
+    const uint32_t qi = lo, len = a.meta[a.queries[qi]].len;
+    const uint64_t cb = a.base[qi], p0 = (item - a.tileOff[qi]) * DP_TILE;
+    // the statistics window: the whole query when len <= 2 x edge, else [edge, len - 1 - edge]
+    uint32_t w0 = 0, w1 = len - 1u;
+    if ((uint64_t) len > 2ull * a.edge) { w0 = a.edge; w1 = len - 1u - a.edge; }
+    const uint32_t *__restrict__ cell = a.cells + cb + 1;
+    uint32_t *__restrict__ out = a.track ? a.track + (cb - qi) : nullptr;
+    unsigned long long sum = 0, sumsq = 0; uint32_t breadth = 0, covered = 0, mx = 0;
+#pragma unroll
+    for (int j = 0; j < DP_PER; j++) {
+        const uint64_t p = p0 + threadIdx.x + (uint64_t) DP_NT * j;
+        if (p >= len) continue;
+        const uint32_t d = cell[p];
+        if (out) out[p] = d;
+        breadth += d != 0;
+        if (p >= w0 && p <= w1) { covered += d != 0; sum += d; sumsq += (unsigned long long) d * d; mx = max(mx, d); }
+    }
+    sum = waveSum64(sum); sumsq = waveSum64(sumsq);
+    const unsigned long long bc = waveSum64(((unsigned long long) breadth << 32) | covered);       // (at most DP_TILE each)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t) __shfl_xor((int) mx, o, 64));
+    if (lane == 0) { sRed[wave][0] = sum; sRed[wave][1] = sumsq; sRed[wave][2] = bc; sRed[wave][3] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t[3] = {0, 0, 0}, m = 0;
+        for (int w = 0; w < DP_NT / 64; w++) { t[0] += sRed[w][0]; t[1] += sRed[w][1]; t[2] += sRed[w][2]; m = max(m, sRed[w][3]); }
+        unsigned long long *row = a.stats + (uint64_t) qi * 8;
+        if (t[2] >> 32) atomicAdd(&row[2], t[2] >> 32);
+        if (t[2] & 0xFFFFFFFFull) atomicAdd(&row[4], t[2] & 0xFFFFFFFFull);
+        if (t[0]) { atomicAdd(&row[5], t[0]); atomicAdd(&row[6], t[1]); atomicMax(&row[7], m); }
+    }
 }
 
 }  // namespace
@@ -175,20 +294,111 @@ int cdm_pileup_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
     return CDM_OK;
 }
 
+static int cdm_depth_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_depth_params *par, uint64_t *stats, uint32_t *depth) {
+    hipStream_t s = ctx->stream;
+    const uint32_t chunk = pileupChunk(), edge = (uint32_t) par->edge;
+    const uint64_t bound = depthCells();
+    DevBuf<SeqMeta> meta;
+    if (int rc = cdm_build_meta(ctx, db, &meta.p)) return rc;
+    DevBuf<uint32_t> dq, dLen; DevBuf<uint64_t> dRecs;
+    if (!dq.alloc(nq) || !dLen.alloc(nq) || !dRecs.alloc(nq)) { cdm_set_error("cdm_pileup_depth: out of device memory for %llu queries", (unsigned long long) nq); return CDM_ERR_HIP; }
+    std::vector<uint32_t> len(nq); std::vector<uint64_t> recs(nq);
+    CDM_HIP(hipMemcpyAsync(dq.p, queries, (size_t) nq * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_depth_sizes, CDM_GRID((nq + 255) / 256, 256), dim3(256), 0, s, (const SeqMeta *) meta.p, (const uint64_t *) alns->off, (const uint32_t *) dq.p, nq, dLen.p, dRecs.p);
+    CDM_LAUNCH_CHECK();
+    CDM_HIP(hipMemcpyAsync(len.data(), dLen.p, (size_t) nq * 4, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipMemcpyAsync(recs.data(), dRecs.p, (size_t) nq * 8, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < nq; i++)
+        if (recs[i] >> 32) { cdm_set_error("cdm_pileup_depth: query %u has %llu records; the 32-bit depth cells hold fewer than 2^32", queries[i], (unsigned long long) recs[i]); return CDM_ERR_UNSUPPORTED; }
+    float msTotal = 0.f;
+    uint64_t trackAt = 0;
+    for (uint64_t b0 = 0; b0 < nq;) {
+        // the batch: listed queries while their cells stay within the bound; a single query longer than the bound goes alone
+        uint32_t m = 0; uint64_t nCells = 0;
+        while (b0 + m < nq && m < (1u << 30) && (m == 0 || nCells + len[b0 + m] + 1ull <= bound)) { nCells += len[b0 + m] + 1ull; m++; }
+        std::vector<uint64_t> base((size_t) m + 1), tileOff((size_t) m + 1);
+        base[0] = tileOff[0] = 0;
+        for (uint32_t i = 0; i < m; i++) { base[i + 1] = base[i] + len[b0 + i] + 1ull; tileOff[i + 1] = tileOff[i] + ((uint64_t) len[b0 + i] + DP_TILE - 1) / DP_TILE; }
+        const uint64_t nTiles = tileOff[m], nTrack = nCells - m;
+        DevBuf<uint64_t> items, itemOff, dBase, dTile; DevBuf<uint32_t> cells, track; DevBuf<unsigned long long> dStats;
+        if (!items.alloc((size_t) m + 1) || !itemOff.alloc((size_t) m + 1) || !dBase.alloc((size_t) m + 1) || !dTile.alloc((size_t) m + 1) || !cells.alloc(nCells) || !dStats.alloc((size_t) m * 8) ||
+            (depth && !track.alloc(nTrack))) {
+            cdm_set_error("cdm_pileup_depth: out of device memory for the %llu cells of %u queries", (unsigned long long) nCells, m); return CDM_ERR_HIP;
+        }
+        CDM_HIP(hipMemcpyAsync(dBase.p, base.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemcpyAsync(dTile.p, tileOff.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemsetAsync(cells.p, 0, (size_t) nCells * 4, s));
+        CDM_HIP(hipMemsetAsync(dStats.p, 0, (size_t) m * 64, s));
+        hipLaunchKernelGGL(k_pileup_chunks, dim3((m + 256) / 256), dim3(256), 0, s, (const uint64_t *) alns->off, (const uint32_t *) (dq.p + b0), m, chunk, items.p);
+        cdmscan::ScanTemp st, stCells;
+        if (int rc = cdmscan::exclusiveScan<uint64_t>(s, st, items.p, itemOff.p, (size_t) m + 1)) return rc;
+        uint64_t nItems = 0;
+        CDM_HIP(hipMemcpyAsync(&nItems, itemOff.p + m, 8, hipMemcpyDeviceToHost, s));
+        CDM_HIP(hipStreamSynchronize(s));
+        DepthArgs a;
+        a.meta = meta.p; a.aoff = alns->off; a.rec = alns->rec; a.queries = dq.p + b0; a.itemOff = itemOff.p; a.tileOff = dTile.p; a.base = dBase.p;
+        a.n = (uint32_t) db->n; a.nq = m; a.chunk = chunk; a.skipExt = par->skip_extended_targets ? 1u : 0u; a.edge = edge; a.minSeqId = par->min_seq_id;
+        a.cells = cells.p; a.stats = dStats.p; a.track = depth ? track.p : nullptr;
+        hipEventRecord(ctx->ev0, s);
+        for (uint64_t first = 0, slice = cdmSliceItems(64); first < nItems; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nItems - first);
+            hipLaunchKernelGGL(k_depth_marks, CDM_GRID((nThis + PU_WAVES - 1) / PU_WAVES, 64 * PU_WAVES), dim3(64 * PU_WAVES), 0, s, a, first, nThis);
+        }
+        if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stCells, cells.p, cells.p, (size_t) nCells)) return rc;     // (in place: scan.h)
+        for (uint64_t first = 0, slice = cdmSliceItems(DP_NT); first < nTiles; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nTiles - first);
+            hipLaunchKernelGGL(k_depth_stats, CDM_GRID(nThis, DP_NT), dim3(DP_NT), 0, s, a, first);
+        }
+        hipEventRecord(ctx->ev1, s);
+        CDM_LAUNCH_CHECK();
+        CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
+        if (depth && nTrack) CDM_HIP(hipMemcpyAsync(depth + trackAt, track.p, (size_t) nTrack * 4, hipMemcpyDeviceToHost, s));
+        { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_pileup_depth: the kernels failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) msTotal += ms;
+        for (uint32_t i = 0; i < m; i++) {
+            uint64_t *row = stats + (b0 + i) * 8;
+            const uint64_t L = len[b0 + i];
+            row[3] = L > 2ull * edge ? L - 2ull * edge : L;
+            // max x sum bounds sumsq from above: where it does not fit 64 bits, sumsq may have wrapped
+            if (((unsigned __int128) row[7] * row[5]) >> 64) { cdm_set_error("cdm_pileup_depth: query %u: max depth %llu x depth sum %llu does not fit 64 bits (the bound of sumsq)", queries[b0 + i], (unsigned long long) row[7], (unsigned long long) row[5]); return CDM_ERR_UNSUPPORTED; }
+        }
+        trackAt += nTrack; b0 += m;
+    }
+    ctx->lastMs[17] = msTotal;
+    return CDM_OK;
+}
+
+// the argument checks the two entry points share
+static int pileupCheckArgs(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries) {
+    if (alns->n != db->n) { cdm_set_error("%s: alignment CSR has %llu queries, DB has %llu", who, (unsigned long long) alns->n, (unsigned long long) db->n); return CDM_ERR_INVALID; }
+    if (db->residues && !db->codes) { cdm_set_error("%s: the DB holds no letters (an index copy)", who); return CDM_ERR_INVALID; }
+    std::vector<uint32_t> sorted(queries, queries + n_queries);
+    std::sort(sorted.begin(), sorted.end());
+    if (n_queries && sorted.back() >= db->n) { cdm_set_error("%s: query index %u of a DB of %llu sequences", who, sorted.back(), (unsigned long long) db->n); return CDM_ERR_INVALID; }
+    for (uint64_t i = 1; i < n_queries; i++)
+        if (sorted[i] == sorted[i - 1]) { cdm_set_error("%s: query index %u is listed twice", who, sorted[i]); return CDM_ERR_INVALID; }
+    return CDM_OK;
+}
+
+extern "C" int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_depth_params *par,
+                                uint64_t *stats, uint32_t *depth) {
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_depth");
+    if (!ctx || !db || !alns || !par || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_depth: NULL argument"); return CDM_ERR_INVALID; }
+    if (par->edge < 0) { cdm_set_error("cdm_pileup_depth: edge = %d; the positions left out at either end of a contig are 0 or more", par->edge); return CDM_ERR_INVALID; }
+    if (int rc = pileupCheckArgs("cdm_pileup_depth", db, alns, queries, n_queries)) return rc;
+    if (n_queries == 0) return CDM_OK;
+    CDM_HIP(hipSetDevice(ctx->device));
+    return cdm_depth_impl(ctx, db, alns, queries, n_queries, par, stats, depth);
+}
+
 extern "C" int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_pileup_params *par,
                                   uint64_t *counts, uint64_t *reads, uint64_t *columns) {
     if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_profile");
     if (!ctx || !db || !alns || !par || (n_queries && (!queries || !counts || !reads || !columns))) { cdm_set_error("cdm_pileup_profile: NULL argument"); return CDM_ERR_INVALID; }
     if (par->ends < 1 || par->ends > PU_MAX_ENDS) { cdm_set_error("cdm_pileup_profile: ends = %d; the tables hold 1 to %d positions from either end of a read", par->ends, PU_MAX_ENDS); return CDM_ERR_INVALID; }
-    if (alns->n != db->n) { cdm_set_error("cdm_pileup_profile: alignment CSR has %llu queries, DB has %llu", (unsigned long long) alns->n, (unsigned long long) db->n); return CDM_ERR_INVALID; }
-    if (db->residues && !db->codes) { cdm_set_error("cdm_pileup_profile: the DB holds no letters (an index copy)"); return CDM_ERR_INVALID; }
-    {
-        std::vector<uint32_t> sorted(queries, queries + n_queries);
-        std::sort(sorted.begin(), sorted.end());
-        if (n_queries && sorted.back() >= db->n) { cdm_set_error("cdm_pileup_profile: query index %u of a DB of %llu sequences", sorted.back(), (unsigned long long) db->n); return CDM_ERR_INVALID; }
-        for (uint64_t i = 1; i < n_queries; i++)
-            if (sorted[i] == sorted[i - 1]) { cdm_set_error("cdm_pileup_profile: query index %u is listed twice", sorted[i]); return CDM_ERR_INVALID; }
-    }
+    if (int rc = pileupCheckArgs("cdm_pileup_profile", db, alns, queries, n_queries)) return rc;
     if (n_queries == 0) return CDM_OK;
     CDM_HIP(hipSetDevice(ctx->device));
     return cdm_pileup_impl(ctx, db, alns, queries, n_queries, par, counts, reads, columns);

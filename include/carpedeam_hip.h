@@ -56,7 +56,8 @@ void *cdm_ctx_stream(cdm_ctx *ctx);
  * 8..11: the WHOLE stage call (everything it launched, host round trips between kernels included) of kmermatcher, rescorediagonal,
  * ancient_correction, ancient_read_assemble; 13: the radix PASS launches of sort 1 on the k-mer slots alone, summed, 14: how many
  * launches that sum covers, 15: the bytes those launches move at the least, in GB - every pair or tuple they sort read once and
- * written once per launch (bench.py's roofline figure); 16: cdm_pileup_profile's counting kernel.
+ * written once per launch (bench.py's roofline figure); 16: cdm_pileup_profile's counting kernel; 17: cdm_pileup_depth's kernels (marks, prefix
+ * sum, statistics), summed over its batches.
  * Returns a negative value when that stage has not run. */
 float cdm_ctx_last_kernel_ms(cdm_ctx *ctx, int which);
 
@@ -375,6 +376,33 @@ int cdm_correct(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const c
 typedef struct cdm_pileup_params { int32_t ends; float min_seq_id; int32_t skip_extended_targets; } cdm_pileup_params;
 int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
                        const cdm_pileup_params *par, uint64_t *counts, uint64_t *reads, uint64_t *columns);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Depth of coverage at every position of the listed queries, and its statistics (not a module of the reference; csrc/pileup.hip).
+ * A record r of a listed query q of `len` letters counts under exactly the rule of cdm_pileup_profile: r.target != q,
+ * r.seq_id >= min_seq_id (float against float), with skip_extended_targets the target's wasExtended flag is 0, and the oriented
+ * record fits both sequences.  The oriented record covers the query positions qs..qe; depth[i] = the number of counted records with
+ * qs <= i <= qe.  A position counts whether or not it holds an N (as `columns` does).
+ * The statistics window is the whole query when len <= 2 * edge, else the positions edge .. len - 1 - edge (binning tools take mean
+ * and variance away from the contig ends, where reads cannot overhang); no query of at least one letter gets an empty window.
+ *   stats   n_queries x 8 uint64, per listed query:
+ *             0 reads    records counted (cdm_pileup_profile's)      1 columns  sum of qe - qs + 1 over them (cdm_pileup_profile's; the
+ *                                                                               sum of depth over the whole query)
+ *             2 breadth  positions of the whole query with depth >= 1  3 window   positions in the statistics window
+ *             4 covered  window positions with depth >= 1              5 sum      sum of depth over the window
+ *             6 sumsq    sum of depth^2 over the window                7 max      largest depth in the window
+ *   depth   NULL, or the depth of every position as uint32: the listed queries back to back in listed order (the sum of their lengths)
+ * The library hands out integers; the caller divides: mean = sum / window, variance = (sumsq - sum^2 / window) / (window - 1).
+ * edge < 0, a query index >= the DB's size or listed twice are CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched); a set
+ * with the coordinates -1 record is refused as cdm_pileup_profile refuses it.  Two bounds are refused with CDM_ERR_UNSUPPORTED, never
+ * wrapped: a listed query with 2^32 records or more (the depth cells are 32 bits wide), and a query whose max * sum does not fit
+ * 64 bits (the upper bound of sumsq, checked in 128-bit arithmetic after the kernels).  Neither is reachable at test size, and
+ * neither is tested.
+ * As with the damage tables, this is coverage by seeded ungapped overlaps at the set's identity threshold, not by a gapped mapping.
+ * Device time of the kernels: cdm_ctx_last_kernel_ms(ctx, 17). */
+typedef struct cdm_depth_params { int32_t edge; float min_seq_id; int32_t skip_extended_targets; } cdm_depth_params;
+int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                     const cdm_depth_params *par, uint64_t *stats, uint32_t *depth);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
