@@ -86,6 +86,22 @@ class DepthParams(C.Structure):
     _fields_ = [("edge", C.c_int32), ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
 
 
+class BasesParams(C.Structure):
+    """cdm_bases_params: read positions left out at either end of a read, the three thresholds of the site flags, the records' identity
+    threshold, reads only as targets"""
+    _fields_ = [("mask_ends", C.c_int32), ("min_depth", C.c_int32), ("min_alt_count", C.c_int32), ("min_alt_percent", C.c_int32),
+                ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
+class Site(C.Structure):
+    """cdm_site: one flagged position"""
+    _fields_ = [("query", C.c_uint32), ("pos", C.c_uint32), ("info", C.c_uint32), ("counts", C.c_uint32 * 8)]
+
+
+SITE_DTYPE = np.dtype([("query", "<u4"), ("pos", "<u4"), ("info", "<u4"), ("counts", "<u4", (8,))])
+SITE_CALLED, SITE_DIFFERS, SITE_VARIABLE = 1, 2, 4
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -97,7 +113,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -213,6 +229,9 @@ def lib():
         l.cdm_seqdb_copy_ext.argtypes = [vp, vp, vp]
         l.cdm_pileup_profile.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(PileupParams), vp, vp, vp]
         l.cdm_pileup_depth.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(DepthParams), vp, vp]
+        l.cdm_pileup_bases.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(BasesParams), vp, vp, C.POINTER(C.POINTER(Site)), u64p, C.POINTER(C.c_float)]
+        l.cdm_sites_free.argtypes = [C.POINTER(Site)]
+        l.cdm_sites_free.restype = None
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -665,6 +684,41 @@ class Ctx:
             return stats
         ends = np.cumsum(lens)
         return stats, [depth[int(e - l):int(e)].copy() for l, e in zip(lens, ends)]
+
+    def pileup_bases(self, db, alns, queries, mask_ends=0, min_depth=3, min_alt_count=2, min_alt_percent=20, min_seq_id=0.0, skip_extended_targets=False,
+                     counts=False, sites=False):
+        """base counts and variant sites of the listed queries (cdm_pileup_bases) -> stats[nq, 8] uint64: reads, columns, bases,
+        mismatches, called, differs, variable, flagged; with counts also a list of uint32 [length, 8] arrays, one per listed query
+        (forward A,C,G,T, reverse A,C,G,T); with sites also the site records as an array of SITE_DTYPE.  The order of the extras in the
+        returned tuple is counts, sites.  self.bases_kernel_ms holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 8), np.uint64)
+        lens, table = None, None
+        if counts:
+            if nq and int(q.max()) < db.n:         # (an index beyond the DB is the library's to refuse: nothing is written then)
+                lens = db.meta()[0][q].astype(np.int64)
+            else:
+                lens = np.zeros(nq, np.int64)
+            table = np.zeros((max(int(lens.sum()), 1), 8), np.uint32)
+        par = BasesParams(int(mask_ends), int(min_depth), int(min_alt_count), int(min_alt_percent), float(min_seq_id), int(bool(skip_extended_targets)))
+        ptr, n_sites, ms = C.POINTER(Site)(), C.c_uint64(0), C.c_float(0.0)
+        _check(lib().cdm_pileup_bases(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(table), C.byref(ptr) if sites else None,
+                                      C.byref(n_sites) if sites else None, C.byref(ms)))
+        self.bases_kernel_ms = float(ms.value)
+        out = [stats]
+        if counts:
+            ends = np.cumsum(lens)
+            out.append([table[int(e - l):int(e)].copy() for l, e in zip(lens, ends)])
+        if sites:
+            n = int(n_sites.value)
+            assert (n == 0) == (not ptr)
+            recs = np.empty(n, SITE_DTYPE)
+            if n:
+                C.memmove(recs.ctypes.data, ptr, n * C.sizeof(Site))
+                lib().cdm_sites_free(ptr)
+            out.append(recs)
+        return out[0] if len(out) == 1 else tuple(out)
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

@@ -36,6 +36,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_damage",
                                     /* per-contig depth, breadth and depth variance from the same pile-up: not a module of the reference either */
                                     "contig_depth",
+                                    /* per-position base counts and variant sites from the same pile-up: not a module of the reference either */
+                                    "contig_variants",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

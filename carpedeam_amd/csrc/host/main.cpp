@@ -1401,14 +1401,91 @@ void depthTrackFile(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<
     }
     if (!writeText(outPath, text)) die("Could not write " + outPath);
 }
-// Both reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
-// alignment set.  damageOut / depthOut: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
+// ---- contig_variants: per-position base counts and variant sites from the same pile-up (not a module of the reference).  The three
+// calls above, then cdm_pileup_bases over the contigs: one summary line per contig, with --sites one line per position where the reads
+// disagree with the contig (D) or among themselves (V), with --consensus the contigs with the reads' majority letter at the D
+// positions.  As with the other two reports the pile-up is seeded UNGAPPED overlaps at the identity threshold: no indels, and no call
+// where no read seeds.  Integers only.
+const FlagSpec VARIANT_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0}, {"--sites", 'U', 0, 0},
+                                  {"--consensus", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+struct VariantOpts { long maskEnds, minDepth, minAltCount, minAltPercent; };
+VariantOpts variantOpts(Args &a, const char *module) {
+    auto ranged = [&](const char *flag, long dflt, long lo, long hi, const char *what) {
+        const long v = iflag(a, flag, dflt);
+        if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
+        return v;
+    };
+    VariantOpts o;
+    o.maskEnds = ranged("--mask-ends", 0, 0, 64, "0 to 64 read positions are left out at either end of a read");
+    o.minDepth = ranged("--min-depth", 3, 1, 1000000, "a called position has 1 to 1000000 bases");
+    o.minAltCount = ranged("--min-alt-count", 2, 1, 1000000, "a second allele has 1 to 1000000 bases");
+    o.minAltPercent = ranged("--min-alt-percent", 20, 0, 100, "a percentage of the depth is 0 to 100");
+    return o;
+}
+// what a variant report writes: the summary always, the other two files when named
+struct VariantOut { VariantOpts opt; const std::string *summary, *sites, *consensus; };
+// no contigs: the summary's header line alone, an empty sites file, an empty FASTA
+void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const VariantOut &v, Laps &laps) {
+    std::string text = "name\tkey\tlength\treads\tcolumns\tbases\tmismatches\tcalled\tdiffers\tvariable\n", sitesText, fasta;
+    if (haveContigs(contigs)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        std::vector<uint32_t> q(nc), lens(nc);
+        std::iota(q.begin(), q.end(), 0u);
+        std::vector<uint64_t> stats(nc * 8);
+        cdm_bases_params bp; bp.mask_ends = (int32_t) v.opt.maskEnds; bp.min_depth = (int32_t) v.opt.minDepth; bp.min_alt_count = (int32_t) v.opt.minAltCount;
+        bp.min_alt_percent = (int32_t) v.opt.minAltPercent; bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
+        const bool wantSites = v.sites || v.consensus;
+        cdm_site *sites = NULL; uint64_t nSites = 0; float ms = 0.f;
+        check(cdm_pileup_bases(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu sites, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nSites, ms);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        char num[32]; std::string tmp;
+        auto put = [&](std::string &to, unsigned long long x) { to.push_back('\t'); to.append(num, (size_t) (utoa(x, num) - num)); };
+        for (uint64_t i = 0; i < nc; i++) {
+            text += contigName(*contigs, i, tmp);
+            put(text, contigs->keys[i]); put(text, lens[i]);
+            for (int c = 0; c < 7; c++) put(text, stats[i * 8 + c]);
+            text.push_back('\n');
+        }
+        static const char LETTER[] = "ACGTN";
+        if (v.sites)
+            for (uint64_t k = 0; k < nSites; k++) {     // name, pos (1-based), ref, major, flags, depth, forward A C G T, reverse a c g t
+                const cdm_site &st = sites[k];
+                const uint32_t fl = st.info >> 8;
+                sitesText += contigName(*contigs, st.query, tmp);
+                put(sitesText, (unsigned long long) st.pos + 1);
+                sitesText.push_back('\t'); sitesText.push_back(LETTER[st.info & 15u]);
+                sitesText.push_back('\t'); sitesText.push_back(LETTER[(st.info >> 4) & 15u]);
+                sitesText.push_back('\t'); if (fl & CDM_SITE_DIFFERS) sitesText.push_back('D'); if (fl & CDM_SITE_VARIABLE) sitesText.push_back('V');
+                unsigned long long d = 0; for (uint32_t c : st.counts) d += c;
+                put(sitesText, d);
+                for (uint32_t c : st.counts) put(sitesText, c);
+                sitesText.push_back('\n');
+            }
+        if (v.consensus) {      // the contigs' own bytes (raw plane included), the reads' majority letter at the D positions
+            std::vector<uint64_t> at(nc + 1, 0);
+            for (uint64_t i = 0; i < nc; i++) at[i + 1] = at[i] + lens[i] + 1ull;
+            std::string letters(at[nc], '\0');
+            check(cdm_seqdb_download(ctx, contigs->db, &letters[0], at.data()), "download of the contigs");
+            for (uint64_t k = 0; k < nSites; k++)
+                if ((sites[k].info >> 8) & CDM_SITE_DIFFERS) letters[at[sites[k].query] + sites[k].pos] = LETTER[(sites[k].info >> 4) & 15u];
+            for (uint64_t i = 0; i < nc; i++) { fasta.push_back('>'); fasta += contigName(*contigs, i, tmp); fasta.push_back('\n'); fasta.append(letters, at[i], lens[i] + 1ull); }
+        }
+        cdm_sites_free(sites);
+        laps.lap("variant report: base counts, tables");
+    }
+    if (!writeText(*v.summary, text)) die("Could not write " + *v.summary);
+    if (v.sites && !writeText(*v.sites, sitesText)) die("Could not write " + *v.sites);
+    if (v.consensus && !writeText(*v.consensus, fasta)) die("Could not write " + *v.consensus);
+}
+// The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
+// alignment set.  damageOut / depthOut / variants: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
 void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const std::string *damageOut, long ends, const std::string *depthOut, long edge,
-                 const std::string *trackOut, Laps &laps) {
+                 const std::string *trackOut, const VariantOut *variants, Laps &laps) {
     PileSet ps;
     if (haveContigs(contigs)) {
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
-        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : "depth report: kmermatcher, rescorediagonal");
+        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : depthOut ? "depth report: kmermatcher, rescorediagonal" : "variant report: kmermatcher, rescorediagonal");
     }
     if (damageOut) damageTable(ctx, contigs, ps, ends, *damageOut, laps);
     if (depthOut) {
@@ -1418,6 +1495,7 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
         if (trackOut) depthTrackFile(ctx, contigs, track, *trackOut);
         laps.lap("depth report: depth, table");
     }
+    if (variants) variantReport(ctx, contigs, ps, *variants, laps);
     freePileSet(ps);
 }
 int contigDamage(Args &a) {
@@ -1430,7 +1508,7 @@ int contigDamage(Args &a) {
     const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
     if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
     laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, laps);
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, NULL, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
     if (reads.db) cdm_seqdb_free(reads.db);
     cdm_ctx_destroy(ctx);
@@ -1463,6 +1541,25 @@ int contigDepth(Args &a) {
     if (wantTrack) depthTrackFile(ctx, have ? &contigs : NULL, track, a.flag["--depth-track"]);
     laps.lap("depth report: table");
     if (contigs.db) cdm_seqdb_free(contigs.db);
+    cdm_ctx_destroy(ctx);
+    return EXIT_SUCCESS;
+}
+int contigVariants(Args &a) {
+    if (a.pos.size() != 3) die("Usage: carpedeam contig_variants <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-alt-count 2] [--min-alt-percent 20] [--mask-ends 0] "
+                               "[--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20]");
+    checkFlags("contig_variants", a, VARIANT_FLAGS);
+    VariantOut v;
+    v.opt = variantOpts(a, "contig_variants");
+    v.summary = &a.pos[2]; v.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; v.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
+    Laps laps;
+    cdm_ctx *ctx = openCtx();
+    DamageInput contigs, reads;
+    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
+    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_variants: " + a.pos[1] + " holds no reads");
+    laps.lap("inputs read, sequences up");
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, &v, laps);
+    if (contigs.db) cdm_seqdb_free(contigs.db);
+    if (reads.db) cdm_seqdb_free(reads.db);
     cdm_ctx_destroy(ctx);
     return EXIT_SUCCESS;
 }
@@ -1667,6 +1764,7 @@ const FlagSpec FUSED_FLAGS[] = {
     {"--k-ancient-contigs", 'U', 0, 0}, {"--include-only-extendable-ancient-contigs", 'U', 0, 0}, {"--cycle-check", 'U', 0, 0}, {"--chop-cycle", 'U', 0, 0}, {"--gpus", 'U', 0, 0},
     // the tail's
     {"--damage-report", 'U', 0, 0}, {"--damage-ends", 'U', 0, 0}, {"--depth-report", 'U', 0, 0}, {"--depth-edge", 'U', 0, 0},
+    {"--variant-report", 'U', 0, 0}, {"--variant-sites", 'U', 0, 0}, {"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0},
     {"--min-contig-len", 'U', 0, 0}, {"--clust-min-seq-id", 'U', 0, 0}, {"--clust-min-cov", 'U', 0, 0}, {"--zdrop", 'U', 0, 0}, {"--threads", 'U', 0, 0}, {"--remove-tmp-files", 'U', 0, 0},
     {"-v", 'U', 0, 0},
     {"--cluster-mode", 'V', "2", "the redundancy reduction clusters greedily, linclust's mode for --cov-mode 1"}, {"--cov-mode", 'V', "1", "the workflow's coverage mode throughout"},
@@ -1779,7 +1877,16 @@ int assembleFused(Args &a) {
     const bool depthRep = a.flag.count("--depth-report") != 0;
     const std::string depthFile = depthRep ? a.flag["--depth-report"] : "";
     const long reportEdge = depthEdge(a, "ancient_assemble_fused");
-    const bool anyReport = report || depthRep;
+    // --variant-report <file> [--variant-sites <file>]: likewise contig_variants' summary and sites of the final representatives (no
+    // consensus FASTA: that would be a second assembly output)
+    const bool variantRep = a.flag.count("--variant-report") != 0;
+    if (a.flag.count("--variant-sites") && !variantRep) die("ancient_assemble_fused: --variant-sites comes with --variant-report");
+    const std::string variantFile = variantRep ? a.flag["--variant-report"] : "", variantSites = a.flag.count("--variant-sites") ? a.flag["--variant-sites"] : "";
+    VariantOut variantOut;
+    variantOut.opt = variantOpts(a, "ancient_assemble_fused");
+    variantOut.summary = &variantFile; variantOut.sites = variantSites.empty() ? NULL : &variantSites; variantOut.consensus = NULL;
+    const VariantOut *const variants = variantRep ? &variantOut : NULL;
+    const bool anyReport = report || depthRep || variantRep;
     // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
     if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
     if (const char *dry = getenv("CDM_FUSED_DRY_RUN")) {        // "cycle": the tail as it runs with circular contigs among the selection
@@ -1826,7 +1933,7 @@ int assembleFused(Args &a) {
         // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
         cdm_seqdb_free(selected);
         if (!writeText(outFile, "")) die("Could not write " + outFile);
-        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, laps); cdm_seqdb_free(E.reads); }
+        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, laps); cdm_seqdb_free(E.reads); }
         cdm_ctx_destroy(ctx);
         if (removeTmp) removeOwnDir(T);
         return EXIT_SUCCESS;
@@ -1917,7 +2024,7 @@ int assembleFused(Args &a) {
     if (anyReport) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
         DamageInput contigs;
         const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
-        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, laps);
+        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, laps);
         if (contigs.db) cdm_seqdb_free(contigs.db);
         cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);
     }
@@ -1947,7 +2054,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -1967,6 +2074,7 @@ int main(int argc, char **argv) {
     else if (cmd == "ancient_assemble_fused") rc = assembleFused(a);
     else if (cmd == "contig_damage") rc = contigDamage(a);
     else if (cmd == "contig_depth") rc = contigDepth(a);
+    else if (cmd == "contig_variants") rc = contigVariants(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

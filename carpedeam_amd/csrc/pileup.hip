@@ -1,5 +1,6 @@
-// Per-query coverage and damage tables of the read pile-up (cdm_pileup_profile) and the depth at every position of a query with its
-// statistics (cdm_pileup_depth, in the second half of this file); neither is a module of the reference.
+// Per-query coverage and damage tables of the read pile-up (cdm_pileup_profile), the depth at every position of a query with its
+// statistics (cdm_pileup_depth, the second part of this file) and the per-position base counts with the variant sites
+// (cdm_pileup_bases, the third); none is a module of the reference.
 //
 // ancient_correction orients every record of a query and piles the targets up column by column (correct.hip: orient(), targetBase());
 // this unit walks the same columns and COUNTS: for the first and the last `ends` positions of every read, which query base stands
@@ -242,6 +243,170 @@ __global__ __launch_bounds__(DP_NT) void k_depth_stats(DepthArgs a, uint64_t fir
     }
 }
 
+// ---------------------------------------------------------------------------------------------- cdm_pileup_bases
+// Which bases the reads put on every position of the listed queries, and the positions where they disagree with the query or among
+// themselves (include/carpedeam_hip.h).  Unlike the two reductions above this one walks EVERY column of every counted record, so the
+// lanes of a wave take the columns of ONE record, not records: a wave instruction then reads one or two read code words per 16 lanes and
+// adds to consecutive words.  The batch's counters are eight planes [forward A,C,G,T, reverse A,C,G,T][position]: the lanes of one
+// instruction that carry the same base add to a contiguous run of one plane (an interleaved [position][8] table would touch one word
+// in each of 64 separate 32-byte cells).  A second kernel reads the planes by tiles of positions, classifies, reduces the query's
+// figures and marks the flagged positions; one prefix sum over the marks places the site records, which a third kernel writes.
+constexpr uint64_t BS_POS_DEFAULT = 1ull << 25;         // positions per batch: 2^25 x 8 planes x 4 bytes = 1 GB
+constexpr int BS_MAX_MASK = 64;
+
+uint64_t basesPositions() {     // CDM_BASES_POSITIONS=<positions> (tests): small inputs in several batches
+    if (const char *e = cdmGetenv("CDM_BASES_POSITIONS")) { const long long v = atoll(e); if (v > 0) return std::min<uint64_t>((uint64_t) v, BS_POS_DEFAULT); }
+    return BS_POS_DEFAULT;
+}
+
+struct BasesArgs {
+    const SeqMeta *meta; const uint32_t *codes, *nmask; const uint64_t *aoff; const AlnRec *rec;
+    const uint32_t *queries;        // [nq] the listed queries of this call's batch
+    const uint64_t *itemOff;        // [nq + 1] first counting item (chunk of records) of each listed query
+    const uint64_t *tileOff;        // [nq + 1] first classification item (tile of positions) of each
+    const uint64_t *base;           // [nq + 1] first position of each in a plane
+    uint32_t n, nq, chunk, skipExt, maskEnds, minDepth, minAlt, minPct, firstQuery; float minSeqId;
+    uint64_t nPos;                  // positions of the batch: the length of a plane
+    uint32_t *planes;               // [8][nPos]
+    unsigned long long *stats;      // [nq][8]
+    uint32_t *place;                // [nPos + 1]: 0/1 per flagged position, after the scan the position's first site record
+    uint32_t *counts;               // NULL, or [nPos][8]
+    cdm_site *sites;                // k_base_emit: [place[nPos]]
+};
+
+// counting: one wave per item (listed query, chunk of its records) of this launch's slice.  Each lane loads one record and evaluates
+// the filter; the wave then walks the counted records one at a time, its lanes on the columns lane, lane + 64, ...
+__global__ __launch_bounds__(64 * PU_WAVES) void k_base_counts(BasesArgs a, uint64_t first, uint64_t nThis) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
+    if (local >= nThis) return;
+    const uint64_t item = first + local;
+    uint32_t lo = 0, hi = a.nq;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.itemOff[mid] <= item) lo = mid; else hi = mid; }
+    const uint32_t qi = lo, q = a.queries[qi];
+    const uint64_t r0 = a.aoff[q] + (item - a.itemOff[qi]) * a.chunk, r1 = min((uint64_t) a.aoff[q + 1], r0 + a.chunk);
+    const uint32_t qLen = a.meta[q].len, m = a.maskEnds;
+    uint32_t *__restrict__ plane0 = a.planes + a.base[qi];
+    unsigned int nReads = 0; unsigned long long nCols = 0;
+    for (uint64_t rb = r0; rb < r1; rb += 64) {       // (wave-uniform: the shuffles below see all 64 lanes)
+        Oriented o = {0, 0, 0, 0, false}; uint32_t tLen = 0, tw = 0;
+        bool counted = false;
+        if (rb + lane < r1) { const AlnRec rec = a.rec[rb + lane]; counted = countedRecord(a.meta, a.n, a.skipExt, a.minSeqId, q, qLen, rec, o, tLen, tw); }
+        const uint32_t myL = counted ? (uint32_t) (o.qe - o.qs) + 1u : 0u;
+        nReads += counted; nCols += myL;
+        for (unsigned long long live = __ballot(counted); live; live &= live - 1) {
+            const int src = __ffsll((long long) live) - 1;
+            const uint32_t qs = (uint32_t) __shfl(o.qs, src, 64), ds = (uint32_t) __shfl(o.ds, src, 64), L = __shfl(myL, src, 64);
+            const uint32_t len = __shfl(tLen, src, 64), w = __shfl(tw, src, 64), rev = (uint32_t) __shfl((int) o.rev, src, 64);
+            // (countedRecord: qs + L <= qLen and ds + L <= len, so every index below stays inside the query's planes and the read's words)
+            for (uint32_t c = lane; c < L; c += 64) {
+                const uint32_t op = ds + c, p = rev ? len - 1u - op : op;
+                if (cdm_isN(a.nmask, w, p)) continue;
+                if (m && (p < m || len - 1u - p < m)) continue;
+                uint32_t b = cdm_base(a.codes, w, p);
+                if (rev) b = 3u - b;                  // the read base as the query's strand sees it
+                atomicAdd(&plane0[(uint64_t) (rev * 4u + b) * a.nPos + qs + c], 1u);        // (result unused: an atomic without return)
+            }
+        }
+    }
+    const unsigned int rd = (unsigned int) cdm_wave_sum((int) nReads);
+    const unsigned long long cl = waveSum64(nCols);
+    if (lane == 0 && rd) { atomicAdd(&a.stats[(uint64_t) qi * 8], (unsigned long long) rd); atomicAdd(&a.stats[(uint64_t) qi * 8 + 1], cl); }
+}
+
+// one position's verdict from its eight counters and the query's letter (ref: its code, 4 for N)
+struct SiteCall { uint32_t ref, major, flags; unsigned long long depth, atRef; };
+__device__ __forceinline__ SiteCall callSite(const uint32_t c[8], uint32_t ref, uint32_t minDepth, uint32_t minAlt, uint32_t minPct) {
+    const uint32_t t[4] = {c[0] + c[4], c[1] + c[5], c[2] + c[6], c[3] + c[7]};       // (a record adds one column to a position: each below 2^32)
+    SiteCall s;
+    s.ref = ref; s.depth = (unsigned long long) t[0] + t[1] + t[2] + t[3];
+    uint32_t mj = 0;
+#pragma unroll
+    for (uint32_t b = 1; b < 4; b++) if (t[b] > t[mj]) mj = b;        // the lowest code among equal largest
+    if (ref < 4u && t[ref] == t[mj]) mj = ref;
+    uint32_t second = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++) if (b != mj) second = max(second, t[b]);
+    s.major = mj; s.atRef = ref < 4u ? t[ref] : 0ull;
+    uint32_t f = 0;
+    if (s.depth >= minDepth) {
+        f = CDM_SITE_CALLED;
+        if (mj != ref && t[mj] > second) f |= CDM_SITE_DIFFERS;
+        if (second >= minAlt && (unsigned long long) second * 100ull >= (unsigned long long) minPct * s.depth) f |= CDM_SITE_VARIABLE;
+    }
+    s.flags = f;
+    return s;
+}
+
+// the item (listed query, tile of DP_TILE positions) of a block and what its threads need of it
+struct BaseTile { uint32_t qi, len, qw; uint64_t pb, p0; };
+__device__ __forceinline__ BaseTile baseTile(const BasesArgs &a, uint64_t item) {
+    uint32_t lo = 0, hi = a.nq;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.tileOff[mid] <= item) lo = mid; else hi = mid; }
+    const SeqMeta qm = a.meta[a.queries[lo]];
+    BaseTile t;
+    t.qi = lo; t.len = qm.len; t.qw = qm.woff; t.pb = a.base[lo]; t.p0 = (item - a.tileOff[lo]) * DP_TILE;
+    return t;
+}
+__device__ __forceinline__ SiteCall callAt(const BasesArgs &a, const BaseTile &t, uint32_t p, uint32_t c[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = a.planes[(uint64_t) k * a.nPos + t.pb + p];
+    const uint32_t ref = cdm_isN(a.nmask, t.qw, p) ? 4u : cdm_base(a.codes, t.qw, p);
+    return callSite(c, ref, a.minDepth, a.minAlt, a.minPct);
+}
+
+// classification: one block per item (listed query, tile of DP_TILE positions) of this launch's slice
+__global__ __launch_bounds__(DP_NT) void k_base_sites(BasesArgs a, uint64_t first) {
+    __shared__ unsigned long long sRed[DP_NT / 64][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const BaseTile t = baseTile(a, first + blockIdx.x);
+    unsigned long long bases = 0, mism = 0, four = 0;       // four: called, differs, variable, flagged in 16 bits each (at most DP_TILE)
+#pragma unroll
+    for (int j = 0; j < DP_PER; j++) {
+        const uint64_t p = t.p0 + threadIdx.x + (uint64_t) DP_NT * j;
+        if (p >= t.len) continue;
+        uint32_t c[8];
+        const SiteCall s = callAt(a, t, (uint32_t) p, c);
+        if (a.counts) {
+            uint4 *row = reinterpret_cast<uint4 *>(a.counts + (t.pb + p) * 8);
+            row[0] = make_uint4(c[0], c[1], c[2], c[3]); row[1] = make_uint4(c[4], c[5], c[6], c[7]);
+        }
+        const uint32_t fl = (s.flags & (CDM_SITE_DIFFERS | CDM_SITE_VARIABLE)) != 0;
+        a.place[t.pb + p] = fl;
+        bases += s.depth;
+        if (s.ref < 4u) mism += s.depth - s.atRef;
+        four += (unsigned long long) (s.flags & 1u) | (unsigned long long) ((s.flags >> 1) & 1u) << 16 | (unsigned long long) ((s.flags >> 2) & 1u) << 32 | (unsigned long long) fl << 48;
+    }
+    bases = waveSum64(bases); mism = waveSum64(mism); four = waveSum64(four);
+    if (lane == 0) { sRed[wave][0] = bases; sRed[wave][1] = mism; sRed[wave][2] = four; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long r[3] = {0, 0, 0};
+        for (int w = 0; w < DP_NT / 64; w++) { r[0] += sRed[w][0]; r[1] += sRed[w][1]; r[2] += sRed[w][2]; }
+        unsigned long long *row = a.stats + (uint64_t) t.qi * 8;
+        if (r[0]) { atomicAdd(&row[2], r[0]); if (r[1]) atomicAdd(&row[3], r[1]); }
+        for (int k = 0; k < 4; k++) { const unsigned long long v = (r[2] >> (16 * k)) & 0xFFFFull; if (v) atomicAdd(&row[4 + k], v); }
+    }
+}
+
+// emission: the same items; a position is flagged where the scanned marks step, and its record goes to the place the scan gave it
+__global__ __launch_bounds__(DP_NT) void k_base_emit(BasesArgs a, uint64_t first) {
+    const BaseTile t = baseTile(a, first + blockIdx.x);
+#pragma unroll
+    for (int j = 0; j < DP_PER; j++) {
+        const uint64_t p = t.p0 + threadIdx.x + (uint64_t) DP_NT * j;
+        if (p >= t.len) continue;
+        const uint32_t at = a.place[t.pb + p];
+        if (a.place[t.pb + p + 1] == at) continue;
+        uint32_t c[8];
+        const SiteCall s = callAt(a, t, (uint32_t) p, c);
+        cdm_site *out = a.sites + at;
+        out->query = a.firstQuery + t.qi; out->pos = (uint32_t) p; out->info = s.ref | s.major << 4 | s.flags << 8;
+#pragma unroll
+        for (int k = 0; k < 8; k++) out->counts[k] = c[k];
+    }
+}
+
 }  // namespace
 
 // test aid, not part of the public header: records per work item as the next call will cut them (tests pile up one record more)
@@ -370,7 +535,101 @@ static int cdm_depth_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
     return CDM_OK;
 }
 
-// the argument checks the two entry points share
+static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_bases_params *par, uint64_t *stats, uint32_t *counts,
+                          cdm_site **sites, uint64_t *nSitesOut, float *kernelMs) {
+    hipStream_t s = ctx->stream;
+    const uint32_t chunk = pileupChunk();
+    const uint64_t bound = basesPositions();
+    DevBuf<SeqMeta> meta;
+    if (int rc = cdm_build_meta(ctx, db, &meta.p)) return rc;
+    DevBuf<uint32_t> dq, dLen; DevBuf<uint64_t> dRecs;
+    if (!dq.alloc(nq) || !dLen.alloc(nq) || !dRecs.alloc(nq)) { cdm_set_error("cdm_pileup_bases: out of device memory for %llu queries", (unsigned long long) nq); return CDM_ERR_HIP; }
+    std::vector<uint32_t> len(nq); std::vector<uint64_t> recs(nq);
+    CDM_HIP(hipMemcpyAsync(dq.p, queries, (size_t) nq * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_depth_sizes, CDM_GRID((nq + 255) / 256, 256), dim3(256), 0, s, (const SeqMeta *) meta.p, (const uint64_t *) alns->off, (const uint32_t *) dq.p, nq, dLen.p, dRecs.p);
+    CDM_LAUNCH_CHECK();
+    CDM_HIP(hipMemcpyAsync(len.data(), dLen.p, (size_t) nq * 4, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipMemcpyAsync(recs.data(), dRecs.p, (size_t) nq * 8, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < nq; i++)
+        if (recs[i] >> 32) { cdm_set_error("cdm_pileup_bases: query %u has %llu records; the 32-bit counters hold fewer than 2^32", queries[i], (unsigned long long) recs[i]); return CDM_ERR_UNSUPPORTED; }
+    float msTotal = 0.f;
+    uint64_t countsAt = 0;
+    for (uint64_t b0 = 0; b0 < nq;) {
+        // the batch: listed queries while their positions stay within the bound; a single query longer than the bound goes alone
+        uint32_t m = 0; uint64_t nPos = 0;
+        while (b0 + m < nq && m < (1u << 30) && (m == 0 || nPos + len[b0 + m] <= bound)) { nPos += len[b0 + m]; m++; }
+        std::vector<uint64_t> base((size_t) m + 1), tileOff((size_t) m + 1);
+        base[0] = tileOff[0] = 0;
+        for (uint32_t i = 0; i < m; i++) { base[i + 1] = base[i] + len[b0 + i]; tileOff[i + 1] = tileOff[i] + ((uint64_t) len[b0 + i] + DP_TILE - 1) / DP_TILE; }
+        const uint64_t nTiles = tileOff[m];
+        DevBuf<uint64_t> items, itemOff, dBase, dTile; DevBuf<uint32_t> planes, place, dCounts; DevBuf<unsigned long long> dStats; DevBuf<cdm_site> dSites;
+        if (!items.alloc((size_t) m + 1) || !itemOff.alloc((size_t) m + 1) || !dBase.alloc((size_t) m + 1) || !dTile.alloc((size_t) m + 1) || !planes.alloc((size_t) nPos * 8) || !place.alloc((size_t) nPos + 1) ||
+            !dStats.alloc((size_t) m * 8) || (counts && !dCounts.alloc((size_t) nPos * 8))) {
+            cdm_set_error("cdm_pileup_bases: out of device memory for the counters of %llu positions of %u queries", (unsigned long long) nPos, m); return CDM_ERR_HIP;
+        }
+        CDM_HIP(hipMemcpyAsync(dBase.p, base.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemcpyAsync(dTile.p, tileOff.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemsetAsync(planes.p, 0, (size_t) nPos * 32, s));
+        CDM_HIP(hipMemsetAsync(place.p + nPos, 0, 4, s));             // (the closing word: the scan leaves the batch's number of sites there)
+        CDM_HIP(hipMemsetAsync(dStats.p, 0, (size_t) m * 64, s));
+        hipLaunchKernelGGL(k_pileup_chunks, dim3((m + 256) / 256), dim3(256), 0, s, (const uint64_t *) alns->off, (const uint32_t *) (dq.p + b0), m, chunk, items.p);
+        cdmscan::ScanTemp st, stPlace;
+        if (int rc = cdmscan::exclusiveScan<uint64_t>(s, st, items.p, itemOff.p, (size_t) m + 1)) return rc;
+        uint64_t nItems = 0;
+        CDM_HIP(hipMemcpyAsync(&nItems, itemOff.p + m, 8, hipMemcpyDeviceToHost, s));
+        CDM_HIP(hipStreamSynchronize(s));
+        BasesArgs a;
+        a.meta = meta.p; a.codes = db->codes; a.nmask = db->nmask; a.aoff = alns->off; a.rec = alns->rec; a.queries = dq.p + b0; a.itemOff = itemOff.p; a.tileOff = dTile.p; a.base = dBase.p;
+        a.n = (uint32_t) db->n; a.nq = m; a.chunk = chunk; a.skipExt = par->skip_extended_targets ? 1u : 0u; a.maskEnds = (uint32_t) par->mask_ends; a.minDepth = (uint32_t) par->min_depth;
+        a.minAlt = (uint32_t) par->min_alt_count; a.minPct = (uint32_t) par->min_alt_percent; a.firstQuery = (uint32_t) b0; a.minSeqId = par->min_seq_id;
+        a.nPos = nPos; a.planes = planes.p; a.stats = dStats.p; a.place = place.p; a.counts = counts ? dCounts.p : nullptr; a.sites = nullptr;
+        hipEventRecord(ctx->ev0, s);
+        for (uint64_t first = 0, slice = cdmSliceItems(64); first < nItems; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nItems - first);
+            hipLaunchKernelGGL(k_base_counts, CDM_GRID((nThis + PU_WAVES - 1) / PU_WAVES, 64 * PU_WAVES), dim3(64 * PU_WAVES), 0, s, a, first, nThis);
+        }
+        for (uint64_t first = 0, slice = cdmSliceItems(DP_NT); first < nTiles; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nTiles - first);
+            hipLaunchKernelGGL(k_base_sites, CDM_GRID(nThis, DP_NT), dim3(DP_NT), 0, s, a, first);
+        }
+        uint32_t nSites = 0;
+        if (sites) {
+            if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stPlace, place.p, place.p, (size_t) nPos + 1)) return rc;      // (in place: scan.h)
+            CDM_HIP(hipMemcpyAsync(&nSites, place.p + nPos, 4, hipMemcpyDeviceToHost, s));
+        }
+        hipEventRecord(ctx->ev1, s);
+        CDM_LAUNCH_CHECK();
+        CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
+        if (counts && nPos) CDM_HIP(hipMemcpyAsync(counts + countsAt * 8, dCounts.p, (size_t) nPos * 32, hipMemcpyDeviceToHost, s));
+        { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_pileup_bases: the kernels failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) msTotal += ms;
+        if (nSites) {       // the records of this batch behind those of the batches before it
+            if (!dSites.alloc(nSites)) { cdm_set_error("cdm_pileup_bases: out of device memory for %u site records", nSites); return CDM_ERR_HIP; }
+            a.sites = dSites.p;
+            hipEventRecord(ctx->ev0, s);
+            for (uint64_t first = 0, slice = cdmSliceItems(DP_NT); first < nTiles; first += slice) {
+                const uint64_t nThis = std::min<uint64_t>(slice, nTiles - first);
+                hipLaunchKernelGGL(k_base_emit, CDM_GRID(nThis, DP_NT), dim3(DP_NT), 0, s, a, first);
+            }
+            hipEventRecord(ctx->ev1, s);
+            CDM_LAUNCH_CHECK();
+            cdm_site *grown = (cdm_site *) realloc(*sites, (size_t) (*nSitesOut + nSites) * sizeof(cdm_site));
+            if (!grown) { cdm_set_error("cdm_pileup_bases: out of host memory for %llu site records", (unsigned long long) (*nSitesOut + nSites)); return CDM_ERR_INVALID; }
+            *sites = grown;
+            CDM_HIP(hipMemcpyAsync(grown + *nSitesOut, dSites.p, (size_t) nSites * sizeof(cdm_site), hipMemcpyDeviceToHost, s));
+            *nSitesOut += nSites;
+            { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_pileup_bases: the emission failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
+            if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) msTotal += ms;
+        }
+        countsAt += nPos; b0 += m;
+    }
+    if (kernelMs) *kernelMs = msTotal;
+    return CDM_OK;
+}
+
+// the argument checks the entry points share
 static int pileupCheckArgs(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries) {
     if (alns->n != db->n) { cdm_set_error("%s: alignment CSR has %llu queries, DB has %llu", who, (unsigned long long) alns->n, (unsigned long long) db->n); return CDM_ERR_INVALID; }
     if (db->residues && !db->codes) { cdm_set_error("%s: the DB holds no letters (an index copy)", who); return CDM_ERR_INVALID; }
@@ -392,6 +651,28 @@ extern "C" int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_aln
     CDM_HIP(hipSetDevice(ctx->device));
     return cdm_depth_impl(ctx, db, alns, queries, n_queries, par, stats, depth);
 }
+
+extern "C" int cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_bases_params *par,
+                                uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *n_sites, float *kernel_ms) {
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_bases");
+    if (!ctx || !db || !alns || !par || (sites && !n_sites) || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_bases: NULL argument"); return CDM_ERR_INVALID; }
+    if (par->mask_ends < 0 || par->mask_ends > BS_MAX_MASK) { cdm_set_error("cdm_pileup_bases: mask_ends = %d; 0 to %d positions are left out at either end of a read", par->mask_ends, BS_MAX_MASK); return CDM_ERR_INVALID; }
+    if (par->min_depth < 1) { cdm_set_error("cdm_pileup_bases: min_depth = %d; a called position has at least one base", par->min_depth); return CDM_ERR_INVALID; }
+    if (par->min_alt_count < 1) { cdm_set_error("cdm_pileup_bases: min_alt_count = %d; a second allele has at least one base", par->min_alt_count); return CDM_ERR_INVALID; }
+    if (par->min_alt_percent < 0 || par->min_alt_percent > 100) { cdm_set_error("cdm_pileup_bases: min_alt_percent = %d; a percentage of the depth is 0 to 100", par->min_alt_percent); return CDM_ERR_INVALID; }
+    if (int rc = pileupCheckArgs("cdm_pileup_bases", db, alns, queries, n_queries)) return rc;
+    if (sites) { *sites = NULL; *n_sites = 0; }
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (n_queries == 0) return CDM_OK;
+    CDM_HIP(hipSetDevice(ctx->device));
+    cdm_site *got = NULL; uint64_t nGot = 0;
+    const int rc = cdm_bases_impl(ctx, db, alns, queries, n_queries, par, stats, counts, sites ? &got : NULL, &nGot, kernel_ms);
+    if (rc != CDM_OK) { free(got); return rc; }
+    if (sites) { *sites = got; *n_sites = nGot; }
+    return CDM_OK;
+}
+
+extern "C" void cdm_sites_free(cdm_site *sites) { free(sites); }
 
 extern "C" int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_pileup_params *par,
                                   uint64_t *counts, uint64_t *reads, uint64_t *columns) {

@@ -405,6 +405,54 @@ int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, co
                      const cdm_depth_params *par, uint64_t *stats, uint32_t *depth);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Per-position base counts and variant sites of the read pile-up (not a module of the reference; csrc/pileup.hip): which bases the
+ * reads put on every position of the listed queries, and the positions where that disagrees with the query or among the reads.
+ * A record counts under exactly the rule of cdm_pileup_profile and cdm_pileup_depth.  Column c = i - qs of a counted, oriented record
+ * on query position i: op = ds + c, p = rev ? tLen - 1 - op : op the position in the read's own orientation.  The column is left out
+ * when the read has its N bit at p, and - with mask_ends = m > 0 - when p < m or tLen - 1 - p < m (genotyping of ancient DNA leaves
+ * the damaged read ends out).  Otherwise b = the read's mapped code at p, complemented (3 - b) when rev - the read base as the
+ * query's strand sees it - and counts[i][rev * 4 + b] += 1: forward counters A,C,G,T, then reverse counters A,C,G,T.  The query's own
+ * letter plays no part in the counts; letters are the mapped codes and N bits, never the raw plane.
+ * Per position, with t[b] = counts[i][b] + counts[i][4 + b] and d = sum of t: ref = the query's code, 4 when its N bit is set;
+ * major = the base with the largest t, among equal largest ref if it is one of them, else the lowest code; second = the largest t
+ * over the three other bases.  Flags, integers only (the percent rule in 64 bits):
+ *   CDM_SITE_CALLED   d >= min_depth
+ *   CDM_SITE_DIFFERS  called, major != ref (a query N differs from any base) and t[major] strictly greater than the other three
+ *   CDM_SITE_VARIABLE called, second >= min_alt_count and second * 100 >= min_alt_percent * d
+ *   stats   n_queries x 8 uint64, per listed query:
+ *             0 reads, 1 columns   cdm_pileup_profile's and cdm_pileup_depth's values (masked and N columns included)
+ *             2 bases              sum of all counters of the query
+ *             3 mismatches         sum of d - t[ref] over the positions with ref != 4
+ *             4 called, 5 differs, 6 variable   positions with that flag
+ *             7 flagged            positions with DIFFERS or VARIABLE: the query's number of site records
+ *   counts  NULL, or uint32 [sum of the listed queries' lengths][8]: the queries back to back in listed order
+ *   sites   NULL, or receives a malloc'ed array (cdm_sites_free) of one record per flagged position in listed query order, then
+ *           ascending pos: query = the index into `queries`, info = ref | major << 4 | flags << 8, counts = the position's row.
+ *           *n_sites = their number; n_queries == 0 or no flagged position: *sites = NULL, *n_sites = 0.  n_sites may be NULL only
+ *           when sites is
+ *   kernel_ms  NULL, or receives the device time of the kernels (cdm_ctx_last_kernel_ms has no slot for this call)
+ * mask_ends in 0..64, min_depth >= 1, min_alt_count >= 1, min_alt_percent in 0..100; anything else, a NULL argument, a query index
+ * >= the DB's size or listed twice is CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched); a set with the coordinates -1
+ * record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more is CDM_ERR_UNSUPPORTED (the counters
+ * are 32 bits wide; not reachable at test size, not tested).  As with the two tables above, the pile-up is the set's seeded
+ * ungapped overlaps at its identity threshold, not a gapped mapping: no indels, and no call where no read seeds. */
+#define CDM_SITE_CALLED 1u
+#define CDM_SITE_DIFFERS 2u
+#define CDM_SITE_VARIABLE 4u
+typedef struct cdm_bases_params {
+    int32_t mask_ends;        /* 0..64: read positions left out at either end of a read */
+    int32_t min_depth;        /* >= 1 */
+    int32_t min_alt_count;    /* >= 1 */
+    int32_t min_alt_percent;  /* 0..100 */
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_bases_params;
+typedef struct cdm_site { uint32_t query, pos, info, counts[8]; } cdm_site;   /* 44 bytes */
+int  cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                      const cdm_bases_params *par, uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *n_sites, float *kernel_ms);
+void cdm_sites_free(cdm_site *sites);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
  * db must be the corrected DB.  Output: new sequence DB (extended sequences get ext=1, others are copied through).
  * scores (optional, may be NULL): for tests, the per-candidate likelihood of the first scoring round
