@@ -1,5 +1,5 @@
 // kmermatcher on the device (kmermatch.hip), stage K1:
-//   K1 k_seq_hash, k_extract_pair, k_extract_fast, k_extract   fillKmerPositionArray :77-388  per sequence: canonical k-mers, XXH64 16-bit
+//   K1 k_seq_hash, k_extract_pair, k_extract_uniform, k_extract_fast, k_extract   fillKmerPositionArray :77-388  per sequence: canonical k-mers, XXH64 16-bit
 //                     min-hash, per-sequence ordering by (hash, k-mer, pos) for the repeated-k-mer skipping and the bottom-m
 //                     selection, + the whole-sequence hash tuple
 // and the helper kernels that lay the sequences' slots out in front of it (KmerJob::phaseA, splitPartition).
@@ -290,6 +290,148 @@ __global__ __launch_bounds__(64 * FAST_WAVES) void k_extract_pair(ExtractArgs<LY
         }
         noteBelow(a, below);
         __builtin_amdgcn_wave_barrier();
+    }
+    if (countHead) headHistFlush(sHead, a.headHist);
+}
+
+// A PLAIN UNIFORM DB (common.h MetaUniform) in the slot layout, the whole k-mer space on one device: ONE kernel writes what k_seq_hash and
+// k_extract_pair write together.  A half-wave per read as there, but
+//   - length and word offset follow from the index (no per-read metadata loads).  A wave works on BATCHES of 32 consecutive pairs:
+//     the 64 reads' words are one contiguous stretch, loaded with at most 8 coalesced instructions ONE BATCH AHEAD and kept in LDS
+//     while the batch is worked on; a lane reads the words of its windows from there.  Nothing inside a batch waits for memory:
+//     the stores stream out behind the wave (a wait for a load would be s_waitcnt vmcnt(0) here, i.e. for every store before it);
+//   - lane hl has the positions hl, hl + 32, hl + 64: a store instruction of a half writes 256 contiguous bytes.  All three windows of
+//     a lane start at the same bit of a word, two words apart: two v_alignbit each;
+//   - the repeated-k-mer test is a set of 32-bit tags (256 x 4 bytes per half; the tag is the k-mer's low word with its bits from 32 on
+//     folded in - the k-mer itself up to k = 15).  Equal k-mers have equal tags and walk the same probe sequence, so no repeat is
+//     missed; two different k-mers of a read share a tag once in ~10^7 reads, and all that costs is that read's trip through
+//     k_extract, which is exact.  No multiplication anywhere in an iteration: the kernel is bound by its vector instructions
+//     (a wave's takes a SIMD four cycles, v_mul_lo_u32 sixteen);
+//   - the whole-sequence hashes (Util::hash's Horner walk, then XXH64) are made once per batch by all 64 lanes, a lane per read, from
+//     the words in LDS - a few instructions per letter for 64 reads at once, as in k_seq_hash, without its second pass over the DB -
+//     and the region-2 stores of a batch are 64 consecutive keys.
+// k_uniform_check is the test k_build_meta makes (seqdb.hip), without the table.
+__global__ void k_uniform_check(const uint32_t *__restrict__ len, const uint32_t *__restrict__ woff, const uint8_t *__restrict__ hasN, uint32_t n, uint32_t uniLen, uint32_t uniWords,
+                                unsigned int *__restrict__ notUniform) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (len[i] != uniLen || woff[i] != i * uniWords || hasN[i] != 0)) atomicOr(notUniform, 1u);
+}
+constexpr int UNI_TABLE = 256, UNI_BATCH = 32, UNI_MINW = 8, UNI_WORDS = 8;      // (96 positions of k <= 30 letters: at most 8 words per read)
+static_assert(PAIR_POS == 96 && UNI_BATCH * 2 == 64, "three rounds of 32 positions per half; a lane per read of the batch for the hashes");
+template <typename LY>
+__global__ __launch_bounds__(64 * FAST_WAVES, UNI_MINW) void k_extract_uniform(ExtractArgs<LY> a, uint32_t L, uint32_t W) {
+    static_assert(LY::bySlot, "slot layout only");
+    __shared__ __attribute__((aligned(16))) uint32_t sTag[FAST_WAVES][2][UNI_TABLE];
+    __shared__ uint32_t sWords[FAST_WAVES][64 * UNI_WORDS + 8];       // the batch's words (+ 8: the last read's windows look two words on)
+    __shared__ unsigned int sHead[HEAD_BINS];
+    const bool countHead = a.headHist != nullptr;
+    if (countHead) headHistClear(sHead);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
+    uint32_t *table = sTag[wave][half];
+    const int k = a.k;
+    const uint64_t kmask = (1ull << (2 * k)) - 1ull;
+    const uint32_t nPos = L - (uint32_t) k + 1u, uniS = a.uniS, n = a.n;
+    const uint32_t nPairs = (n + 1) / 2, nBatch = (nPairs + UNI_BATCH - 1) / UNI_BATCH;
+    const uint32_t waveId = blockIdx.x * FAST_WAVES + wave, nWaves = gridDim.x * FAST_WAVES;
+    const uint32_t sh = (uint32_t) (hl & 15) * 2u, rsh = 64u - 2u * (uint32_t) k;
+    uint32_t *words = sWords[wave];
+    const uint64_t nWords = (uint64_t) n * W;
+    // words j x 64 + lane (j < W) of the 64 reads of batch b, A,C,G,T -> A,C,T,G (0: behind the DB's last word)
+    uint32_t pre[UNI_WORDS];
+    auto loadBatch = [&](uint64_t b) {
+#pragma unroll
+        for (int j = 0; j < UNI_WORDS; j++) {
+            const uint64_t g = b * (2u * UNI_BATCH) * W + (uint32_t) (j * 64 + lane);
+            pre[j] = ((uint32_t) j < W && b < nBatch && g < nWords) ? a.codes[g] : 0u;
+        }
+    };
+    loadBatch(waveId);
+    for (uint32_t b = waveId; b < nBatch; b += nWaves) {
+        const uint32_t pr0 = b * UNI_BATCH, cnt = min((uint32_t) UNI_BATCH, nPairs - pr0);
+#pragma unroll
+        for (int j = 0; j < UNI_WORDS; j++) if ((uint32_t) j < W) words[j * 64 + lane] = pre[j] ^ ((pre[j] >> 1) & 0x55555555u);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+        loadBatch((uint64_t) b + nWaves);      // the wave's next batch: on its way while this one is worked on
+        for (uint32_t it = 0; it < cnt; it++) {
+            const uint32_t pr = pr0 + it, seq = 2 * pr + (uint32_t) half;
+            const bool have = seq < n;
+            const uint64_t base = (uint64_t) seq * uniS;
+            const uint32_t *rw = words + (2 * it + (uint32_t) half) * W;
+            { uint4 z; z.x = z.y = z.z = z.w = 0u; ((uint4 *) table)[hl] = z; ((uint4 *) table)[hl + 32] = z; }
+            // The set is this wave's own, and a wave's LDS instructions execute in order: a fence of WAVEFRONT scope keeps the compiler from
+            // moving the compare-and-swaps in front of the clear and costs no wait.  (A workgroup-scope release, as in k_extract_pair, orders
+            // every address space: s_waitcnt vmcnt(0) - the iteration then waits for the read-ahead and for all stores of the one before.)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+            uint32_t x[7];
+#pragma unroll
+            for (int i = 0; i < 7; i++) x[i] = rw[(hl >> 4) + i];
+            // ---- the k-mers at hl, hl + 32, hl + 64
+            uint64_t key[3]; uint32_t tag[3], digit[3]; bool real[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const uint32_t pos = 32u * j + (uint32_t) hl;
+                const bool act = have && pos < nPos;
+                const uint32_t lo = __builtin_amdgcn_alignbit(x[2 * j + 1], x[2 * j], sh), hi = __builtin_amdgcn_alignbit(x[2 * j + 2], x[2 * j + 1], sh);
+                const uint64_t w = (((uint64_t) hi << 32) | lo) & kmask;
+                const uint64_t rc = (w ^ 0xAAAAAAAAAAAAAAAAull) & kmask;     // Util::revComplement(idx): window order, complemented
+                // Indexer order (groupsReversed): all bits reversed, the two bits of every letter swapped back
+                uint64_t idx;
+                {
+                    const uint32_t rh = __builtin_bitreverse32((uint32_t) w), rl = __builtin_bitreverse32((uint32_t) (w >> 32));      // (the reversed value's high and low word)
+                    const uint32_t th = ((rh >> 1) & 0x55555555u) | ((rh & 0x55555555u) << 1), tl = ((rl >> 1) & 0x55555555u) | ((rl & 0x55555555u) << 1);
+                    // >> (64 - 2k), word by word (64-bit shifts are slow vector instructions)
+                    idx = rsh >= 32u ? (uint64_t) (th >> (rsh - 32u)) : (((uint64_t) (th >> rsh) << 32) | __builtin_amdgcn_alignbit(th, tl, rsh));
+                }
+                const bool pickRev = rc < idx;
+                const uint64_t km = pickRev ? rc : idx;
+                real[j] = act && rc != idx;
+                key[j] = rc != idx ? (km | (pickRev ? 0ull : BIT63)) : ~0ull;
+                tag[j] = ((uint32_t) km ^ ((uint32_t) (km >> 32) << 4)) | 0x80000000u;      // (never 0 = empty; k <= 30: 28 bits from 32 on)
+                digit[j] = (uint32_t) (km >> a.headShift);
+                if (act) a.keys[base + 1 + pos] = key[j];
+            }
+            if (have && hl == 0) a.keys[base] = ~0ull;      // (slot 0: a hash that fits 2k bits is written at the batch's end, behind this)
+            bool dup = false;
+            if (a.ignoreMultiKmer) {
+                uint32_t h[3], old[3];
+#pragma unroll
+                for (int j = 0; j < 3; j++) { h[j] = tag[j] & (UNI_TABLE - 1); old[j] = real[j] ? atomicCAS(&table[h[j]], 0u, tag[j]) : 0u; }
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    while (old[j] != 0u) {
+                        if (old[j] == tag[j]) { dup = true; break; }
+                        h[j] = (h[j] + 1) & (UNI_TABLE - 1);
+                        old[j] = atomicCAS(&table[h[j]], 0u, tag[j]);
+                    }
+            }
+            const unsigned long long dm = __ballot(dup);
+            const bool halfDup = (half ? (dm >> 32) : (dm & 0xFFFFFFFFull)) != 0ull;
+            if (halfDup && hl == 0) a.slowShort[atomicAdd(&a.slowCnt[0], 1u)] = seq;   // rewritten by k_extract
+            if (countHead && !halfDup) {        // (a sequence k_extract rewrites is counted there)
+#pragma unroll
+                for (int j = 0; j < 3; j++) if (real[j]) atomicAdd(&sHead[digit[j]], 1u);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // ---- the whole-sequence hash tuples of the batch's sequences (putSeqHashTuple for the whole k-mer space): lane l has sequence
+        // 2 pr0 + l and walks its words in LDS
+        const uint32_t seq = 2 * pr0 + (uint32_t) lane;
+        if ((uint32_t) (lane >> 1) < cnt && seq < n) {
+            uint64_t acc = 0;
+            for (uint32_t j = 0; j < W; j++) {
+                uint32_t word = words[(uint32_t) lane * W + j];
+                const uint32_t nb = min(16u, L - 16u * j);
+                for (uint32_t i = 0; i < nb; i++) { acc = (acc << 5) - acc + (word & 3u); word >>= 2; }      // h = h x 31 + c
+            }
+            const uint64_t hk = xxh64_u64(acc, a.seed);
+            const uint64_t hslot = a.hashBase + seq;
+            if ((hk & ~BIT63) < (1ull << (2 * k))) {            // (one sequence in 2^(63 - 2k): the tuple stays in slot 0)
+                __threadfence();                                 // behind the ~0 another lane of this wave put there
+                LY::storeHash(a.keys, a.vals, (uint64_t) seq * uniS, hk, seq, L, a.geom);
+                if (a.headHist) atomicAdd(&a.headHist[(hk & ~BIT63) >> a.headShift], 1ull);
+                LY::storeEmpty(a.keys, a.vals, hslot);
+            } else LY::storeHash(a.keys, a.vals, hslot, hk, seq, L, a.geom);
+        }
     }
     if (countHead) headHistFlush(sHead, a.headHist);
 }

@@ -251,16 +251,28 @@ template <typename LY> struct GkGeom {
     static_assert(WIN % 64 == 0 && FIRST % 64 == 0 && FIRST < WIN && OWN <= FIRST && WIN <= (1 << bucket::WV_IDX) && (MAXB == 64 || MAXB == 128 || MAXB == 256 || MAXB == 512), "grouping kernel geometry");
 };
 #ifndef CDM_GK_MINW
-#define CDM_GK_MINW 0      // waves per SIMD the register allocation of the grouping kernel leaves room for (scripts/build_variant.py sweeps it; 0: as many as its LDS lets run - 6 blocks of 4 waves per CU with (key, value) pairs in the window, 7 with slot tuples)
+#define CDM_GK_MINW 0      // waves per SIMD the register allocation of the grouping kernel leaves room for (scripts/build_variant.py sweeps it; 0: 6 with slot tuples - the 6 blocks of 4 waves per CU its LDS lets run -, no request with (key, value) pairs in the window)
 #endif
-template <typename LY> constexpr int gkMinWaves() { return CDM_GK_MINW ? CDM_GK_MINW : (LY::bySlot ? 7 : 1); }
+// LDS the kernel declares per block (a block of BK_NT threads is one wave per SIMD: blocks per CU = waves per SIMD)
+template <typename LY> constexpr size_t gkLdsBytes() {
+    return (size_t) bucket::BK_WAVES * ((size_t) GkGeom<LY>::WIN * 8 + (LY::bySlot ? 1 : (size_t) GkGeom<LY>::WIN) * sizeof(typename LY::V) + (size_t) GkGeom<LY>::MAXB * 4 + sizeof(bucket::WaveLdsT<GkGeom<LY>::WIN>) +
+                                      (LY::bySlot ? (size_t) REC_CAP : 1) * 12);
+}
+constexpr size_t CU_LDS_BYTES = 160 * 1024;
+// A request the LDS cannot meet is not approximated by the compiler but dropped ("failed to meet occupancy target"): the slot instance
+// asked for 7 with 26 KB of LDS per block, got an uncapped allocation of 83 registers and ran at 5.  Hence the assert next to the bound
+// (a sweep's CDM_GK_MINW reaches the other layouts' instances as far as their LDS goes).
+template <typename LY> constexpr int gkMinWaves() {
+    return LY::bySlot ? (CDM_GK_MINW ? CDM_GK_MINW : 6) : (CDM_GK_MINW ? (int) std::min<size_t>(CDM_GK_MINW, CU_LDS_BYTES / gkLdsBytes<LY>()) : 1);
+}
 template <typename LY, typename W>
 __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_groups(BucketGroupArgs<LY, W> a) {
+    static_assert(bucket::BK_NT == 256 && (size_t) gkMinWaves<LY>() * gkLdsBytes<LY>() <= CU_LDS_BYTES, "the launch bound asks for more blocks per CU than the kernel's LDS lets run: the compiler would drop the request");
     using namespace bucket;
     typedef typename LY::V V;
     constexpr int GK_WIN = GkGeom<LY>::WIN, GK_FIRST = GkGeom<LY>::FIRST, GK_MAXB = GkGeom<LY>::MAXB;
     __shared__ uint64_t sKeyAll[BK_WAVES][GK_WIN];
-    __shared__ V sValAll[BK_WAVES][GK_WIN];
+    __shared__ V sValAll[BK_WAVES][LY::bySlot ? 1 : GK_WIN];       // (slot tuples: no value array)
     __shared__ uint32_t sSAll[BK_WAVES][GK_MAXB];
     __shared__ WaveLdsT<GK_WIN> wAll[BK_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

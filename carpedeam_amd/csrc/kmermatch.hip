@@ -202,14 +202,39 @@ int phaseA() override {
         if (headRange) { ea.kLo = 0; ea.kHi = ~0ull; }      // (every k-mer: the head pass keeps the rank's range; the whole-sequence hash tuples stay the last rank's)
     }
     hipEventRecord(ctx->ev0, s);
-    hipLaunchKernelGGL(k_seq_hash<LY>, dim3((n + 255) / 256), dim3(256), 0, s, ea);
-    ea.single = listSingle.p; ea.listCount = nullptr;
-    if (k <= 30) {      // two short reads per wave; what does not fit comes back through the `single` list
-        hipLaunchKernelGGL(k_extract_pair<LY>, dim3(std::min<uint32_t>(((n + 1) / 2 + FAST_WAVES - 1) / FAST_WAVES, ctx->cuCount * 16)), dim3(64 * FAST_WAVES), 0, s, ea);
-        ea.list = listSingle.p; ea.listCount = cls.p + 2;
+    // A plain uniform DB (common.h MetaUniform: one length, stored back to back, no N) in the slot layout, every k-mer of every read on
+    // this device, reads short enough for a half-wave that takes all their k-mers: k_extract_uniform does the work of k_seq_hash and
+    // k_extract_pair.  CDM_EXTRACT=pair: those two for every DB (A/B, tests).
+    bool uniformKernel = false;
+    if constexpr (LY::bySlot) {
+        const char *e = cdmGetenv("CDM_EXTRACT");
+        const uint32_t L = db->maxLen, W = (L + 15) / 16, nPos = L - (uint32_t) k + 1u;
+        const size_t cap = (size_t) (float) ((float) (par->kmers_per_seq - 1) + (par->kmers_per_seq_scale * (float) L));
+        if (!(e && !strcmp(e, "pair")) && k <= 30 && ea.kLo == 0 && ea.kHi == ~0ull && ea.ordHi == 0 && ea.lastPart && nPos <= cap && nPos <= (uint32_t) PAIR_POS &&
+            db->nCount == 0 && !db->raw && (uint64_t) n * W < (1ull << 32)) {
+            unsigned int bad = 1;                  // (cls[6] is zero: the memset above)
+            hipLaunchKernelGGL(k_uniform_check, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t *) db->len, (const uint32_t *) db->woff, (const uint8_t *) db->hasN, n, L, W, cls.p + 6);
+            hipMemcpyAsync(&bad, cls.p + 6, 4, hipMemcpyDeviceToHost, s);
+            if (hipStreamSynchronize(s) != hipSuccess) { cdm_set_error("cdm_kmermatch: looking at the sequence lengths failed"); return CDM_ERR_HIP; }
+            uniformKernel = bad == 0;
+        }
+        if (uniformKernel) {
+            const uint32_t batches = ((n + 1) / 2 + UNI_BATCH - 1) / UNI_BATCH;
+            uint32_t blocks = std::min<uint32_t>((batches + FAST_WAVES - 1) / FAST_WAVES, ctx->cuCount * UNI_MINW);     // (every wave resident at once)
+            if (const char *eb = cdmGetenv("CDM_EXTRACT_BLOCKS")) blocks = std::max(1u, std::min<uint32_t>(blocks, (uint32_t) atoi(eb)));      // (tests: several batches per wave on a small DB)
+            hipLaunchKernelGGL(k_extract_uniform<LY>, dim3(blocks), dim3(64 * FAST_WAVES), 0, s, ea, L, W);
+        }
     }
-    hipLaunchKernelGGL(k_extract_fast<LY>, dim3(std::min<uint32_t>((n + FAST_WAVES - 1) / FAST_WAVES, ctx->cuCount * 16)), dim3(64 * FAST_WAVES), 0, s, ea);
-    ea.listCount = nullptr;
+    ea.single = listSingle.p; ea.listCount = nullptr;
+    if (!uniformKernel) {
+        hipLaunchKernelGGL(k_seq_hash<LY>, dim3((n + 255) / 256), dim3(256), 0, s, ea);
+        if (k <= 30) {      // two short reads per wave; what does not fit comes back through the `single` list
+            hipLaunchKernelGGL(k_extract_pair<LY>, dim3(std::min<uint32_t>(((n + 1) / 2 + FAST_WAVES - 1) / FAST_WAVES, ctx->cuCount * 16)), dim3(64 * FAST_WAVES), 0, s, ea);
+            ea.list = listSingle.p; ea.listCount = cls.p + 2;
+        }
+        hipLaunchKernelGGL(k_extract_fast<LY>, dim3(std::min<uint32_t>((n + FAST_WAVES - 1) / FAST_WAVES, ctx->cuCount * 16)), dim3(64 * FAST_WAVES), 0, s, ea);
+        ea.listCount = nullptr;
+    }
     unsigned int hcls[4] = {0, 0, 0, 0};
     hipMemcpyAsync(hcls, cls.p, 16, hipMemcpyDeviceToHost, s);
     { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_kmermatch: extraction failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
@@ -231,6 +256,7 @@ int phaseA() override {
     { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_kmermatch: extraction (general path) failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
     anyBelow = belowHost != 0;
     hipEventElapsedTime(&ctx->lastMs[3], ctx->ev0, ctx->ev1);
+    if (cdmGetenv("CDM_BUCKET_STATS")) fprintf(stderr, "kmermatch extraction (%s): %u sequences through k_extract for a repeated k-mer or a bottom-m selection, %u + %u longer ones\n", uniformKernel ? "uniform kernel" : "pair + fast kernels", hcls[0], hcls[1], hcls[3]);
     if (split) return splitPartition();
     if constexpr (LY::bySlot) if (headRange) {
         unsigned long long hh[HEAD_BINS];
