@@ -102,6 +102,22 @@ SITE_DTYPE = np.dtype([("query", "<u4"), ("pos", "<u4"), ("info", "<u4"), ("coun
 SITE_CALLED, SITE_DIFFERS, SITE_VARIABLE = 1, 2, 4
 
 
+class BreaksParams(C.Structure):
+    """cdm_breaks_params: columns a spanning read has on either side of a boundary, boundaries left out at either end of a query, the two
+    thresholds of a weak boundary, the records' identity threshold, reads only as targets"""
+    _fields_ = [("anchor", C.c_int32), ("edge", C.c_int32), ("min_span", C.c_int32), ("min_span_percent", C.c_int32),
+                ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
+class Break(C.Structure):
+    """cdm_break: one run of weak boundaries"""
+    _fields_ = [(n, C.c_uint32) for n in ("query", "first", "last", "min_span", "uncovered", "depth_left", "depth_right", "flags")]
+
+
+BREAK_DTYPE = np.dtype([(n, "<u4") for n in ("query", "first", "last", "min_span", "uncovered", "depth_left", "depth_right", "flags")])
+BREAK_JOIN, BREAK_GAP = 1, 2
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -113,7 +129,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -232,6 +248,9 @@ def lib():
         l.cdm_pileup_bases.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(BasesParams), vp, vp, C.POINTER(C.POINTER(Site)), u64p, C.POINTER(C.c_float)]
         l.cdm_sites_free.argtypes = [C.POINTER(Site)]
         l.cdm_sites_free.restype = None
+        l.cdm_pileup_breaks.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(BreaksParams), vp, vp, C.POINTER(C.POINTER(Break)), u64p, C.POINTER(C.c_float)]
+        l.cdm_breaks_free.argtypes = [C.POINTER(Break)]
+        l.cdm_breaks_free.restype = None
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -717,6 +736,41 @@ class Ctx:
             if n:
                 C.memmove(recs.ctypes.data, ptr, n * C.sizeof(Site))
                 lib().cdm_sites_free(ptr)
+            out.append(recs)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def pileup_breaks(self, db, alns, queries, anchor=16, edge=50, min_span=1, min_span_percent=0, min_seq_id=0.0, skip_extended_targets=False,
+                      track=False, breaks=False):
+        """break points of the listed queries (cdm_pileup_breaks) -> stats[nq, 8] uint64: reads, columns, window, weak, breaks, joins,
+        min_span, sum_span; with track also the span at every boundary b = 0 .. len - 1, a list of uint32 arrays, one per listed query;
+        with breaks also the break records as an array of BREAK_DTYPE.  The order of the extras in the returned tuple is track, breaks.
+        self.breaks_kernel_ms holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 8), np.uint64)
+        lens, span = None, None
+        if track:
+            if nq and int(q.max()) < db.n:         # (an index beyond the DB is the library's to refuse: nothing is written then)
+                lens = db.meta()[0][q].astype(np.int64)
+            else:
+                lens = np.zeros(nq, np.int64)
+            span = np.zeros(max(int(lens.sum()), 1), np.uint32)
+        par = BreaksParams(int(anchor), int(edge), int(min_span), int(min_span_percent), float(min_seq_id), int(bool(skip_extended_targets)))
+        ptr, n_breaks, ms = C.POINTER(Break)(), C.c_uint64(0), C.c_float(0.0)
+        _check(lib().cdm_pileup_breaks(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(span), C.byref(ptr) if breaks else None,
+                                       C.byref(n_breaks) if breaks else None, C.byref(ms)))
+        self.breaks_kernel_ms = float(ms.value)
+        out = [stats]
+        if track:
+            ends = np.cumsum(lens)
+            out.append([span[int(e - l):int(e)].copy() for l, e in zip(lens, ends)])
+        if breaks:
+            n = int(n_breaks.value)
+            assert (n == 0) == (not ptr)
+            recs = np.empty(n, BREAK_DTYPE)
+            if n:
+                C.memmove(recs.ctypes.data, ptr, n * C.sizeof(Break))
+                lib().cdm_breaks_free(ptr)
             out.append(recs)
         return out[0] if len(out) == 1 else tuple(out)
 

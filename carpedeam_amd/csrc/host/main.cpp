@@ -1478,14 +1478,106 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
     if (v.sites && !writeText(*v.sites, sitesText)) die("Could not write " + *v.sites);
     if (v.consensus && !writeText(*v.consensus, fasta)) die("Could not write " + *v.consensus);
 }
+// ---- contig_breaks: contig break points from spanning reads of the same pile-up (not a module of the reference).  The three calls
+// above, then cdm_pileup_breaks over the contigs: one summary line per contig and, behind it, one `#break` line per run of boundaries
+// that too few reads span with --break-anchor columns on either side (J: the reads cover the stretch and none spans it - the
+// signature of a chimeric join; G: a stretch without reads); with --split the contigs cut at their breaks, with --span-track the
+// spanning coverage of every boundary.  As with the other three reports the pile-up is seeded UNGAPPED overlaps at the identity
+// threshold: reads shorter than twice the anchor span nothing, and there is no break call where no read seeds.  Integers only.
+const FlagSpec BREAK_FLAGS[] = {{"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0}, {"--split", 'U', 0, 0},
+                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+struct BreakOpts { long anchor, edge, minSpan, minSpanPercent; };
+long rangedFlag(Args &a, const char *module, const char *flag, long dflt, long lo, long hi, const char *what) {
+    const long v = iflag(a, flag, dflt);
+    if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
+    return v;
+}
+// The default anchor is reasoned, not measured: a read with w columns beyond a false join expects 0.75 w mismatches there, and at the
+// identity threshold t a read of L columns is dropped when 0.75 w > (1 - t) L; w = 16 covers L <= 120 at t = 0.9.
+BreakOpts breakOpts(Args &a, const char *module) {
+    BreakOpts o;
+    o.anchor = rangedFlag(a, module, "--break-anchor", 16, 1, 1024, "a spanning read has 1 to 1024 columns on either side of a boundary");
+    o.edge = rangedFlag(a, module, "--break-edge", 50, 1, 1048576, "1 to 1048576 boundaries are left out at either end of a contig");
+    if (o.edge < o.anchor) unsupported(std::string(module) + ": --break-edge " + std::to_string(o.edge) + " is not supported by the MI355X path (it is --break-anchor, here " + std::to_string(o.anchor) +
+                                       ", at the least: nearer to a contig's end no read has its anchor on both sides)");
+    o.minSpan = rangedFlag(a, module, "--min-span", 1, 1, 1000000, "a boundary is held by 1 to 1000000 spanning reads");
+    o.minSpanPercent = rangedFlag(a, module, "--min-span-percent", 0, 0, 100, "a percentage of the depth is 0 to 100");
+    return o;
+}
+// what a break report writes: the summary always, the other two files when named
+struct BreakOut { BreakOpts opt; long minPiece; const std::string *summary, *split, *track; };
+// no contigs: the summary's header line alone, an empty FASTA, an empty track
+void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const BreakOut &o, Laps &laps) {
+    std::string text = "name\tkey\tlength\treads\tcolumns\twindow\tweak\tbreaks\tjoins\tmin_span\tsum_span\n", fasta, bed;
+    if (haveContigs(contigs)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        std::vector<uint32_t> q(nc), lens(nc), track;
+        std::iota(q.begin(), q.end(), 0u);
+        std::vector<uint64_t> stats(nc * 8);
+        if (o.track) track.assign(cdm_seqdb_residues(contigs->db) + 1, 0);
+        cdm_breaks_params bp; bp.anchor = (int32_t) o.opt.anchor; bp.edge = (int32_t) o.opt.edge; bp.min_span = (int32_t) o.opt.minSpan; bp.min_span_percent = (int32_t) o.opt.minSpanPercent;
+        bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
+        cdm_break *br = NULL; uint64_t nBr = 0; float ms = 0.f;
+        check(cdm_pileup_breaks(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu breaks, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nBr, ms);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        char num[32]; std::string tmp;
+        auto put = [&](std::string &to, unsigned long long x) { to.push_back('\t'); to.append(num, (size_t) (utoa(x, num) - num)); };
+        std::vector<uint64_t> at(nc + 1, 0);
+        std::string letters;
+        if (o.split) {          // the contigs' own bytes (raw plane included)
+            for (uint64_t i = 0; i < nc; i++) at[i + 1] = at[i] + lens[i] + 1ull;
+            letters.assign(at[nc], '\0');
+            check(cdm_seqdb_download(ctx, contigs->db, &letters[0], at.data()), "download of the contigs");
+        }
+        uint64_t k = 0, trackAt = 0;
+        for (uint64_t i = 0; i < nc; trackAt += lens[i], i++) {
+            const std::string &name = contigName(*contigs, i, tmp);
+            text += name;
+            put(text, contigs->keys[i]); put(text, lens[i]);
+            for (int c = 0; c < 8; c++) put(text, stats[i * 8 + c]);
+            text.push_back('\n');
+            const uint64_t k0 = k;
+            for (; k < nBr && br[k].query == i; k++) {      // 1-based boundaries
+                const cdm_break &b = br[k];
+                text += "#break\t"; text += name;
+                put(text, (unsigned long long) b.first + 1); put(text, (unsigned long long) b.last + 1); put(text, b.min_span); put(text, b.uncovered); put(text, b.depth_left); put(text, b.depth_right);
+                text.push_back('\t'); text.push_back(b.flags & CDM_BREAK_GAP ? 'G' : 'J'); text.push_back('\n');
+            }
+            if (o.split) {      // a piece ends at position first - 1, the next begins at position last: the letters between, which no read spans, are dropped
+                uint64_t from = 0, piece = 0;
+                for (uint64_t j = k0; j <= k; j++) {
+                    const uint64_t to = j < k ? br[j].first : lens[i];
+                    piece++;
+                    if (to - from >= (uint64_t) o.minPiece) {
+                        fasta.push_back('>'); fasta += name;
+                        if (k > k0) { fasta.push_back('_'); fasta += std::to_string(piece); }
+                        fasta.push_back('\n'); fasta.append(letters, at[i] + from, to - from); fasta.push_back('\n');
+                    }
+                    if (j < k) from = br[j].last;
+                }
+            }
+            if (o.track) {      // bedGraph of the runs of equal span: name, start, end (0-based, half-open), span
+                const uint32_t *d = track.data() + trackAt;
+                for (uint32_t start = 0, p = 1; p <= lens[i]; p++)
+                    if (p == lens[i] || d[p] != d[start]) { bed += name; put(bed, start); put(bed, p); put(bed, d[start]); bed.push_back('\n'); start = p; }
+            }
+        }
+        cdm_breaks_free(br);
+        laps.lap("break report: break points, tables");
+    }
+    if (!writeText(*o.summary, text)) die("Could not write " + *o.summary);
+    if (o.split && !writeText(*o.split, fasta)) die("Could not write " + *o.split);
+    if (o.track && !writeText(*o.track, bed)) die("Could not write " + *o.track);
+}
 // The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
-// alignment set.  damageOut / depthOut / variants: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
+// alignment set.  damageOut / depthOut / variants / breaks: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
 void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const std::string *damageOut, long ends, const std::string *depthOut, long edge,
-                 const std::string *trackOut, const VariantOut *variants, Laps &laps) {
+                 const std::string *trackOut, const VariantOut *variants, const BreakOut *breaks, Laps &laps) {
     PileSet ps;
     if (haveContigs(contigs)) {
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
-        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : depthOut ? "depth report: kmermatcher, rescorediagonal" : "variant report: kmermatcher, rescorediagonal");
+        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : depthOut ? "depth report: kmermatcher, rescorediagonal" : variants ? "variant report: kmermatcher, rescorediagonal" : "break report: kmermatcher, rescorediagonal");
     }
     if (damageOut) damageTable(ctx, contigs, ps, ends, *damageOut, laps);
     if (depthOut) {
@@ -1496,6 +1588,7 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
         laps.lap("depth report: depth, table");
     }
     if (variants) variantReport(ctx, contigs, ps, *variants, laps);
+    if (breaks) breakReport(ctx, contigs, ps, *breaks, laps);
     freePileSet(ps);
 }
 int contigDamage(Args &a) {
@@ -1508,7 +1601,7 @@ int contigDamage(Args &a) {
     const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
     if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
     laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, NULL, laps);
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, NULL, NULL, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
     if (reads.db) cdm_seqdb_free(reads.db);
     cdm_ctx_destroy(ctx);
@@ -1557,7 +1650,27 @@ int contigVariants(Args &a) {
     const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
     if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_variants: " + a.pos[1] + " holds no reads");
     laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, &v, laps);
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, &v, NULL, laps);
+    if (contigs.db) cdm_seqdb_free(contigs.db);
+    if (reads.db) cdm_seqdb_free(reads.db);
+    cdm_ctx_destroy(ctx);
+    return EXIT_SUCCESS;
+}
+int contigBreaks(Args &a) {
+    if (a.pos.size() != 3) die("Usage: carpedeam contig_breaks <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--break-anchor 16] [--break-edge 50] [--min-span 1] [--min-span-percent 0] "
+                               "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--min-seq-id 0.9] [-k 20]");
+    checkFlags("contig_breaks", a, BREAK_FLAGS);
+    BreakOut o;
+    o.opt = breakOpts(a, "contig_breaks");
+    o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
+    o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
+    Laps laps;
+    cdm_ctx *ctx = openCtx();
+    DamageInput contigs, reads;
+    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
+    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_breaks: " + a.pos[1] + " holds no reads");
+    laps.lap("inputs read, sequences up");
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, NULL, &o, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
     if (reads.db) cdm_seqdb_free(reads.db);
     cdm_ctx_destroy(ctx);
@@ -1765,6 +1878,7 @@ const FlagSpec FUSED_FLAGS[] = {
     // the tail's
     {"--damage-report", 'U', 0, 0}, {"--damage-ends", 'U', 0, 0}, {"--depth-report", 'U', 0, 0}, {"--depth-edge", 'U', 0, 0},
     {"--variant-report", 'U', 0, 0}, {"--variant-sites", 'U', 0, 0}, {"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0},
+    {"--break-report", 'U', 0, 0}, {"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0},
     {"--min-contig-len", 'U', 0, 0}, {"--clust-min-seq-id", 'U', 0, 0}, {"--clust-min-cov", 'U', 0, 0}, {"--zdrop", 'U', 0, 0}, {"--threads", 'U', 0, 0}, {"--remove-tmp-files", 'U', 0, 0},
     {"-v", 'U', 0, 0},
     {"--cluster-mode", 'V', "2", "the redundancy reduction clusters greedily, linclust's mode for --cov-mode 1"}, {"--cov-mode", 'V', "1", "the workflow's coverage mode throughout"},
@@ -1886,7 +2000,15 @@ int assembleFused(Args &a) {
     variantOut.opt = variantOpts(a, "ancient_assemble_fused");
     variantOut.summary = &variantFile; variantOut.sites = variantSites.empty() ? NULL : &variantSites; variantOut.consensus = NULL;
     const VariantOut *const variants = variantRep ? &variantOut : NULL;
-    const bool anyReport = report || depthRep || variantRep;
+    // --break-report <file>: likewise contig_breaks' summary and break records of the final representatives (no split FASTA: that would
+    // be a second assembly output)
+    const bool breakRep = a.flag.count("--break-report") != 0;
+    const std::string breakFile = breakRep ? a.flag["--break-report"] : "";
+    BreakOut breakOut;
+    breakOut.opt = breakOpts(a, "ancient_assemble_fused");
+    breakOut.minPiece = 1; breakOut.summary = &breakFile; breakOut.split = NULL; breakOut.track = NULL;
+    const BreakOut *const breakPts = breakRep ? &breakOut : NULL;
+    const bool anyReport = report || depthRep || variantRep || breakRep;
     // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
     if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
     if (const char *dry = getenv("CDM_FUSED_DRY_RUN")) {        // "cycle": the tail as it runs with circular contigs among the selection
@@ -1933,7 +2055,7 @@ int assembleFused(Args &a) {
         // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
         cdm_seqdb_free(selected);
         if (!writeText(outFile, "")) die("Could not write " + outFile);
-        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, laps); cdm_seqdb_free(E.reads); }
+        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, breakPts, laps); cdm_seqdb_free(E.reads); }
         cdm_ctx_destroy(ctx);
         if (removeTmp) removeOwnDir(T);
         return EXIT_SUCCESS;
@@ -2024,7 +2146,7 @@ int assembleFused(Args &a) {
     if (anyReport) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
         DamageInput contigs;
         const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
-        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, laps);
+        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, breakPts, laps);
         if (contigs.db) cdm_seqdb_free(contigs.db);
         cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);
     }
@@ -2054,7 +2176,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|contig_breaks|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -2075,6 +2197,7 @@ int main(int argc, char **argv) {
     else if (cmd == "contig_damage") rc = contigDamage(a);
     else if (cmd == "contig_depth") rc = contigDepth(a);
     else if (cmd == "contig_variants") rc = contigVariants(a);
+    else if (cmd == "contig_breaks") rc = contigBreaks(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

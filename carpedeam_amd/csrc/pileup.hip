@@ -1,6 +1,7 @@
 // Per-query coverage and damage tables of the read pile-up (cdm_pileup_profile), the depth at every position of a query with its
-// statistics (cdm_pileup_depth, the second part of this file) and the per-position base counts with the variant sites
-// (cdm_pileup_bases, the third); none is a module of the reference.
+// statistics (cdm_pileup_depth, the second part of this file), the per-position base counts with the variant sites
+// (cdm_pileup_bases, the third) and the contig break points from spanning reads (cdm_pileup_breaks, the fourth); none is a module of
+// the reference.
 //
 // ancient_correction orients every record of a query and piles the targets up column by column (correct.hip: orient(), targetBase());
 // this unit walks the same columns and COUNTS: for the first and the last `ends` positions of every read, which query base stands
@@ -176,12 +177,12 @@ __device__ __forceinline__ unsigned long long waveSum64(unsigned long long v) {
     return v;
 }
 
-// marks: one wave per item (listed query, chunk of its records) of this launch's slice, lanes take records
-__global__ __launch_bounds__(64 * PU_WAVES) void k_depth_marks(DepthArgs a, uint64_t first, uint64_t nThis) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
-    if (local >= nThis) return;
-    const uint64_t item = first + local;
+// The marks of one item (listed query, chunk of its records) by one wave, lanes take records: +1 at qs and -1 behind qe in the depth
+// cells; with SPAN (cdm_pileup_breaks, the fourth part of this file) also +1 at qs + w and -1 at qe + 2 - w in a second plane of the same
+// layout `plane` cells behind the first, for the records of at least 2 w columns.  reads and columns go to the query's stats row, once
+// per item.
+template <bool SPAN>
+__device__ __forceinline__ void depthMarkItem(const DepthArgs &a, uint64_t item, int lane, uint32_t w, uint64_t plane) {
     uint32_t lo = 0, hi = a.nq;
     while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.itemOff[mid] <= item) lo = mid; else hi = mid; }
     const uint32_t qi = lo, q = a.queries[qi];
@@ -193,13 +194,26 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_depth_marks(DepthArgs a, uint
         const AlnRec rec = a.rec[r];
         Oriented o; uint32_t tLen, tw;
         if (!countedRecord(a.meta, a.n, a.skipExt, a.minSeqId, q, qLen, rec, o, tLen, tw)) continue;
-        nReads++; nCols += (uint32_t) (o.qe - o.qs) + 1u;
+        const uint32_t L = (uint32_t) (o.qe - o.qs) + 1u;
+        nReads++; nCols += L;
         atomicAdd(&cell[(uint32_t) o.qs], 1u);                        // (results unused: atomics without return)
         atomicAdd(&cell[(uint32_t) o.qe + 1u], 0xFFFFFFFFu);          // qe < qLen: at the most the query's closing cell
+        if (SPAN && L >= 2u * w) {                                    // qs + w <= qe + 1 - w < qe + 2 - w <= qLen (w >= 1): inside the query's cells
+            atomicAdd(&cell[plane + (uint32_t) o.qs + w], 1u);
+            atomicAdd(&cell[plane + (uint32_t) o.qe + 2u - w], 0xFFFFFFFFu);
+        }
     }
     const unsigned int rd = (unsigned int) cdm_wave_sum((int) nReads);
     const unsigned long long cl = waveSum64(nCols);
     if (lane == 0 && rd) { atomicAdd(&a.stats[(uint64_t) qi * 8], (unsigned long long) rd); atomicAdd(&a.stats[(uint64_t) qi * 8 + 1], cl); }
+}
+
+// marks: one wave per item of this launch's slice
+__global__ __launch_bounds__(64 * PU_WAVES) void k_depth_marks(DepthArgs a, uint64_t first, uint64_t nThis) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
+    if (local >= nThis) return;
+    depthMarkItem<false>(a, first + local, lane, 0u, 0ull);
 }
 
 // statistics: one block per item (listed query, tile of DP_TILE positions) of this launch's slice, on the scanned cells:
@@ -405,6 +419,144 @@ __global__ __launch_bounds__(DP_NT) void k_base_emit(BasesArgs a, uint64_t first
 #pragma unroll
         for (int k = 0; k < 8; k++) out->counts[k] = c[k];
     }
+}
+
+// ---------------------------------------------------------------------------------------------- cdm_pileup_breaks
+// Contig break points (include/carpedeam_hip.h): how many counted records SPAN every boundary b of the listed queries with at least
+// `anchor` columns on either side, and the runs of boundaries where too few do.  The marks are depth's, in two planes of len + 1 cells
+// per listed query laid end to end (depthMarkItem<true>): both planes sum to zero per query, so ONE prefix sum over the 2 x N cells
+// turns them into depth[i] and span[i], each at cell i + 1 of its plane.  A tile kernel classifies the boundaries, reduces the query's
+// figures and writes a 0/1 word where a run of weak boundaries starts; a prefix sum over those words numbers the runs, and an emission
+// kernel fills one record per run.  A run never leaves its query, and a batch holds whole queries.
+constexpr int BK_MAX_ANCHOR = 1024, BK_MAX_EDGE = 1048576, BK_MAX_SPAN = 1000000;
+
+struct BreakArgs {
+    DepthArgs d;                    // edge: the window's; stats: [nq][8]; track: NULL, or the spans without the closing cells
+    uint64_t plane;                 // N = base[nq]: the span plane lies N cells behind the depth plane
+    uint32_t anchor, minSpan, minPct, firstQuery;
+    uint32_t *place;                // [N + 1], laid out as a plane: 0/1 per run start, after the scan the number of run starts in front
+    cdm_break *out;                 // k_break_init, k_break_emit, k_break_flags: [nRuns]
+    uint32_t nRuns;
+};
+
+// marks: one wave per item (listed query, chunk of its records) of this launch's slice, into both planes
+__global__ __launch_bounds__(64 * PU_WAVES) void k_break_marks(BreakArgs a, uint64_t first, uint64_t nThis) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
+    if (local >= nThis) return;
+    depthMarkItem<true>(a.d, first + local, lane, a.anchor, a.plane);
+}
+
+// the item (listed query, tile of DP_TILE boundaries) of a block: the query's scanned cells, depth[i] = dep[i] and span[i] = spn[i]
+struct BreakTile { uint32_t qi, len; uint64_t cb, p0; const uint32_t *dep, *spn; };
+__device__ __forceinline__ BreakTile breakTile(const BreakArgs &a, uint64_t item) {
+    uint32_t lo = 0, hi = a.d.nq;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a.d.tileOff[mid] <= item) lo = mid; else hi = mid; }
+    BreakTile t;
+    t.qi = lo; t.len = a.d.meta[a.d.queries[lo]].len; t.cb = a.d.base[lo]; t.p0 = (item - a.d.tileOff[lo]) * DP_TILE;
+    t.dep = a.d.cells + t.cb + 1; t.spn = t.dep + a.plane;
+    return t;
+}
+// boundary b lies in the window: edge <= b <= len - edge (edge >= 1: never b = 0; nothing when len < 2 x edge)
+__device__ __forceinline__ bool breakWindow(const BreakArgs &a, const BreakTile &t, uint64_t b) { return b >= a.d.edge && b + a.d.edge <= t.len; }
+// a window boundary with span s is weak
+__device__ __forceinline__ bool breakWeakSpan(const BreakArgs &a, const BreakTile &t, uint32_t b, uint32_t s) {
+    if (s < a.minSpan) return true;
+    return a.minPct && (unsigned long long) s * 100ull < (unsigned long long) a.minPct * min(t.dep[b - 1], t.dep[b]);
+}
+__device__ __forceinline__ bool breakWeak(const BreakArgs &a, const BreakTile &t, uint64_t b) { return breakWindow(a, t, b) && breakWeakSpan(a, t, (uint32_t) b, t.spn[b]); }
+
+// classification: one block per item of this launch's slice
+__global__ __launch_bounds__(DP_NT) void k_break_classify(BreakArgs a, uint64_t first) {
+    __shared__ unsigned long long sRed[DP_NT / 64][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const BreakTile t = breakTile(a, first + blockIdx.x);
+    uint32_t *__restrict__ track = a.d.track ? a.d.track + (t.cb - t.qi) : nullptr;
+    unsigned long long sum = 0, three = 0;       // three: window, weak, run starts in 16 bits each (at most DP_TILE)
+    uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < DP_PER; j++) {
+        const uint64_t b = t.p0 + threadIdx.x + (uint64_t) DP_NT * j;
+        if (b >= t.len) continue;
+        const uint32_t s = t.spn[b];
+        if (track) track[b] = s;
+        bool start = false;
+        if (breakWindow(a, t, b)) {
+            const bool weak = breakWeakSpan(a, t, (uint32_t) b, s);
+            start = weak && !breakWeak(a, t, b - 1);
+            sum += s; mn = min(mn, s);
+            three += 1ull | (unsigned long long) weak << 16 | (unsigned long long) start << 32;
+        }
+        if (a.place) a.place[t.cb + b] = start;
+    }
+    sum = waveSum64(sum); three = waveSum64(three);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t) __shfl_xor((int) mn, o, 64));
+    if (lane == 0) { sRed[wave][0] = sum; sRed[wave][1] = three; sRed[wave][2] = mn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long r[2] = {0, 0}, m = 0xFFFFFFFFull;
+        for (int w = 0; w < DP_NT / 64; w++) { r[0] += sRed[w][0]; r[1] += sRed[w][1]; m = min(m, sRed[w][2]); }
+        unsigned long long *row = a.d.stats + (uint64_t) t.qi * 8;
+        if (r[1] & 0xFFFFull) {
+            atomicAdd(&row[2], r[1] & 0xFFFFull); atomicMin(&row[6], m);
+            if (r[0]) atomicAdd(&row[7], r[0]);
+            if ((r[1] >> 16) & 0xFFFFull) atomicAdd(&row[3], (r[1] >> 16) & 0xFFFFull);
+            if ((r[1] >> 32) & 0xFFFFull) atomicAdd(&row[4], (r[1] >> 32) & 0xFFFFull);
+        }
+    }
+}
+
+// the records before emission: nothing uncovered, the largest span
+__global__ void k_break_init(BreakArgs a) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.nRuns) return;
+    cdm_break b = {0u, 0u, 0u, 0xFFFFFFFFu, 0u, 0u, 0u, 0u};
+    a.out[r] = b;
+}
+
+// emission: the same items on the scanned run starts.  The run of a weak boundary b is the number of run starts up to b, minus 1.
+__global__ __launch_bounds__(DP_NT) void k_break_emit(BreakArgs a, uint64_t first) {
+    const int lane = threadIdx.x & 63;
+    const BreakTile t = breakTile(a, first + blockIdx.x);
+#pragma unroll
+    for (int j = 0; j < DP_PER; j++) {              // (wave-uniform: the ballots and shuffles below see all 64 lanes)
+        const uint64_t b = t.p0 + threadIdx.x + (uint64_t) DP_NT * j;
+        uint32_t s = 0, run = 0;
+        bool weak = false, more = false;
+        if (b < t.len && breakWindow(a, t, b)) { s = t.spn[b]; weak = breakWeakSpan(a, t, (uint32_t) b, s); }
+        if (weak) {
+            const uint32_t upTo = a.place[t.cb + b + 1];              // (b + 1 <= len: at the most the query's closing word)
+            run = upTo - 1u;
+            more = breakWeak(a, t, b + 1);
+            cdm_break *out = a.out + run;
+            if (a.place[t.cb + b] != upTo) { out->query = a.firstQuery + t.qi; out->first = (uint32_t) b; out->depth_left = t.dep[b - 1]; }
+            if (!more) { out->last = (uint32_t) b; out->depth_right = t.dep[b]; }
+        }
+        const uint32_t hole = weak && more && t.dep[b] == 0u;         // position b of first .. last - 1 without a read
+        const unsigned long long live = __ballot(weak);
+        if (!live) continue;
+        const uint32_t run0 = (uint32_t) __shfl((int) run, __ffsll((long long) live) - 1, 64);
+        if (!__ballot(weak && run != run0)) {       // the wave's weak lanes share a run (a long gap): one atomic of each kind
+            uint32_t mn = weak ? s : 0xFFFFFFFFu;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t) __shfl_xor((int) mn, o, 64));
+            const uint32_t holes = (uint32_t) cdm_wave_sum((int) hole);
+            if (lane == 0) { atomicMin(&a.out[run0].min_span, mn); if (holes) atomicAdd(&a.out[run0].uncovered, holes); }
+        } else if (weak) {
+            atomicMin(&a.out[run].min_span, s);
+            if (hole) atomicAdd(&a.out[run].uncovered, 1u);
+        }
+    }
+}
+
+// the last pass: gap or join, and the query's number of joins
+__global__ void k_break_flags(BreakArgs a) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.nRuns) return;
+    const bool gap = a.out[r].uncovered != 0u;
+    a.out[r].flags = gap ? CDM_BREAK_GAP : CDM_BREAK_JOIN;
+    if (!gap) atomicAdd(&a.d.stats[(uint64_t) (a.out[r].query - a.firstQuery) * 8 + 5], 1ull);
 }
 
 }  // namespace
@@ -629,6 +781,106 @@ static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
     return CDM_OK;
 }
 
+static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_breaks_params *par, uint64_t *stats, uint32_t *track,
+                           cdm_break **breaks, uint64_t *nBreaksOut, float *kernelMs) {
+    hipStream_t s = ctx->stream;
+    const uint32_t chunk = pileupChunk();
+    const uint64_t bound = depthCells();
+    DevBuf<SeqMeta> meta;
+    if (int rc = cdm_build_meta(ctx, db, &meta.p)) return rc;
+    DevBuf<uint32_t> dq, dLen; DevBuf<uint64_t> dRecs;
+    if (!dq.alloc(nq) || !dLen.alloc(nq) || !dRecs.alloc(nq)) { cdm_set_error("cdm_pileup_breaks: out of device memory for %llu queries", (unsigned long long) nq); return CDM_ERR_HIP; }
+    std::vector<uint32_t> len(nq); std::vector<uint64_t> recs(nq);
+    CDM_HIP(hipMemcpyAsync(dq.p, queries, (size_t) nq * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_depth_sizes, CDM_GRID((nq + 255) / 256, 256), dim3(256), 0, s, (const SeqMeta *) meta.p, (const uint64_t *) alns->off, (const uint32_t *) dq.p, nq, dLen.p, dRecs.p);
+    CDM_LAUNCH_CHECK();
+    CDM_HIP(hipMemcpyAsync(len.data(), dLen.p, (size_t) nq * 4, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipMemcpyAsync(recs.data(), dRecs.p, (size_t) nq * 8, hipMemcpyDeviceToHost, s));
+    CDM_HIP(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < nq; i++)
+        if (recs[i] >> 32) { cdm_set_error("cdm_pileup_breaks: query %u has %llu records; the 32-bit cells hold fewer than 2^32", queries[i], (unsigned long long) recs[i]); return CDM_ERR_UNSUPPORTED; }
+    float msTotal = 0.f;
+    uint64_t trackAt = 0;
+    for (uint64_t b0 = 0; b0 < nq;) {
+        // the batch: listed queries while the cells of their two planes stay within the bound; a single longer query goes alone
+        uint32_t m = 0; uint64_t N = 0;
+        while (b0 + m < nq && m < (1u << 30) && (m == 0 || 2ull * (N + len[b0 + m] + 1ull) <= bound)) { N += len[b0 + m] + 1ull; m++; }
+        std::vector<uint64_t> base((size_t) m + 1), tileOff((size_t) m + 1), init((size_t) m * 8, 0);
+        base[0] = tileOff[0] = 0;
+        for (uint32_t i = 0; i < m; i++) { base[i + 1] = base[i] + len[b0 + i] + 1ull; tileOff[i + 1] = tileOff[i] + ((uint64_t) len[b0 + i] + DP_TILE - 1) / DP_TILE; init[(size_t) i * 8 + 6] = ~0ull; }
+        const uint64_t nTiles = tileOff[m], nTrack = N - m;
+        DevBuf<uint64_t> items, itemOff, dBase, dTile; DevBuf<uint32_t> cells, dTrack, place; DevBuf<unsigned long long> dStats; DevBuf<cdm_break> dBreaks;
+        if (!items.alloc((size_t) m + 1) || !itemOff.alloc((size_t) m + 1) || !dBase.alloc((size_t) m + 1) || !dTile.alloc((size_t) m + 1) || !cells.alloc((size_t) N * 2) || !place.alloc((size_t) N + 1) ||
+            !dStats.alloc((size_t) m * 8) || (track && !dTrack.alloc(nTrack))) {
+            cdm_set_error("cdm_pileup_breaks: out of device memory for the %llu cells of %u queries", (unsigned long long) N * 2, m); return CDM_ERR_HIP;
+        }
+        CDM_HIP(hipMemcpyAsync(dBase.p, base.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemcpyAsync(dTile.p, tileOff.data(), ((size_t) m + 1) * 8, hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemcpyAsync(dStats.p, init.data(), (size_t) m * 64, hipMemcpyHostToDevice, s));        // (zeros; min_span all ones)
+        CDM_HIP(hipMemsetAsync(cells.p, 0, (size_t) N * 8, s));
+        CDM_HIP(hipMemsetAsync(place.p, 0, ((size_t) N + 1) * 4, s));       // (the closing words stay 0; the scan leaves the batch's number of runs in the last)
+        hipLaunchKernelGGL(k_pileup_chunks, dim3((m + 256) / 256), dim3(256), 0, s, (const uint64_t *) alns->off, (const uint32_t *) (dq.p + b0), m, chunk, items.p);
+        cdmscan::ScanTemp st, stCells, stPlace;
+        if (int rc = cdmscan::exclusiveScan<uint64_t>(s, st, items.p, itemOff.p, (size_t) m + 1)) return rc;
+        uint64_t nItems = 0;
+        CDM_HIP(hipMemcpyAsync(&nItems, itemOff.p + m, 8, hipMemcpyDeviceToHost, s));
+        CDM_HIP(hipStreamSynchronize(s));
+        BreakArgs a;
+        a.d.meta = meta.p; a.d.aoff = alns->off; a.d.rec = alns->rec; a.d.queries = dq.p + b0; a.d.itemOff = itemOff.p; a.d.tileOff = dTile.p; a.d.base = dBase.p;
+        a.d.n = (uint32_t) db->n; a.d.nq = m; a.d.chunk = chunk; a.d.skipExt = par->skip_extended_targets ? 1u : 0u; a.d.edge = (uint32_t) par->edge; a.d.minSeqId = par->min_seq_id;
+        a.d.cells = cells.p; a.d.stats = dStats.p; a.d.track = track ? dTrack.p : nullptr;
+        a.plane = N; a.anchor = (uint32_t) par->anchor; a.minSpan = (uint32_t) par->min_span; a.minPct = (uint32_t) par->min_span_percent; a.firstQuery = (uint32_t) b0;
+        a.place = place.p; a.out = nullptr; a.nRuns = 0;
+        hipEventRecord(ctx->ev0, s);
+        for (uint64_t first = 0, slice = cdmSliceItems(64); first < nItems; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nItems - first);
+            hipLaunchKernelGGL(k_break_marks, CDM_GRID((nThis + PU_WAVES - 1) / PU_WAVES, 64 * PU_WAVES), dim3(64 * PU_WAVES), 0, s, a, first, nThis);
+        }
+        if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stCells, cells.p, cells.p, (size_t) N * 2)) return rc;      // (in place: scan.h; both planes, each summing to zero)
+        for (uint64_t first = 0, slice = cdmSliceItems(DP_NT); first < nTiles; first += slice) {
+            const uint64_t nThis = std::min<uint64_t>(slice, nTiles - first);
+            hipLaunchKernelGGL(k_break_classify, CDM_GRID(nThis, DP_NT), dim3(DP_NT), 0, s, a, first);
+        }
+        // The runs are numbered whether or not the caller takes the records: `joins` needs every run's `uncovered`.
+        uint32_t nRuns = 0;
+        if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stPlace, place.p, place.p, (size_t) N + 1)) return rc;
+        CDM_HIP(hipMemcpyAsync(&nRuns, place.p + N, 4, hipMemcpyDeviceToHost, s));
+        hipEventRecord(ctx->ev1, s);
+        CDM_LAUNCH_CHECK();
+        { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_pileup_breaks: the kernels failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) msTotal += ms;
+        if (nRuns) {
+            if (!dBreaks.alloc(nRuns)) { cdm_set_error("cdm_pileup_breaks: out of device memory for %u break records", nRuns); return CDM_ERR_HIP; }
+            a.out = dBreaks.p; a.nRuns = nRuns;
+            hipEventRecord(ctx->ev0, s);
+            hipLaunchKernelGGL(k_break_init, CDM_GRID(((uint64_t) nRuns + 255) / 256, 256), dim3(256), 0, s, a);
+            for (uint64_t first = 0, slice = cdmSliceItems(DP_NT); first < nTiles; first += slice) {
+                const uint64_t nThis = std::min<uint64_t>(slice, nTiles - first);
+                hipLaunchKernelGGL(k_break_emit, CDM_GRID(nThis, DP_NT), dim3(DP_NT), 0, s, a, first);
+            }
+            hipLaunchKernelGGL(k_break_flags, CDM_GRID(((uint64_t) nRuns + 255) / 256, 256), dim3(256), 0, s, a);
+            hipEventRecord(ctx->ev1, s);
+            CDM_LAUNCH_CHECK();
+            if (breaks) {       // the records of this batch behind those of the batches before it
+                cdm_break *grown = (cdm_break *) realloc(*breaks, (size_t) (*nBreaksOut + nRuns) * sizeof(cdm_break));
+                if (!grown) { cdm_set_error("cdm_pileup_breaks: out of host memory for %llu break records", (unsigned long long) (*nBreaksOut + nRuns)); return CDM_ERR_INVALID; }
+                *breaks = grown;
+                CDM_HIP(hipMemcpyAsync(grown + *nBreaksOut, dBreaks.p, (size_t) nRuns * sizeof(cdm_break), hipMemcpyDeviceToHost, s));
+                *nBreaksOut += nRuns;
+            }
+        }
+        CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
+        if (track && nTrack) CDM_HIP(hipMemcpyAsync(track + trackAt, dTrack.p, (size_t) nTrack * 4, hipMemcpyDeviceToHost, s));
+        { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("cdm_pileup_breaks: the emission failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
+        if (nRuns && hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) msTotal += ms;
+        for (uint32_t i = 0; i < m; i++) { uint64_t *row = stats + (b0 + i) * 8; if (row[2] == 0) row[6] = 0; }       // (an empty window has no smallest span)
+        trackAt += nTrack; b0 += m;
+    }
+    if (kernelMs) *kernelMs = msTotal;
+    return CDM_OK;
+}
+
 // the argument checks the entry points share
 static int pileupCheckArgs(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries) {
     if (alns->n != db->n) { cdm_set_error("%s: alignment CSR has %llu queries, DB has %llu", who, (unsigned long long) alns->n, (unsigned long long) db->n); return CDM_ERR_INVALID; }
@@ -673,6 +925,28 @@ extern "C" int cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_aln
 }
 
 extern "C" void cdm_sites_free(cdm_site *sites) { free(sites); }
+
+extern "C" int cdm_pileup_breaks(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_breaks_params *par,
+                                 uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *n_breaks, float *kernel_ms) {
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_breaks");
+    if (!ctx || !db || !alns || !par || (breaks && !n_breaks) || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_breaks: NULL argument"); return CDM_ERR_INVALID; }
+    if (par->anchor < 1 || par->anchor > BK_MAX_ANCHOR) { cdm_set_error("cdm_pileup_breaks: anchor = %d; a spanning read has 1 to %d columns on either side of a boundary", par->anchor, BK_MAX_ANCHOR); return CDM_ERR_INVALID; }
+    if (par->edge < par->anchor || par->edge > BK_MAX_EDGE) { cdm_set_error("cdm_pileup_breaks: edge = %d; anchor (%d) to %d boundaries are left out at either end of a query", par->edge, par->anchor, BK_MAX_EDGE); return CDM_ERR_INVALID; }
+    if (par->min_span < 1 || par->min_span > BK_MAX_SPAN) { cdm_set_error("cdm_pileup_breaks: min_span = %d; a boundary is held by 1 to %d spanning reads", par->min_span, BK_MAX_SPAN); return CDM_ERR_INVALID; }
+    if (par->min_span_percent < 0 || par->min_span_percent > 100) { cdm_set_error("cdm_pileup_breaks: min_span_percent = %d; a percentage of the depth is 0 to 100", par->min_span_percent); return CDM_ERR_INVALID; }
+    if (int rc = pileupCheckArgs("cdm_pileup_breaks", db, alns, queries, n_queries)) return rc;
+    if (breaks) { *breaks = NULL; *n_breaks = 0; }
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (n_queries == 0) return CDM_OK;
+    CDM_HIP(hipSetDevice(ctx->device));
+    cdm_break *got = NULL; uint64_t nGot = 0;
+    const int rc = cdm_breaks_impl(ctx, db, alns, queries, n_queries, par, stats, track, breaks ? &got : NULL, &nGot, kernel_ms);
+    if (rc != CDM_OK) { free(got); return rc; }
+    if (breaks) { *breaks = got; *n_breaks = nGot; }
+    return CDM_OK;
+}
+
+extern "C" void cdm_breaks_free(cdm_break *breaks) { free(breaks); }
 
 extern "C" int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_pileup_params *par,
                                   uint64_t *counts, uint64_t *reads, uint64_t *columns) {

@@ -453,6 +453,54 @@ int  cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, c
 void cdm_sites_free(cdm_site *sites);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Contig break points from spanning reads (not a module of the reference; csrc/pileup.hip): is a query one molecule, or two stitched
+ * together?  A read that crosses a false join collects mismatches on the far side and falls below the set's identity threshold, so
+ * across a false join reads cover both flanks but none spans the boundary with a real anchor on either side - which depth cannot see.
+ * A record counts under exactly the rule of the three reductions above; the oriented record covers the query positions qs..qe.
+ * Boundary b of a query of `len` letters, 1 <= b <= len - 1, lies between the positions b - 1 and b.  With w = anchor:
+ *   span[b]   the number of counted records with qs + w <= b <= qe + 1 - w: at least w columns on either side of the boundary (a
+ *             record of fewer than 2 w columns spans nothing)
+ *   depth[i]  as in cdm_pileup_depth
+ *   window    the boundaries with edge <= b <= len - edge; empty when len < 2 * edge or len < 2
+ *   weak      a window boundary with span[b] < min_span, or - with min_span_percent > 0 - with
+ *             span[b] * 100 < min_span_percent * min(depth[b - 1], depth[b]) (64 bits)
+ *   break     a maximal run first..last of consecutive weak boundaries of one query: min_span = the smallest span of the run,
+ *             uncovered = the positions first .. last - 1 with depth 0, depth_left = depth[first - 1], depth_right = depth[last],
+ *             flags = CDM_BREAK_GAP where uncovered > 0, else CDM_BREAK_JOIN (the reads cover the stretch and none spans it: the
+ *             signature of a chimeric join)
+ *   stats   n_queries x 8 uint64, per listed query:
+ *             0 reads, 1 columns   cdm_pileup_depth's values       2 window    boundaries examined
+ *             3 weak               weak boundaries                 4 breaks    runs of them
+ *             5 joins              runs flagged CDM_BREAK_JOIN     6 min_span  smallest span over the window, 0 where it is empty
+ *             7 sum_span           sum of span over the window
+ *   track   NULL, or uint32 [sum of the listed queries' lengths]: per listed query span[b] for b = 0 .. len - 1 (span[0] = 0), the
+ *           queries back to back in listed order
+ *   breaks  NULL, or receives a malloc'ed array (cdm_breaks_free) of one record per break in listed query order, then ascending
+ *           first; query = the index into `queries`.  *n_breaks = their number; none: *breaks = NULL, *n_breaks = 0.  n_breaks may be
+ *           NULL only when breaks is
+ *   kernel_ms  NULL, or receives the device time of the kernels
+ * anchor in 1..1024, edge in anchor..1048576, min_span in 1..1000000, min_span_percent in 0..100; anything else, a NULL argument, a
+ * query index >= the DB's size or listed twice is CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched); a set with the
+ * coordinates -1 record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more is CDM_ERR_UNSUPPORTED
+ * (the cells are 32 bits wide; not reachable at test size, not tested).  The pile-up is the set's seeded ungapped overlaps at its
+ * identity threshold, not a gapped mapping: reads shorter than 2 * anchor span nothing, and there is no break call where no read
+ * seeds - a stretch without reads is reported as a gap, whatever its cause. */
+#define CDM_BREAK_JOIN 1u
+#define CDM_BREAK_GAP 2u
+typedef struct cdm_breaks_params {
+    int32_t anchor;            /* 1..1024: columns a spanning read has on either side of a boundary */
+    int32_t edge;              /* anchor..1048576: boundaries left out at either end of a query */
+    int32_t min_span;          /* 1..1000000 */
+    int32_t min_span_percent;  /* 0..100 */
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_breaks_params;
+typedef struct cdm_break { uint32_t query, first, last, min_span, uncovered, depth_left, depth_right, flags; } cdm_break;   /* 32 bytes */
+int  cdm_pileup_breaks(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                       const cdm_breaks_params *par, uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *n_breaks, float *kernel_ms);
+void cdm_breaks_free(cdm_break *breaks);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
  * db must be the corrected DB.  Output: new sequence DB (extended sequences get ext=1, others are copied through).
  * scores (optional, may be NULL): for tests, the per-candidate likelihood of the first scoring round
