@@ -49,6 +49,11 @@ def build(verbose=False):
         objs.append(obj)
         if _newer(src, obj, headers):
             jobs.append(["g++"] + GXX_FLAGS + ["-fopenmp", "-c", src, "-o", obj])
+    # a library that is newer than every source it is made of is up to date, whether or not the object files are still there
+    # (a tree copied without them); otherwise the link below needs them all
+    sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip")] + [os.path.join(hostdir, f) for f in host_lib_srcs]
+    if os.path.exists(LIB) and not any(_newer(src, LIB, headers) for src in sources):
+        jobs = []
     procs = [(j, subprocess.Popen(j, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for j in jobs]
     for j, p in procs:
         out, _ = p.communicate()

@@ -33,6 +33,8 @@ struct CorrectArgs {
     uint32_t *outCodes, *outNmask;
     const DamageLut *lut;
     float seqIdThr, corrRy;
+    uint32_t stagePool;       // fast kernels: usable words of the stage pool (CDM_CORRECT_STAGE_POOL; clamped to the instance's POOL)
+    unsigned long long *stats;        // CDM_CORRECT_STATS: [0] accepted records, [1] of them with N in the target, [2] longer than STAGE_WORDS, [3] past the pool; or NULL
 };
 
 constexpr int WAVES_PER_BLOCK = 2;      // general kernel: 64-bit counters (any number of records piles up), 22.5 KB of LDS per wave
@@ -276,21 +278,59 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_correct(CorrectArgs a)
 // phase (RY identity on 16-base words, XOR + popcount) and keeps the record, lane = position in the pile-up.
 // Same arithmetic as k_correct; 8-bit (4-bit) pile-up counters (a slot cannot exceed the 64 (15) records).
 constexpr int FAST_WAVES = 4;
-// Target words staged in LDS per record (lane = record loads the words its aligned span covers, all records at once): the pile-up
-// then takes its letters from LDS instead of one dependent global load per record and 64 positions.  12 words hold a span of 177
-// columns wherever it starts; longer spans and targets with N keep the global path.
+// Target words staged in LDS (lane = record loads the words its aligned span covers, all records at once): the pile-up then takes
+// its letters from LDS instead of one dependent global load per record and 64 positions.  A record of up to STAGE_WORDS words (12
+// hold a span of 177 columns wherever it starts) is staged; longer spans and targets with N keep the global path.
 constexpr int STAGE_WORDS = 12;
+// The stage is a pool of POOL words per wave, cut up per query: an exclusive wave scan over the word counts of the accepted records
+// gives each its offset, and a record whose words end past the pool keeps the global path like the long ones (which records land in
+// the pool never shows in a result).  A 100-column span takes 7 or 8 words and rejected records take none, so a pool far below
+// records * STAGE_WORDS holds nearly every accepted record - and the LDS it frees is what lets a fifth block onto the CU.
+constexpr size_t FAST_TABLE_BYTES = (16 + 12 * 16 + 2 * 11 * 16) * sizeof(double);
+template <typename CT> constexpr size_t fastCntWords() { return (size_t) SLOTS * (64 / (4 / sizeof(CT))); }
+template <typename CT> constexpr size_t fastLdsBytes(size_t pool) { return FAST_TABLE_BYTES + (size_t) FAST_WAVES * 4 * (fastCntWords<CT>() + pool); }
+// what the CU takes for a block: its LDS is handed out in CU_LDS_GRANULE steps, so that is what MINW blocks have to fit with
+constexpr size_t ldsAllocBytes(size_t bytes) { return (bytes + CU_LDS_GRANULE - 1) / CU_LDS_GRANULE * CU_LDS_GRANULE; }
+// POOL: the 15-record instance keeps 16 * STAGE_WORDS (its LDS is small either way); the 64-record one gets the most words with which
+// MINW blocks still fit the CU, at most 64 * STAGE_WORDS (every record at full length, what MINW = 4 comes to)
+template <int MAXREC, typename CT, int MINW> constexpr int fastPoolWords() {
+    if (MAXREC != 64) return 16 * STAGE_WORDS;
+    const size_t perBlock = CU_LDS_BYTES / MINW / CU_LDS_GRANULE * CU_LDS_GRANULE, fixed = fastLdsBytes<CT>(0);
+    if (perBlock <= fixed) return 0;
+    const size_t w = (perBlock - fixed) / (FAST_WAVES * 4);
+    return (int) (w < (size_t) 64 * STAGE_WORDS ? w : (size_t) 64 * STAGE_WORDS);
+}
+// Inclusive sum over the lanes 0 .. RECORDS - 1 of a wave (the others hold 0) on the DPP path: four shifts inside the rows of 16 lanes,
+// then the last lane of a row handed to the next row, and lane 31 to the upper two rows.  (A lane whose source lies outside its row, or
+// whose row is masked out, keeps the 0 it is given.)  Six VALU steps; the same through __shfl_up is six trips through the LDS crossbar.
+template <int RECORDS> __device__ __forceinline__ uint32_t waveInclusiveSum(uint32_t v) {
+    int x = (int) v;
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);      // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);      // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);      // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);      // row_shr:8
+    if (RECORDS > 16) {
+        x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+        x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+    }
+    return (uint32_t) x;
+}
+constexpr uint32_t NOT_STAGED = 0x80000000u;        // no offset - first word comes near it (offsets < POOL, word indices < 2^26)
 
 // MAXREC: most records of a query on this instance (64, or 15 with CT = uint8_t: two 4-bit fields per counter and a quarter of the
 // record slots - less LDS per block, more waves per CU; the kernel is bound by the latency of its dependent gathers, so the
-// occupancy is what it runs on).  MINW: waves per SIMD the register allocation has to leave room for.
+// occupancy is what it runs on).  MINW: waves per SIMD (= blocks per CU) the register allocation has to leave room for.
 template <int MAXREC, typename CT, int MINW>
 __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectArgs a, const uint32_t *__restrict__ list, const unsigned int *__restrict__ nList) {
     constexpr int HB = sizeof(CT) * 4;                  // bits per field: total | reverse << HB
     constexpr int PER = 4 / sizeof(CT);                 // counters per LDS dword
+    constexpr int POOL = fastPoolWords<MAXREC, CT, MINW>();
+    static_assert(POOL >= STAGE_WORDS && (size_t) MINW * ldsAllocBytes(fastLdsBytes<CT>(POOL)) <= CU_LDS_BYTES,
+                  "the launch bound asks for more blocks per CU than the kernel's LDS lets run: the compiler would drop the request");
     __shared__ double sLogT[16], sLogQ[12 * 16], sLogD[2 * 11 * 16];
     __shared__ uint32_t sCnt[FAST_WAVES][SLOTS * (64 / PER)];      // counter [slot][lane], PER lanes to a word
-    __shared__ uint32_t sStage[FAST_WAVES][(MAXREC == 64 ? 64 : 16) * STAGE_WORDS];
+    __shared__ uint32_t sStage[FAST_WAVES][POOL];
+    static_assert(sizeof(sLogT) + sizeof(sLogQ) + sizeof(sLogD) + sizeof(sCnt) + sizeof(sStage) == fastLdsBytes<CT>(POOL), "fastLdsBytes() is not what the kernel declares");
     for (int i = threadIdx.x; i < 16; i += blockDim.x) sLogT[i] = (&a.lut->logT[0][0])[i];
     for (int i = threadIdx.x; i < 12 * 16; i += blockDim.x) sLogQ[i] = (&a.lut->logQ[0][0][0])[i];
     for (int i = threadIdx.x; i < 2 * 11 * 16; i += blockDim.x) sLogD[i] = (&a.lut->logD[0][0][0][0])[i];
@@ -303,6 +343,7 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
     const uint32_t laneWord = (uint32_t) lane / PER, laneShift = ((uint32_t) lane % PER) * (8 * sizeof(CT));
     const uint32_t incFwd = 1u << laneShift, incRev = (1u | (1u << HB)) << laneShift;
     const uint32_t laneClear = ~((uint32_t) (CT) ~(CT) 0 << laneShift);
+    const uint32_t pool = min(a.stagePool, (uint32_t) POOL);
     for (int s = lane; s < SLOTS * (64 / PER); s += 64) cntWords[s] = 0;       // a lane clears the slots it touched after every call
     // The chain list -> record offsets + query metadata -> records is walked one query AHEAD: the next query's offsets and metadata are
     // requested at the top of an iteration, its records (one per lane) and their RY counts once the gate of the current query is through,
@@ -337,7 +378,8 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
         const float avCov = static_cast<float>(static_cast<float>(cdm_wave_sum((int) aLen))) / qLen;
         bool ok = false;
         uint32_t iTw = 0, iLenFlags = 0, iQs = 0, iSpan = 0, iDs = 0;     // the record as the pile-up needs it, kept in this lane's registers
-        uint32_t iW0 = 0;                                                 // bit 31: the span's words are staged, from this word of the target on
+        uint32_t iDelta = NOT_STAGED;                                     // staged: stage[iDelta + w] holds word w of the target
+        uint32_t w0 = 0, nW = 0; bool tN = false;                         // the span's words on the target as stored (nW = 0: asks for no pool space)
         if (have) {
             const uint32_t t = rec.target, tLen = a.len[t], tw = a.woff[t];
             const bool tHasN = a.hasN[t] != 0;
@@ -375,16 +417,26 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
             }
             // sequences on this path are shorter than 2^30 letters (the DB's word offsets are 32 bit)
             iTw = tw; iLenFlags = tLen | (o.rev ? 0x80000000u : 0u) | (tHasN ? 0x40000000u : 0u); iQs = (uint32_t) o.qs; iSpan = (uint32_t) (o.qe - o.qs); iDs = (uint32_t) o.ds;
+            tN = tHasN;
             if (ok && !tHasN) {
                 const uint32_t fLo = o.rev ? tLen - 1u - (iDs + iSpan) : iDs;       // the span on the target as stored
-                const uint32_t w0 = fLo >> 4, nW = ((fLo + iSpan) >> 4) - w0 + 1u;
-                if (nW <= (uint32_t) STAGE_WORDS) {
-                    for (uint32_t j = 0; j < nW; j++) stage[lane * STAGE_WORDS + j] = a.codes[tw + w0 + j];
-                    iW0 = w0 | 0x80000000u;
-                }
+                w0 = fLo >> 4; nW = ((fLo + iSpan) >> 4) - w0 + 1u;
             }
         }
+        const bool fits = nW != 0 && nW <= (uint32_t) STAGE_WORDS;
+        const uint32_t end = waveInclusiveSum<MAXREC>(fits ? nW : 0u);       // where this record's words end, if they are all taken
+        const bool staged = fits && end <= pool;
+        if (staged) {
+            const uint32_t off = end - nW;
+            for (uint32_t j = 0; j < nW; j++) stage[off + j] = a.codes[iTw + w0 + j];
+            iDelta = off - w0;
+        }
         const uint64_t okMask = __ballot(ok);
+        if (a.stats) {      // (a stats run: not what is timed)
+            const uint64_t mN = __ballot(ok && tN), mLong = __ballot(nW > (uint32_t) STAGE_WORDS), mOver = __ballot(fits && !staged);
+            if (lane == 0) { atomicAdd(&a.stats[0], (unsigned long long) __popcll(okMask)); atomicAdd(&a.stats[1], (unsigned long long) __popcll(mN));
+                             atomicAdd(&a.stats[2], (unsigned long long) __popcll(mLong)); atomicAdd(&a.stats[3], (unsigned long long) __popcll(mOver)); }
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // the next query's records, on their way during the pile-up
         qCur = qN; qmCur = qmN; r0Cur = r0N; nRecCur = (uint32_t) (r1N - r0N); ryCur = 0xFFFFu;
@@ -403,15 +455,15 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
                 if (qs + span < base || qs >= base + 64) continue;   // wave uniform
                 const uint32_t lf = (uint32_t) __builtin_amdgcn_readlane((int) iLenFlags, r), tw = (uint32_t) __builtin_amdgcn_readlane((int) iTw, r);
                 const uint32_t ds = (uint32_t) __builtin_amdgcn_readlane((int) iDs, r), tLen = lf & 0x3FFFFFFFu;
-                const uint32_t w0f = (uint32_t) __builtin_amdgcn_readlane((int) iW0, r);
+                const uint32_t dl = (uint32_t) __builtin_amdgcn_readlane((int) iDelta, r);
                 const uint32_t d = p - qs;
                 if (d <= span) {
                     const uint32_t tpos = ds + d;                            // position on the oriented target
                     uint32_t tb;
-                    if (w0f & 0x80000000u) {
+                    if (dl != NOT_STAGED) {
                         const bool rev = (lf & 0x80000000u) != 0;
                         const uint32_t f = rev ? tLen - 1u - tpos : tpos;
-                        tb = (stage[(uint32_t) r * STAGE_WORDS + (f >> 4) - (w0f & 0x7FFFFFFFu)] >> ((f & 15u) * 2u)) & 3u;
+                        tb = (stage[dl + (f >> 4)] >> ((f & 15u) * 2u)) & 3u;
                         if (rev) tb = 3u - tb;
                     } else if (lf & 0x40000000u) tb = targetBase(a, tw, tLen, true, (lf & 0x80000000u) != 0, tpos);
                     else if (lf & 0x80000000u) tb = 3u - cdm_base(a.codes, tw, tLen - 1u - tpos);
@@ -489,6 +541,14 @@ __global__ void k_debug_call(const DamageLut *lut, const uint32_t *vec, uint32_t
     out[i] = (uint8_t) callBase(sLogT, sLogQ, sLogD, v[0], v[1], v[2], v[3] != 0, [&](int slot) { const uint32_t x = v[4 + slot]; return (uint64_t) (x & 0xFFFFu) | ((uint64_t) (x >> 16) << 32); }, ALL_SLOTS, keep);
 }
 
+// blocks of a persistent kernel: GRID_ROUNDS times what the device holds at once; `guess` when the runtime cannot tell
+constexpr int GRID_ROUNDS = 8;
+template <typename K> int residentGrid(K kernel, int threads, unsigned dynLds, int cuCount, int guess) {
+    int perCu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, threads, dynLds) != hipSuccess || perCu <= 0) { (void) hipGetLastError(); return guess; }
+    return cuCount * perCu * GRID_ROUNDS;
+}
+
 }  // namespace
 
 // not part of the public header: used by tests/test_gpu_correct.py through ctypes to run the reference's
@@ -532,24 +592,58 @@ int cdm_correct_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, co
     cdmSetMeta(a, meta.p, uni); a.ext.m = meta.p; a.ext.plain = uni.words; a.codes = db->codes; a.nmask = db->nmask; a.raw = db->raw; a.outRaw = out->raw;
     a.aoff = alns->off; a.rec = alns->rec; a.ry = (alns->ryMism && alns->rySerial == db->serial) ? alns->ryMism : nullptr; a.active = active.p; a.nActive = counters.p; a.accept = accept.p; a.errFlag = counters.p + 1;
     a.outCodes = out->codes; a.outNmask = out->nmask; a.lut = ctx->lutDev; a.seqIdThr = par->seq_id_thr; a.corrRy = par->corr_reads_ry_seq_id;
+    // CDM_CORRECT_STAGE_POOL=<words> (tests): lowers the usable stage pool of the fast kernels, 0 stages nothing
+    const char *poolEnv = cdmGetenv("CDM_CORRECT_STAGE_POOL");
+    a.stagePool = poolEnv ? (uint32_t) std::max(0, atoi(poolEnv)) : ~0u;
+    // CDM_CORRECT_STATS=1: count the accepted records of the fast kernels that were not staged, and why (printed to stderr)
+    DevBuf<unsigned long long> stats;
+    a.stats = nullptr;
+    if (const char *e = cdmGetenv("CDM_CORRECT_STATS"); e && atoi(e)) {
+        if (!stats.alloc(4)) { cdm_set_error("out of device memory in cdm_correct"); return CDM_ERR_HIP; }
+        CDM_HIP(hipMemsetAsync(stats.p, 0, 32, s));
+        a.stats = stats.p;
+    }
     const int blocks = ctx->cuCount * 8;
     hipEventRecord(ctx->ev0, s);
     const char *padEnv = cdmGetenv("CDM_LDS_PAD");          // experiments: dynamic LDS that lowers the occupancy
     const unsigned pad = padEnv ? (unsigned) atoi(padEnv) : 0u;
-    if (smallW == 8) hipLaunchKernelGGL((k_correct_fast<15, uint8_t, 8>), dim3(blocks * 2), dim3(64 * FAST_WAVES), pad, s, a, activeSmall.p, counters.p + 3);
-    else if (smallW == 5) hipLaunchKernelGGL((k_correct_fast<15, uint8_t, 5>), dim3(blocks * 2), dim3(64 * FAST_WAVES), pad, s, a, activeSmall.p, counters.p + 3);
-    else if (smallW) hipLaunchKernelGGL((k_correct_fast<15, uint8_t, 6>), dim3(blocks * 2), dim3(64 * FAST_WAVES), pad, s, a, activeSmall.p, counters.p + 3);
-    const char *bigEnv = cdmGetenv("CDM_CORRECT_BIGW");     // experiments: waves per SIMD of the 16..64-record instance
+    // Every grid is a whole number of rounds of what the device holds at once, cuCount x resident blocks x GRID_ROUNDS: a grid that is no
+    // multiple of the resident blocks ends on a short round (16 blocks per CU at 6 resident is 6 + 6 + 4).  One round alone is the slowest:
+    // the loops split their list by gridDim, and the waves of one round do not end together - with several rounds the block dispatcher
+    // evens that out (50 M reads, the stage's kernels with the deep launch at 1, 2, 4, 8 and 32 rounds of 5 blocks per CU: 37.1, 35.4, 34.0,
+    // 33.2 and 33.0 ms; profiles/r07_correct_grids.txt).  `guess` is the size used when the runtime cannot tell the resident blocks.
+    int grids[3] = {0, 0, 0};       // small, deep, general (for the stats line)
+    // CDM_CORRECT_GRID=<small>,<deep> (experiments): blocks per CU of the two fast launches, 0 = GRID_ROUNDS rounds of the resident ones
+    int gridPerCu[2] = {0, 0};
+    if (const char *e = cdmGetenv("CDM_CORRECT_GRID")) sscanf(e, "%d,%d", &gridPerCu[0], &gridPerCu[1]);
+    auto launchFast = [&](auto kernel, int guess, const uint32_t *list, const unsigned int *nList, int &grid) {
+        const int perCu = gridPerCu[&grid - grids];
+        grid = perCu > 0 ? ctx->cuCount * perCu : residentGrid(kernel, 64 * FAST_WAVES, pad, ctx->cuCount, guess);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * FAST_WAVES), pad, s, a, list, nList);
+    };
+    if (smallW == 8) launchFast(k_correct_fast<15, uint8_t, 8>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    else if (smallW == 5) launchFast(k_correct_fast<15, uint8_t, 5>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    else if (smallW) launchFast(k_correct_fast<15, uint8_t, 6>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    // CDM_CORRECT_BIGW (experiments): blocks per CU of the 16..64-record instance.  5 (the default) with the pool that leaves room for five,
+    // 4 with a pool for every record at full length; 6 does not fit the LDS with any pool and selects the default instance.
+    const char *bigEnv = cdmGetenv("CDM_CORRECT_BIGW");
     const int bigW = bigEnv ? atoi(bigEnv) : 5;
-    if (bigW == 6) hipLaunchKernelGGL((k_correct_fast<64, uint16_t, 6>), dim3(blocks * 2), dim3(64 * FAST_WAVES), pad, s, a, activeFast.p, counters.p + 2);
-    else if (bigW == 5) hipLaunchKernelGGL((k_correct_fast<64, uint16_t, 5>), dim3(blocks * 2), dim3(64 * FAST_WAVES), pad, s, a, activeFast.p, counters.p + 2);
-    else hipLaunchKernelGGL((k_correct_fast<64, uint16_t, 4>), dim3(blocks), dim3(64 * FAST_WAVES), pad, s, a, activeFast.p, counters.p + 2);
-    hipLaunchKernelGGL(k_correct, dim3(blocks / 2), dim3(64 * WAVES_PER_BLOCK), 0, s, a);
+    if (bigW == 4) launchFast(k_correct_fast<64, uint16_t, 4>, blocks, activeFast.p, counters.p + 2, grids[1]);
+    else launchFast(k_correct_fast<64, uint16_t, 5>, blocks * 2, activeFast.p, counters.p + 2, grids[1]);
+    grids[2] = residentGrid(k_correct, 64 * WAVES_PER_BLOCK, 0, ctx->cuCount, blocks / 2);
+    hipLaunchKernelGGL(k_correct, dim3(grids[2]), dim3(64 * WAVES_PER_BLOCK), 0, s, a);
     hipEventRecord(ctx->ev1, s);
     CDM_LAUNCH_CHECK();
     unsigned int flags[2] = {0, 0};
     CDM_HIP(hipMemcpyAsync(flags, counters.p, 8, hipMemcpyDeviceToHost, s));
     { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) { cdm_set_error("ancient_correction kernel failed: %s", hipGetErrorString(e)); return CDM_ERR_HIP; } }
     hipEventElapsedTime(&ctx->lastMs[0], ctx->ev0, ctx->ev1);
+    if (a.stats) {
+        unsigned long long st[4] = {0, 0, 0, 0};
+        CDM_HIP(hipMemcpy(st, stats.p, 32, hipMemcpyDeviceToHost));
+        fprintf(stderr, "cdm_correct stats (fast kernels): accepted records %llu, not staged %llu (target with N %llu, more than %d words %llu, past the pool %llu)\n",
+                st[0], st[1] + st[2] + st[3], st[1], STAGE_WORDS, st[2], st[3]);
+        fprintf(stderr, "cdm_correct grids: small %d, deep %d, general %d blocks on %d CUs\n", grids[0], grids[1], grids[2], ctx->cuCount);
+    }
     return CDM_OK;
 }

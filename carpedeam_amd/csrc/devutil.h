@@ -60,6 +60,10 @@ __device__ __forceinline__ uint32_t cdm_squash16(uint32_t x) {
     return x;
 }
 
+// LDS of a gfx950 compute unit, and the step in which blocks are given theirs (a block's size is rounded up to it): what a launch
+// bound's blocks per CU are checked against
+constexpr size_t CU_LDS_BYTES = 160 * 1024, CU_LDS_GRANULE = 1280;
+
 __device__ __forceinline__ int cdm_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ uint64_t cdm_ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ int cdm_wave_sum(int v) {

@@ -258,7 +258,6 @@ template <typename LY> constexpr size_t gkLdsBytes() {
     return (size_t) bucket::BK_WAVES * ((size_t) GkGeom<LY>::WIN * 8 + (LY::bySlot ? 1 : (size_t) GkGeom<LY>::WIN) * sizeof(typename LY::V) + (size_t) GkGeom<LY>::MAXB * 4 + sizeof(bucket::WaveLdsT<GkGeom<LY>::WIN>) +
                                       (LY::bySlot ? (size_t) REC_CAP : 1) * 12);
 }
-constexpr size_t CU_LDS_BYTES = 160 * 1024;
 // A request the LDS cannot meet is not approximated by the compiler but dropped ("failed to meet occupancy target"): the slot instance
 // asked for 7 with 26 KB of LDS per block, got an uncapped allocation of 83 registers and ran at 5.  Hence the assert next to the bound
 // (a sweep's CDM_GK_MINW reaches the other layouts' instances as far as their LDS goes).
