@@ -71,6 +71,12 @@ __device__ __forceinline__ int cdm_wave_sum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ unsigned long long waveSum64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v += ((unsigned long long) (unsigned int) __shfl_xor((int) (v >> 32), o, 64) << 32) | (unsigned int) __shfl_xor((int) (unsigned int) v, o, 64);
+    return v;
+}
 
 // slot for this lane in a global append list: one atomic per wave instead of one per lane (a single word saturates at
 // ~88 atomics/us, MI355X_MICROARCH.md "dequeue"); every lane of the wave must call it

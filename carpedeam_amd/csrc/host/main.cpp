@@ -1252,11 +1252,15 @@ void concatByKey(const OutChunk &all, const OutChunk &cyclic, OutChunk &merged) 
 // (kmermatcher's representative rule), possibly on several contigs.  One TSV line per contig, integers only.
 bool writeText(const std::string &path, const std::string &text);
 const FlagSpec DAMAGE_FLAGS[] = {{"--damage-ends", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-long damageEnds(Args &a, const char *module) {
-    const long e = iflag(a, "--damage-ends", 16);
-    if (e < 1 || e > 64) unsupported(std::string(module) + ": --damage-ends " + a.flag["--damage-ends"] + " is not supported by the MI355X path (the tables hold 1 to 64 positions from either end of a read)");
-    return e;
+// an integer flag with the values the device path takes: lo to hi, or the module refuses it with `what`
+long rangedFlag(Args &a, const char *module, const char *flag, long dflt, long lo, long hi, const char *what) {
+    const long v = iflag(a, flag, dflt);
+    if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
+    return v;
 }
+long damageEnds(Args &a, const char *module) { return rangedFlag(a, module, "--damage-ends", 16, 1, 64, "the tables hold 1 to 64 positions from either end of a read"); }
+// a tab and an integer behind a TSV line
+void put(std::string &to, unsigned long long v) { char num[32]; to.push_back('\t'); to.append(num, (size_t) (utoa(v, num) - num)); }
 // a set of sequences on the device with the names and keys its TSV lines carry
 struct DamageInput { cdm_seqdb *db = NULL; std::vector<std::string> names; std::vector<uint32_t> keys; };
 // path: a sequence DB (names from its header DB where it has one) or FASTA/FASTQ[.gz] (shuffle: createdb's order, as the loop lays its
@@ -1308,6 +1312,19 @@ PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int
 void freePileSet(PileSet &p) { if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
 bool haveContigs(const DamageInput *contigs) { return contigs && contigs->db && cdm_seqdb_size(contigs->db); }
 const std::string &contigName(const DamageInput &c, uint64_t i, std::string &tmp) { if (i < c.names.size()) return c.names[i]; tmp = std::to_string(c.keys[i]); return tmp; }
+// bedGraph lines of one contig's runs of equal value, zero runs included: name, start, end (0-based, half-open), value
+void bedGraphRuns(std::string &to, const std::string &name, const uint32_t *d, uint32_t len) {
+    for (uint32_t start = 0, p = 1; p <= len; p++)
+        if (p == len || d[p] != d[start]) { to += name; put(to, start); put(to, p); put(to, d[start]); to.push_back('\n'); start = p; }
+}
+// the contigs' own bytes (raw plane included): contig i from at[i], lens[i] + 1 bytes
+std::string contigLetters(cdm_ctx *ctx, const DamageInput &contigs, const std::vector<uint32_t> &lens, std::vector<uint64_t> &at) {
+    at.assign(lens.size() + 1, 0);
+    for (size_t i = 0; i < lens.size(); i++) at[i + 1] = at[i] + lens[i] + 1ull;
+    std::string letters(at.back(), '\0');
+    check(cdm_seqdb_download(ctx, contigs.db, &letters[0], at.data()), "download of the contigs");
+    return letters;
+}
 // the damage TSV from the alignments of a PileSet; no contigs: the header line alone
 void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, long ends, const std::string &outPath, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns";
@@ -1323,15 +1340,14 @@ void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, lo
         check(cdm_pileup_profile(ctx, ps.both, ps.alns, q.data(), nc, &pp, counts.data(), nReads.data(), nCols.data()), "pile-up profile");
         if (getenv("CDM_TIMING")) fprintf(stderr, "  damage report: %llu records, pile-up kernel %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 16));
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        char num[32]; std::string tmp;
-        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        std::string tmp;
         for (uint64_t i = 0; i < nc; i++) {
             text += contigName(*contigs, i, tmp);
-            put(contigs->keys[i]); put(lens[i]); put(nReads[i]); put(nCols[i]);
+            put(text, contigs->keys[i]); put(text, lens[i]); put(text, nReads[i]); put(text, nCols[i]);
             const uint64_t *c5 = counts.data() + i * cells, *c3 = c5 + (size_t) ends * 16;
             for (long d = 0; d < ends; d++) {       // [d][x][y], A,C,G,T = 0..3: C under any read base / under T; G under any / under A
                 const uint64_t *c = c5 + d * 16 + 1 * 4, *g = c3 + d * 16 + 2 * 4;
-                put(c[0] + c[1] + c[2] + c[3]); put(c[3]); put(g[0] + g[1] + g[2] + g[3]); put(g[0]);
+                put(text, c[0] + c[1] + c[2] + c[3]); put(text, c[3]); put(text, g[0] + g[1] + g[2] + g[3]); put(text, g[0]);
             }
             text.push_back('\n');
         }
@@ -1344,11 +1360,7 @@ void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, lo
 // identity threshold, not a gapped mapping.  One TSV line per contig, integers only: the caller divides (mean = sum / window,
 // variance = (sumsq - sum^2 / window) / (window - 1)).
 const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-long depthEdge(Args &a, const char *module) {
-    const long e = iflag(a, "--depth-edge", 0);
-    if (e < 0 || e > 1048576) unsupported(std::string(module) + ": --depth-edge " + a.flag["--depth-edge"] + " is not supported by the MI355X path (0 to 1048576 positions are left out at either end of a contig)");
-    return e;
-}
+long depthEdge(Args &a, const char *module) { return rangedFlag(a, module, "--depth-edge", 0, 0, 1048576, "0 to 1048576 positions are left out at either end of a contig"); }
 // one read set's statistics (nc x 8) and, when asked for, the depth of every contig position back to back
 void depthSample(cdm_ctx *ctx, const DamageInput &contigs, const PileSet &ps, long edge, std::vector<uint64_t> &stats, std::vector<uint32_t> *track) {
     const uint64_t nc = cdm_seqdb_size(contigs.db);
@@ -1371,33 +1383,26 @@ void depthTable(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<std:
         const uint64_t nc = cdm_seqdb_size(contigs->db);
         std::vector<uint32_t> lens(nc);
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        char num[32]; std::string tmp;
-        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        std::string tmp;
         for (uint64_t i = 0; i < nc; i++) {
             text += contigName(*contigs, i, tmp);
-            put(contigs->keys[i]); put(lens[i]); put(stats[0][i * 8 + 3]);
-            for (size_t s = 0; s < samples; s++) for (int c : AT) put(stats[s][i * 8 + c]);
+            put(text, contigs->keys[i]); put(text, lens[i]); put(text, stats[0][i * 8 + 3]);
+            for (size_t s = 0; s < samples; s++) for (int c : AT) put(text, stats[s][i * 8 + c]);
             text.push_back('\n');
         }
     }
     if (!writeText(outPath, text)) die("Could not write " + outPath);
 }
-// bedGraph of the runs of equal depth, zero runs included: name, start, end (0-based, half-open), depth
+// bedGraph of the runs of equal depth
 void depthTrackFile(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<uint32_t> &track, const std::string &outPath) {
     std::string text;
     if (haveContigs(contigs)) {
         const uint64_t nc = cdm_seqdb_size(contigs->db);
         std::vector<uint32_t> lens(nc);
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        char num[32]; std::string tmp;
-        auto put = [&](unsigned long long v) { text.push_back('\t'); text.append(num, (size_t) (utoa(v, num) - num)); };
+        std::string tmp;
         uint64_t at = 0;
-        for (uint64_t i = 0; i < nc; at += lens[i], i++) {
-            const std::string &name = contigName(*contigs, i, tmp);
-            const uint32_t *d = track.data() + at;
-            for (uint32_t start = 0, p = 1; p <= lens[i]; p++)
-                if (p == lens[i] || d[p] != d[start]) { text += name; put(start); put(p); put(d[start]); text.push_back('\n'); start = p; }
-        }
+        for (uint64_t i = 0; i < nc; at += lens[i], i++) bedGraphRuns(text, contigName(*contigs, i, tmp), track.data() + at, lens[i]);
     }
     if (!writeText(outPath, text)) die("Could not write " + outPath);
 }
@@ -1410,16 +1415,11 @@ const FlagSpec VARIANT_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-alt-count"
                                   {"--consensus", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 struct VariantOpts { long maskEnds, minDepth, minAltCount, minAltPercent; };
 VariantOpts variantOpts(Args &a, const char *module) {
-    auto ranged = [&](const char *flag, long dflt, long lo, long hi, const char *what) {
-        const long v = iflag(a, flag, dflt);
-        if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
-        return v;
-    };
     VariantOpts o;
-    o.maskEnds = ranged("--mask-ends", 0, 0, 64, "0 to 64 read positions are left out at either end of a read");
-    o.minDepth = ranged("--min-depth", 3, 1, 1000000, "a called position has 1 to 1000000 bases");
-    o.minAltCount = ranged("--min-alt-count", 2, 1, 1000000, "a second allele has 1 to 1000000 bases");
-    o.minAltPercent = ranged("--min-alt-percent", 20, 0, 100, "a percentage of the depth is 0 to 100");
+    o.maskEnds = rangedFlag(a, module, "--mask-ends", 0, 0, 64, "0 to 64 read positions are left out at either end of a read");
+    o.minDepth = rangedFlag(a, module, "--min-depth", 3, 1, 1000000, "a called position has 1 to 1000000 bases");
+    o.minAltCount = rangedFlag(a, module, "--min-alt-count", 2, 1, 1000000, "a second allele has 1 to 1000000 bases");
+    o.minAltPercent = rangedFlag(a, module, "--min-alt-percent", 20, 0, 100, "a percentage of the depth is 0 to 100");
     return o;
 }
 // what a variant report writes: the summary always, the other two files when named
@@ -1439,8 +1439,7 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
         check(cdm_pileup_bases(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
         if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu sites, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nSites, ms);
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        char num[32]; std::string tmp;
-        auto put = [&](std::string &to, unsigned long long x) { to.push_back('\t'); to.append(num, (size_t) (utoa(x, num) - num)); };
+        std::string tmp;
         for (uint64_t i = 0; i < nc; i++) {
             text += contigName(*contigs, i, tmp);
             put(text, contigs->keys[i]); put(text, lens[i]);
@@ -1462,11 +1461,9 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
                 for (uint32_t c : st.counts) put(sitesText, c);
                 sitesText.push_back('\n');
             }
-        if (v.consensus) {      // the contigs' own bytes (raw plane included), the reads' majority letter at the D positions
-            std::vector<uint64_t> at(nc + 1, 0);
-            for (uint64_t i = 0; i < nc; i++) at[i + 1] = at[i] + lens[i] + 1ull;
-            std::string letters(at[nc], '\0');
-            check(cdm_seqdb_download(ctx, contigs->db, &letters[0], at.data()), "download of the contigs");
+        if (v.consensus) {      // the contigs' own bytes, the reads' majority letter at the D positions
+            std::vector<uint64_t> at;
+            std::string letters = contigLetters(ctx, *contigs, lens, at);
             for (uint64_t k = 0; k < nSites; k++)
                 if ((sites[k].info >> 8) & CDM_SITE_DIFFERS) letters[at[sites[k].query] + sites[k].pos] = LETTER[(sites[k].info >> 4) & 15u];
             for (uint64_t i = 0; i < nc; i++) { fasta.push_back('>'); fasta += contigName(*contigs, i, tmp); fasta.push_back('\n'); fasta.append(letters, at[i], lens[i] + 1ull); }
@@ -1487,11 +1484,6 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
 const FlagSpec BREAK_FLAGS[] = {{"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0}, {"--split", 'U', 0, 0},
                                 {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 struct BreakOpts { long anchor, edge, minSpan, minSpanPercent; };
-long rangedFlag(Args &a, const char *module, const char *flag, long dflt, long lo, long hi, const char *what) {
-    const long v = iflag(a, flag, dflt);
-    if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
-    return v;
-}
 // The default anchor is reasoned, not measured: a read with w columns beyond a false join expects 0.75 w mismatches there, and at the
 // identity threshold t a read of L columns is dropped when 0.75 w > (1 - t) L; w = 16 covers L <= 120 at t = 0.9.
 BreakOpts breakOpts(Args &a, const char *module) {
@@ -1521,15 +1513,9 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
         check(cdm_pileup_breaks(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
         if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu breaks, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nBr, ms);
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        char num[32]; std::string tmp;
-        auto put = [&](std::string &to, unsigned long long x) { to.push_back('\t'); to.append(num, (size_t) (utoa(x, num) - num)); };
-        std::vector<uint64_t> at(nc + 1, 0);
-        std::string letters;
-        if (o.split) {          // the contigs' own bytes (raw plane included)
-            for (uint64_t i = 0; i < nc; i++) at[i + 1] = at[i] + lens[i] + 1ull;
-            letters.assign(at[nc], '\0');
-            check(cdm_seqdb_download(ctx, contigs->db, &letters[0], at.data()), "download of the contigs");
-        }
+        std::string tmp, letters;
+        std::vector<uint64_t> at;
+        if (o.split) letters = contigLetters(ctx, *contigs, lens, at);
         uint64_t k = 0, trackAt = 0;
         for (uint64_t i = 0; i < nc; trackAt += lens[i], i++) {
             const std::string &name = contigName(*contigs, i, tmp);
@@ -1557,11 +1543,7 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
                     if (j < k) from = br[j].last;
                 }
             }
-            if (o.track) {      // bedGraph of the runs of equal span: name, start, end (0-based, half-open), span
-                const uint32_t *d = track.data() + trackAt;
-                for (uint32_t start = 0, p = 1; p <= lens[i]; p++)
-                    if (p == lens[i] || d[p] != d[start]) { bed += name; put(bed, start); put(bed, p); put(bed, d[start]); bed.push_back('\n'); start = p; }
-            }
+            if (o.track) bedGraphRuns(bed, name, track.data() + trackAt, lens[i]);      // the runs of equal span
         }
         cdm_breaks_free(br);
         laps.lap("break report: break points, tables");
@@ -1570,42 +1552,55 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
     if (o.split && !writeText(*o.split, fasta)) die("Could not write " + *o.split);
     if (o.track && !writeText(*o.track, bed)) die("Could not write " + *o.track);
 }
+// What a pileReports call is asked for (NULL: not asked for): the damage table with its ends, the depth table with its edge and
+// track, the variant and the break reports.
+struct PileAsk {
+    const std::string *damageOut = NULL; long ends = 0;
+    const std::string *depthOut = NULL; long edge = 0; const std::string *trackOut = NULL;
+    const VariantOut *variants = NULL; const BreakOut *breaks = NULL;
+};
 // The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
-// alignment set.  damageOut / depthOut / variants / breaks: NULL = not asked for; contigs == NULL: the header lines alone.  Neither DB is freed here.
-void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const std::string *damageOut, long ends, const std::string *depthOut, long edge,
-                 const std::string *trackOut, const VariantOut *variants, const BreakOut *breaks, Laps &laps) {
+// alignment set.  contigs == NULL: the header lines alone.  Neither DB is freed here.
+void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const PileAsk &ask, Laps &laps) {
     PileSet ps;
     if (haveContigs(contigs)) {
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
-        laps.lap(damageOut ? "damage report: kmermatcher, rescorediagonal" : depthOut ? "depth report: kmermatcher, rescorediagonal" : variants ? "variant report: kmermatcher, rescorediagonal" : "break report: kmermatcher, rescorediagonal");
+        laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" : "break report: kmermatcher, rescorediagonal");
     }
-    if (damageOut) damageTable(ctx, contigs, ps, ends, *damageOut, laps);
-    if (depthOut) {
+    if (ask.damageOut) damageTable(ctx, contigs, ps, ask.ends, *ask.damageOut, laps);
+    if (ask.depthOut) {
         std::vector<std::vector<uint64_t>> stats(1); std::vector<uint32_t> track;
-        if (haveContigs(contigs)) depthSample(ctx, *contigs, ps, edge, stats[0], trackOut ? &track : NULL);
-        depthTable(ctx, contigs, stats, 1, *depthOut);
-        if (trackOut) depthTrackFile(ctx, contigs, track, *trackOut);
+        if (haveContigs(contigs)) depthSample(ctx, *contigs, ps, ask.edge, stats[0], ask.trackOut ? &track : NULL);
+        depthTable(ctx, contigs, stats, 1, *ask.depthOut);
+        if (ask.trackOut) depthTrackFile(ctx, contigs, track, *ask.trackOut);
         laps.lap("depth report: depth, table");
     }
-    if (variants) variantReport(ctx, contigs, ps, *variants, laps);
-    if (breaks) breakReport(ctx, contigs, ps, *breaks, laps);
+    if (ask.variants) variantReport(ctx, contigs, ps, *ask.variants, laps);
+    if (ask.breaks) breakReport(ctx, contigs, ps, *ask.breaks, laps);
     freePileSet(ps);
 }
-int contigDamage(Args &a) {
-    if (a.pos.size() < 3) die("Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]");
-    checkFlags("contig_damage", a, DAMAGE_FLAGS);
-    const long ends = damageEnds(a, "contig_damage");
+// The commands with one read set: exactly (or at least) three positional arguments or the usage line, the flag check, what the
+// command asks for from its flags (fill), both inputs, the reports.
+template <class Fill> int contigReport(Args &a, const char *module, bool exactly, const char *usage, const FlagSpec *flags, Fill fill) {
+    if (exactly ? a.pos.size() != 3 : a.pos.size() < 3) die(usage);
+    checkFlags(module, a, flags);
+    PileAsk ask;
+    fill(ask);
     Laps laps;
     cdm_ctx *ctx = openCtx();
     DamageInput contigs, reads;
     const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_damage: " + a.pos[1] + " holds no reads");
+    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die(std::string(module) + ": " + a.pos[1] + " holds no reads");
     laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), &a.pos[2], ends, NULL, 0, NULL, NULL, NULL, laps);
+    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), ask, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
     if (reads.db) cdm_seqdb_free(reads.db);
     cdm_ctx_destroy(ctx);
     return EXIT_SUCCESS;
+}
+int contigDamage(Args &a) {
+    return contigReport(a, "contig_damage", false, "Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]", DAMAGE_FLAGS,
+                        [&](PileAsk &ask) { ask.ends = damageEnds(a, "contig_damage"); ask.damageOut = &a.pos[2]; });
 }
 int contigDepth(Args &a) {
     if (a.pos.size() < 3) die("Usage: carpedeam contig_depth <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> [<i:reads> ...] <o:tsvFile> [--depth-edge 0] [--min-seq-id 0.9] [-k 20] [--depth-track <bedGraph>]");
@@ -1638,43 +1633,23 @@ int contigDepth(Args &a) {
     return EXIT_SUCCESS;
 }
 int contigVariants(Args &a) {
-    if (a.pos.size() != 3) die("Usage: carpedeam contig_variants <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-alt-count 2] [--min-alt-percent 20] [--mask-ends 0] "
-                               "[--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20]");
-    checkFlags("contig_variants", a, VARIANT_FLAGS);
     VariantOut v;
-    v.opt = variantOpts(a, "contig_variants");
-    v.summary = &a.pos[2]; v.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; v.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
-    Laps laps;
-    cdm_ctx *ctx = openCtx();
-    DamageInput contigs, reads;
-    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_variants: " + a.pos[1] + " holds no reads");
-    laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, &v, NULL, laps);
-    if (contigs.db) cdm_seqdb_free(contigs.db);
-    if (reads.db) cdm_seqdb_free(reads.db);
-    cdm_ctx_destroy(ctx);
-    return EXIT_SUCCESS;
+    return contigReport(a, "contig_variants", true, "Usage: carpedeam contig_variants <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-alt-count 2] [--min-alt-percent 20] [--mask-ends 0] "
+                        "[--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20]", VARIANT_FLAGS, [&](PileAsk &ask) {
+        v.opt = variantOpts(a, "contig_variants");
+        v.summary = &a.pos[2]; v.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; v.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
+        ask.variants = &v;
+    });
 }
 int contigBreaks(Args &a) {
-    if (a.pos.size() != 3) die("Usage: carpedeam contig_breaks <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--break-anchor 16] [--break-edge 50] [--min-span 1] [--min-span-percent 0] "
-                               "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--min-seq-id 0.9] [-k 20]");
-    checkFlags("contig_breaks", a, BREAK_FLAGS);
     BreakOut o;
-    o.opt = breakOpts(a, "contig_breaks");
-    o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
-    o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
-    Laps laps;
-    cdm_ctx *ctx = openCtx();
-    DamageInput contigs, reads;
-    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die("contig_breaks: " + a.pos[1] + " holds no reads");
-    laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), NULL, 0, NULL, 0, NULL, NULL, &o, laps);
-    if (contigs.db) cdm_seqdb_free(contigs.db);
-    if (reads.db) cdm_seqdb_free(reads.db);
-    cdm_ctx_destroy(ctx);
-    return EXIT_SUCCESS;
+    return contigReport(a, "contig_breaks", true, "Usage: carpedeam contig_breaks <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--break-anchor 16] [--break-edge 50] [--min-span 1] [--min-span-percent 0] "
+                        "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--min-seq-id 0.9] [-k 20]", BREAK_FLAGS, [&](PileAsk &ask) {
+        o.opt = breakOpts(a, "contig_breaks");
+        o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
+        o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
+        ask.breaks = &o;
+    });
 }
 int readsLoop(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
@@ -1985,12 +1960,13 @@ int assembleFused(Args &a) {
     // loop started from (contig_damage's four steps on the resident reads); without the flag nothing is kept resident and no call is made
     const bool report = a.flag.count("--damage-report") != 0;
     const std::string reportFile = report ? a.flag["--damage-report"] : "";
-    const long reportEnds = damageEnds(a, "ancient_assemble_fused");
+    PileAsk ask;
+    ask.damageOut = report ? &reportFile : NULL; ask.ends = damageEnds(a, "ancient_assemble_fused");
     // --depth-report <file>: likewise contig_depth's table of the final representatives against those reads; with both flags the two
     // reductions read one alignment set
     const bool depthRep = a.flag.count("--depth-report") != 0;
     const std::string depthFile = depthRep ? a.flag["--depth-report"] : "";
-    const long reportEdge = depthEdge(a, "ancient_assemble_fused");
+    ask.depthOut = depthRep ? &depthFile : NULL; ask.edge = depthEdge(a, "ancient_assemble_fused");
     // --variant-report <file> [--variant-sites <file>]: likewise contig_variants' summary and sites of the final representatives (no
     // consensus FASTA: that would be a second assembly output)
     const bool variantRep = a.flag.count("--variant-report") != 0;
@@ -1999,7 +1975,7 @@ int assembleFused(Args &a) {
     VariantOut variantOut;
     variantOut.opt = variantOpts(a, "ancient_assemble_fused");
     variantOut.summary = &variantFile; variantOut.sites = variantSites.empty() ? NULL : &variantSites; variantOut.consensus = NULL;
-    const VariantOut *const variants = variantRep ? &variantOut : NULL;
+    ask.variants = variantRep ? &variantOut : NULL;
     // --break-report <file>: likewise contig_breaks' summary and break records of the final representatives (no split FASTA: that would
     // be a second assembly output)
     const bool breakRep = a.flag.count("--break-report") != 0;
@@ -2007,7 +1983,7 @@ int assembleFused(Args &a) {
     BreakOut breakOut;
     breakOut.opt = breakOpts(a, "ancient_assemble_fused");
     breakOut.minPiece = 1; breakOut.summary = &breakFile; breakOut.split = NULL; breakOut.track = NULL;
-    const BreakOut *const breakPts = breakRep ? &breakOut : NULL;
+    ask.breaks = breakRep ? &breakOut : NULL;
     const bool anyReport = report || depthRep || variantRep || breakRep;
     // (the parameter strings are split at blanks again, and linclust's filterdb carries a path under <tmpDir> in its string)
     if (tmpDir.find_first_of(" \t\n") != std::string::npos) die("ancient_assemble_fused: a <tmpDir> with white space in its name is not taken: " + tmpDir);
@@ -2055,7 +2031,7 @@ int assembleFused(Args &a) {
         // nothing to reduce: the reference's whole program ends with status 0 and an empty FASTA here (tests/golden/fused/cases.json)
         cdm_seqdb_free(selected);
         if (!writeText(outFile, "")) die("Could not write " + outFile);
-        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, breakPts, laps); cdm_seqdb_free(E.reads); }
+        if (anyReport) { pileReports(ctx, NULL, NULL, 20, 0.9f, ask, laps); cdm_seqdb_free(E.reads); }
         cdm_ctx_destroy(ctx);
         if (removeTmp) removeOwnDir(T);
         return EXIT_SUCCESS;
@@ -2146,7 +2122,7 @@ int assembleFused(Args &a) {
     if (anyReport) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
         DamageInput contigs;
         const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
-        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, report ? &reportFile : NULL, reportEnds, depthRep ? &depthFile : NULL, reportEdge, NULL, variants, breakPts, laps);
+        pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, ask, laps);
         if (contigs.db) cdm_seqdb_free(contigs.db);
         cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);
     }

@@ -378,7 +378,7 @@ int cdm_pileup_profile(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, 
                        const cdm_pileup_params *par, uint64_t *counts, uint64_t *reads, uint64_t *columns);
 
 /* ---------------------------------------------------------------------------------------------------------
- * Depth of coverage at every position of the listed queries, and its statistics (not a module of the reference; csrc/pileup.hip).
+ * Depth of coverage at every position of the listed queries, and its statistics (not a module of the reference; csrc/pileup_depth.hip).
  * A record r of a listed query q of `len` letters counts under exactly the rule of cdm_pileup_profile: r.target != q,
  * r.seq_id >= min_seq_id (float against float), with skip_extended_targets the target's wasExtended flag is 0, and the oriented
  * record fits both sequences.  The oriented record covers the query positions qs..qe; depth[i] = the number of counted records with
@@ -405,7 +405,7 @@ int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, co
                      const cdm_depth_params *par, uint64_t *stats, uint32_t *depth);
 
 /* ---------------------------------------------------------------------------------------------------------
- * Per-position base counts and variant sites of the read pile-up (not a module of the reference; csrc/pileup.hip): which bases the
+ * Per-position base counts and variant sites of the read pile-up (not a module of the reference; csrc/pileup_bases.hip): which bases the
  * reads put on every position of the listed queries, and the positions where that disagrees with the query or among the reads.
  * A record counts under exactly the rule of cdm_pileup_profile and cdm_pileup_depth.  Column c = i - qs of a counted, oriented record
  * on query position i: op = ds + c, p = rev ? tLen - 1 - op : op the position in the read's own orientation.  The column is left out
@@ -453,7 +453,7 @@ int  cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, c
 void cdm_sites_free(cdm_site *sites);
 
 /* ---------------------------------------------------------------------------------------------------------
- * Contig break points from spanning reads (not a module of the reference; csrc/pileup.hip): is a query one molecule, or two stitched
+ * Contig break points from spanning reads (not a module of the reference; csrc/pileup_depth.hip): is a query one molecule, or two stitched
  * together?  A read that crosses a false join collects mismatches on the far side and falls below the set's identity threshold, so
  * across a false join reads cover both flanks but none spans the boundary with a real anchor on either side - which depth cannot see.
  * A record counts under exactly the rule of the three reductions above; the oriented record covers the query positions qs..qe.
