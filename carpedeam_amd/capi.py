@@ -118,6 +118,20 @@ BREAK_DTYPE = np.dtype([(n, "<u4") for n in ("query", "first", "last", "min_span
 BREAK_JOIN, BREAK_GAP = 1, 2
 
 
+class MapParams(C.Structure):
+    """cdm_map_params: the records' identity threshold, reads only as targets"""
+    _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
+class MapRec(C.Structure):
+    """cdm_map_rec: one read on one query"""
+    _fields_ = [(n, C.c_uint32) for n in ("query", "target", "pos", "columns", "tstart", "tlen", "nm", "flags")] + [("mm", C.c_uint64)]
+
+
+MAP_DTYPE = np.dtype([(n, "<u4") for n in ("query", "target", "pos", "columns", "tstart", "tlen", "nm", "flags")] + [("mm", "<u8")])
+MAP_REVERSE, MAP_SECONDARY = 1, 2
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -129,7 +143,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -251,6 +265,9 @@ def lib():
         l.cdm_pileup_breaks.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(BreaksParams), vp, vp, C.POINTER(C.POINTER(Break)), u64p, C.POINTER(C.c_float)]
         l.cdm_breaks_free.argtypes = [C.POINTER(Break)]
         l.cdm_breaks_free.restype = None
+        l.cdm_pileup_map.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(MapParams), vp, C.POINTER(C.POINTER(MapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(C.c_float)]
+        l.cdm_map_free.argtypes = [C.POINTER(MapRec), u32p]
+        l.cdm_map_free.restype = None
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -773,6 +790,31 @@ class Ctx:
                 lib().cdm_breaks_free(ptr)
             out.append(recs)
         return out[0] if len(out) == 1 else tuple(out)
+
+    def pileup_map(self, db, alns, queries, min_seq_id=0.0, skip_extended_targets=False, records=False):
+        """the reads on the listed queries as alignment records (cdm_pileup_map) -> stats[nq, 4] uint64: reads, columns, mismatches,
+        primary; with records (stats, recs, mism): the records as an array of MAP_DTYPE in listed query order, then by pos, then in the
+        set's order, and their mismatch words (uint32: column | ref << 24 | read << 28).  self.map_kernel_ms holds the device time of
+        the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 4), np.uint64)
+        par = MapParams(float(min_seq_id), int(bool(skip_extended_targets)))
+        ptr, words, n_recs, n_words, ms = C.POINTER(MapRec)(), C.POINTER(C.c_uint32)(), C.c_uint64(0), C.c_uint64(0), C.c_float(0.0)
+        _check(lib().cdm_pileup_map(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), C.byref(ptr) if records else None,
+                                    C.byref(n_recs) if records else None, C.byref(words) if records else None, C.byref(n_words) if records else None, C.byref(ms)))
+        self.map_kernel_ms = float(ms.value)
+        if not records:
+            return stats
+        n, nw = int(n_recs.value), int(n_words.value)
+        assert (n == 0) == (not ptr) and (nw == 0) == (not words)
+        recs, mism = np.empty(n, MAP_DTYPE), np.empty(nw, np.uint32)
+        if n:
+            C.memmove(recs.ctypes.data, ptr, n * C.sizeof(MapRec))
+        if nw:
+            C.memmove(mism.ctypes.data, words, nw * 4)
+        lib().cdm_map_free(ptr, words)
+        return stats, recs, mism
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

@@ -40,6 +40,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_variants",
                                     /* contig break points from the spanning reads of the same pile-up: not a module of the reference either */
                                     "contig_breaks",
+                                    /* the reads on the contigs as a SAM file, the records of the same pile-up: not a module of the reference either */
+                                    "contig_map",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

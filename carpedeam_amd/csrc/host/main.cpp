@@ -1552,20 +1552,117 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
     if (o.split && !writeText(*o.split, fasta)) die("Could not write " + *o.split);
     if (o.track && !writeText(*o.track, bed)) die("Could not write " + *o.track);
 }
+// ---- contig_map: the reads on the contigs as a SAM file (not a module of the reference).  The three calls above, then cdm_pileup_map
+// over the contigs: one line per counted record in coordinate order, soft clips around the overlap, NM and MD from the mismatch
+// words, one primary line per read.  SEQ is the read as the device compared it - the letters its codes and N bits stand for - so SEQ,
+// CIGAR and MD agree by construction.  As with the four reports the records are seeded UNGAPPED overlaps at the identity threshold:
+// no insertions or deletions, no line for a read that seeds nowhere.
+const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// what a map report writes: the SAM file, with the read group when one is named, without the secondary lines when asked
+struct MapOut { const std::string *sam; const std::string *readGroup; bool primaryOnly; };
+// SAM names a reference sequence once: two contigs of one name end the command
+void mapCheckNames(const DamageInput &contigs) {
+    std::vector<std::string> names; std::string tmp;
+    for (uint64_t i = 0; i < contigs.keys.size(); i++) names.push_back(contigName(contigs, i, tmp));
+    std::sort(names.begin(), names.end());
+    for (size_t i = 1; i < names.size(); i++)
+        if (names[i] == names[i - 1]) die("contig_map: two contigs are named " + names[i] + "; a SAM file can not tell them apart");
+}
+void putNumber(std::string &to, unsigned long long v) { char num[32]; to.append(num, (size_t) (utoa(v, num) - num)); }
+// no contigs: the header lines without @SQ
+void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *reads, const PileSet &ps, const MapOut &o, Laps &laps) {
+    std::string text = "@HD\tVN:1.6\tSO:coordinate\n", tmp;
+    std::vector<uint32_t> lens;
+    std::vector<std::string> part;        // the record lines, a chunk a host thread
+    const uint64_t nc = haveContigs(contigs) ? cdm_seqdb_size(contigs->db) : 0;
+    if (nc) {
+        lens.resize(nc);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        for (uint64_t i = 0; i < nc; i++) { text += "@SQ\tSN:"; text += contigName(*contigs, i, tmp); text += "\tLN:"; putNumber(text, lens[i]); text.push_back('\n'); }
+    }
+    if (o.readGroup) text += "@RG\tID:" + *o.readGroup + "\n";
+    text += "@PG\tID:carpedeam\tPN:carpedeam\n";
+    if (nc) {
+        std::vector<uint32_t> q(nc);
+        std::iota(q.begin(), q.end(), 0u);
+        std::vector<uint64_t> stats(nc * 4);
+        cdm_map_params mp; mp.min_seq_id = 0.0f; mp.skip_extended_targets = 1;
+        cdm_map_rec *recs = NULL; uint32_t *mism = NULL; uint64_t nRecs = 0, nMism = 0; float ms = 0.f;
+        check(cdm_pileup_map(ctx, ps.both, ps.alns, q.data(), nc, &mp, stats.data(), &recs, &nRecs, &mism, &nMism, &ms), "pile-up map");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  map report: %llu records, %llu lines, %llu mismatches, map kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nRecs, (unsigned long long) nMism, ms);
+        // the reads as the device compared them: their packed codes and N bits come down, no byte of the input is looked at
+        const uint64_t nr = cdm_seqdb_size(reads->db), words = cdm_seqdb_words(reads->db);
+        std::vector<uint32_t> rlens(nr), codes(words + 1); std::vector<uint16_t> nbits(words + 1);
+        check(cdm_seqdb_export_packed(ctx, reads->db, codes.data(), nbits.data(), rlens.data(), NULL, NULL, NULL, NULL), "download of the reads");
+        std::vector<uint64_t> woff(nr + 1, 0);        // (every sequence starts on a word boundary: 16 letters a code word, 16 N bits beside it)
+        for (uint64_t i = 0; i < nr; i++) woff[i + 1] = woff[i] + (rlens[i] + 15u) / 16u;
+        // the lines on the host threads, in contiguous chunks of records
+        const int T = std::max(1, omp_get_max_threads());
+        part.resize((size_t) T);
+        static const char LETTER[] = "ACGTN";
+#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the chunks: a smaller team still visits them all
+        for (int t = 0; t < T; t++) {
+            std::string &to = part[(size_t) t]; std::string name;
+            for (uint64_t k = nRecs * (uint64_t) t / (uint64_t) T, end = nRecs * (uint64_t) (t + 1) / (uint64_t) T; k < end; k++) {
+                const cdm_map_rec &r = recs[k];
+                if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
+                const uint64_t read = (uint64_t) r.target - nc;       // (reads only as targets: behind the contigs in the joint DB)
+                const bool rev = (r.flags & CDM_MAP_REVERSE) != 0;
+                to += contigName(*reads, read, name);
+                to.push_back('\t'); putNumber(to, (rev ? 16u : 0u) | (r.flags & CDM_MAP_SECONDARY ? 256u : 0u));
+                to.push_back('\t'); to += contigName(*contigs, r.query, name);
+                to.push_back('\t'); putNumber(to, (unsigned long long) r.pos + 1);
+                to += "\t255\t";
+                const uint32_t right = r.tlen - r.tstart - r.columns;
+                if (r.tstart) { putNumber(to, r.tstart); to.push_back('S'); }
+                putNumber(to, r.columns); to.push_back('M');
+                if (right) { putNumber(to, right); to.push_back('S'); }
+                to += "\t*\t0\t0\t";
+                const uint32_t *cw = codes.data() + woff[read]; const uint16_t *nw = nbits.data() + woff[read];
+                for (uint32_t i = 0; i < r.tlen; i++) {       // the read in the contig's orientation: complemented from its end when reverse
+                    const uint32_t p = rev ? r.tlen - 1u - i : i, b = (cw[p >> 4] >> ((p & 15u) * 2u)) & 3u;
+                    to.push_back((nw[p >> 4] >> (p & 15u)) & 1u ? 'N' : LETTER[rev ? 3u - b : b]);
+                }
+                to += "\t*\tNM:i:"; putNumber(to, r.nm);
+                to += "\tMD:Z:";
+                uint32_t from = 0;
+                for (uint32_t j = 0; j < r.nm; j++) {       // the matches in front of a mismatch, then the contig's letter there
+                    const uint32_t w = mism[r.mm + j], c = w & 0xFFFFFFu;
+                    putNumber(to, c - from); to.push_back(LETTER[std::min(4u, (w >> 24) & 15u)]);
+                    from = c + 1u;
+                }
+                putNumber(to, r.columns - from);
+                if (o.readGroup) { to += "\tRG:Z:"; to += *o.readGroup; }
+                to.push_back('\n');
+            }
+        }
+        cdm_map_free(recs, mism);
+        laps.lap("map report: records, lines");
+    }
+    // the header, then the chunks in order: the text is never joined in memory
+    FILE *f = fopen(o.sam->c_str(), "w");
+    bool ok = f != NULL && fwrite(text.data(), 1, text.size(), f) == text.size();
+    for (size_t t = 0; ok && t < part.size(); t++) { ok = fwrite(part[t].data(), 1, part[t].size(), f) == part[t].size(); std::string().swap(part[t]); }
+    if (f && fclose(f) != 0) ok = false;
+    if (!ok) die("Could not write " + *o.sam);
+}
 // What a pileReports call is asked for (NULL: not asked for): the damage table with its ends, the depth table with its edge and
-// track, the variant and the break reports.
+// track, the variant and the break reports, the map report with the read set whose names and letters its lines carry.
 struct PileAsk {
     const std::string *damageOut = NULL; long ends = 0;
     const std::string *depthOut = NULL; long edge = 0; const std::string *trackOut = NULL;
     const VariantOut *variants = NULL; const BreakOut *breaks = NULL;
+    const MapOut *map = NULL; const DamageInput *mapReads = NULL;
 };
 // The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
 // alignment set.  contigs == NULL: the header lines alone.  Neither DB is freed here.
 void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const PileAsk &ask, Laps &laps) {
     PileSet ps;
     if (haveContigs(contigs)) {
+        if (ask.map) mapCheckNames(*contigs);
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
-        laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" : "break report: kmermatcher, rescorediagonal");
+        laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" :
+                 ask.breaks ? "break report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
     }
     if (ask.damageOut) damageTable(ctx, contigs, ps, ask.ends, *ask.damageOut, laps);
     if (ask.depthOut) {
@@ -1577,6 +1674,7 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
     }
     if (ask.variants) variantReport(ctx, contigs, ps, *ask.variants, laps);
     if (ask.breaks) breakReport(ctx, contigs, ps, *ask.breaks, laps);
+    if (ask.map) mapReport(ctx, contigs, ask.mapReads, ps, *ask.map, laps);
     freePileSet(ps);
 }
 // The commands with one read set: exactly (or at least) three positional arguments or the usage line, the flag check, what the
@@ -1590,7 +1688,8 @@ template <class Fill> int contigReport(Args &a, const char *module, bool exactly
     cdm_ctx *ctx = openCtx();
     DamageInput contigs, reads;
     const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (have && !loadDamageInput(ctx, a.pos[1], true, false, reads)) die(std::string(module) + ": " + a.pos[1] + " holds no reads");
+    if (have && !loadDamageInput(ctx, a.pos[1], true, ask.map != NULL, reads)) die(std::string(module) + ": " + a.pos[1] + " holds no reads");      // (the map's lines carry the reads' names)
+    ask.mapReads = &reads;
     laps.lap("inputs read, sequences up");
     pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), ask, laps);
     if (contigs.db) cdm_seqdb_free(contigs.db);
@@ -1649,6 +1748,18 @@ int contigBreaks(Args &a) {
         o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
         o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
         ask.breaks = &o;
+    });
+}
+int contigMap(Args &a) {
+    MapOut o;
+    return contigReport(a, "contig_map", true, "Usage: carpedeam contig_map <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:samFile> [--read-group <id>] [--primary-only 0] [--min-seq-id 0.9] [-k 20] [--threads N]",
+                        MAP_FLAGS, [&](PileAsk &ask) {
+        o.primaryOnly = rangedFlag(a, "contig_map", "--primary-only", 0, 0, 1, "0 writes every line, 1 leaves the secondary lines out") != 0;
+        o.readGroup = a.flag.count("--read-group") ? &a.flag["--read-group"] : NULL;
+        if (o.readGroup && (o.readGroup->empty() || o.readGroup->find('\t') != std::string::npos))
+            unsupported("contig_map: --read-group \"" + *o.readGroup + "\" is not supported by the MI355X path (a read group's ID is at least one character and holds no tab)");
+        o.sam = &a.pos[2];
+        ask.map = &o;
     });
 }
 int readsLoop(Args &a) {
@@ -2152,7 +2263,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|contig_breaks|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|contig_breaks|contig_map|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -2174,6 +2285,7 @@ int main(int argc, char **argv) {
     else if (cmd == "contig_depth") rc = contigDepth(a);
     else if (cmd == "contig_variants") rc = contigVariants(a);
     else if (cmd == "contig_breaks") rc = contigBreaks(a);
+    else if (cmd == "contig_map") rc = contigMap(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

@@ -1,7 +1,8 @@
 // What the reductions over the read pile-up share (pileup.hip: cdm_pileup_profile; pileup_depth.hip: cdm_pileup_depth and
-// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases): the rule by which a record counts, the work items (listed query, chunk of
-// its records) and the tiles (listed query, DP_TILE positions) with their lookups, and the host steps of a call - query sizes, batch
-// cut, work items, sliced launches, the timed synchronisation, the caller's record array.  Every step is defined here once.
+// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map): the rule by which a record counts, the
+// work items (listed query, chunk of its records) and the tiles (listed query, DP_TILE positions) with their lookups, and the host
+// steps of a call - query sizes, batch cut, work items, sliced launches, the timed synchronisation, the caller's record array.  Every
+// step is defined here once.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -130,15 +131,16 @@ int pileupCheckArgs(const char *who, const cdm_seqdb *db, const cdm_alns *alns, 
     return CDM_OK;
 }
 
-// (a) The DB's metadata and the listed queries on the device, the queries' lengths on the host; a query with 2^32 records or more is
-// refused (the 32-bit `what` of `who` hold fewer).  One stream synchronisation behind cdm_build_meta's own.
-struct QuerySizes { DevBuf<SeqMeta> meta; DevBuf<uint32_t> dq; std::vector<uint32_t> len; };
+// (a) The DB's metadata and the listed queries on the device, the queries' lengths and record counts on the host; a query with 2^32
+// records or more is refused (the 32-bit `what` of `who` hold fewer).  One stream synchronisation behind cdm_build_meta's own.
+struct QuerySizes { DevBuf<SeqMeta> meta; DevBuf<uint32_t> dq; std::vector<uint32_t> len; std::vector<uint64_t> recs; };
 int querySizes(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const char *who, const char *what, QuerySizes &qs) {
     hipStream_t s = ctx->stream;
     if (int rc = cdm_build_meta(ctx, db, &qs.meta.p)) return rc;
     DevBuf<uint32_t> dLen; DevBuf<uint64_t> dRecs;
     if (!qs.dq.alloc(nq) || !dLen.alloc(nq) || !dRecs.alloc(nq)) { cdm_set_error("%s: out of device memory for %llu queries", who, (unsigned long long) nq); return CDM_ERR_HIP; }
-    qs.len.resize(nq); std::vector<uint64_t> recs(nq);
+    qs.len.resize(nq); qs.recs.resize(nq);
+    std::vector<uint64_t> &recs = qs.recs;
     CDM_HIP(hipMemcpyAsync(qs.dq.p, queries, (size_t) nq * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_depth_sizes, CDM_GRID((nq + 255) / 256, 256), dim3(256), 0, s, (const SeqMeta *) qs.meta.p, (const uint64_t *) alns->off, (const uint32_t *) qs.dq.p, nq, dLen.p, dRecs.p);
     CDM_LAUNCH_CHECK();

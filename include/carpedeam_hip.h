@@ -501,6 +501,54 @@ int  cdm_pileup_breaks(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, 
 void cdm_breaks_free(cdm_break *breaks);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The reads on the queries as alignment records (not a module of the reference; csrc/pileup_map.hip): the pile-up itself, completed
+ * with what a SAM line needs and the alignment set does not carry.  A record counts under exactly the rule of the four reductions
+ * above.  One cdm_map_rec per counted record of a listed query, from its oriented form (qs, qe, ds, de; reverse when qStart > qEnd):
+ *   query    the index into `queries`                      target   the read's index in db
+ *   pos      qs, 0-based                                   columns  qe - qs + 1
+ *   tstart   the oriented ds: the letters of the read, in the query's orientation, in front of the overlap
+ *   tlen     the read's length                             flags    CDM_MAP_REVERSE iff the record is reverse; CDM_MAP_SECONDARY below
+ * Letters are the mapped codes and N bits of the DB, never the raw plane.  Column c, 0 <= c < columns, sits on query position pos + c:
+ *   ref      the query's code there (A,C,G,T = 0..3), or 4 when its N bit is set
+ *   read     the read's code at p = reverse ? tlen - 1 - (tstart + c) : tstart + c, complemented (3 - code) when reverse, or 4 when
+ *            the read's N bit is set at p
+ *   the column is a mismatch iff ref == 4 || read == 4 || ref != read (the rule of samtools calmd: an N matches nothing)
+ *   nm       the number of mismatch columns
+ *   mm       the index of the record's first word in `mism`; the record owns nm words there, ascending in c, each
+ *            c | ref << 24 | read << 28 (sequences of 4 M letters and more are refused at upload, so c fits 24 bits)
+ * Order: listed query order, then ascending pos, then the order the records have in the alignment set (stable).  The mismatch words
+ * follow the same order, so mm is the running sum of nm.
+ * Primary and secondary: per target, over all its counted records on all listed queries OF THE CALL, the primary is the one with the
+ * most columns, among equals the one with the smallest index in the set's record array; every other record of that target carries
+ * CDM_MAP_SECONDARY.  Records on queries that are not listed take no part.
+ *   stats   n_queries x 4 uint64, per listed query:
+ *             0 reads, 1 columns   cdm_pileup_depth's values       2 mismatches  sum of nm       3 primary  records without the
+ *             secondary flag
+ *   recs    NULL (statistics only), or receives a malloc'ed array of the records; *n_recs = their number; none: *recs = NULL,
+ *           *n_recs = 0
+ *   mism    NULL only when recs is; receives a malloc'ed array of the mismatch words; *n_mism = their number; none: *mism = NULL.
+ *           Both arrays are released with cdm_map_free (either may be NULL).  n_recs and n_mism may be NULL only when recs is.  The
+ *           arrays are the caller's only when the call returns CDM_OK
+ *   kernel_ms  NULL, or receives the device time of the kernels
+ * A NULL argument, a query index >= the DB's size or listed twice is CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched);
+ * a set with the coordinates -1 record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more is
+ * CDM_ERR_UNSUPPORTED (the record slots are 32 bits wide), and so is a set of 2^40 records or more (the primary is found with one
+ * 64-bit maximum per target of columns << 40 | (2^40 - 1 - record index)); neither is reachable at test size, neither is tested.
+ * The records are the set's seeded ungapped overlaps at its identity threshold, not a gapped mapping: no insertions or deletions, and
+ * no record where no read seeds. */
+#define CDM_MAP_REVERSE   1u
+#define CDM_MAP_SECONDARY 2u
+typedef struct cdm_map_params {
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_map_params;
+typedef struct cdm_map_rec { uint32_t query, target, pos, columns, tstart, tlen, nm, flags; uint64_t mm; } cdm_map_rec;   /* 40 bytes */
+int  cdm_pileup_map(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                    const cdm_map_params *par, uint64_t *stats, cdm_map_rec **recs, uint64_t *n_recs, uint32_t **mism, uint64_t *n_mism,
+                    float *kernel_ms);
+void cdm_map_free(cdm_map_rec *recs, uint32_t *mism);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
  * db must be the corrected DB.  Output: new sequence DB (extended sequences get ext=1, others are copied through).
  * scores (optional, may be NULL): for tests, the per-candidate likelihood of the first scoring round
