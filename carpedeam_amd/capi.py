@@ -132,6 +132,28 @@ MAP_DTYPE = np.dtype([(n, "<u4") for n in ("query", "target", "pos", "columns", 
 MAP_REVERSE, MAP_SECONDARY = 1, 2
 
 
+class GapParams(C.Structure):
+    """cdm_gap_params: the records' identity threshold, reads only as targets, the band, the two thresholds of a rescue, the scores"""
+    _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32), ("band", C.c_uint32), ("min_columns", C.c_uint32), ("min_id_permille", C.c_uint32),
+                ("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32)]
+
+    @classmethod
+    def default(cls, min_seq_id=0.0, skip_extended_targets=False, band=8, min_columns=32, min_id_permille=900, match=2, mismatch=-3, gap_open=5, gap_extend=2):
+        """the values `carpedeam contig_map --gapped 1` passes: nucleotide.out's scores, the gap costs of `align`"""
+        return cls(float(min_seq_id), int(bool(skip_extended_targets)), band, min_columns, min_id_permille, match, mismatch, gap_open, gap_extend)
+
+
+class GapRec(C.Structure):
+    """cdm_gap_rec: one rescued read on one query"""
+    _fields_ = [(n, C.c_uint32) for n in ("query", "target", "pos", "span", "tstart", "tlen", "columns", "nm", "flags", "n_ops", "n_words")] + [
+        ("score", C.c_int32), ("ops", C.c_uint64), ("words", C.c_uint64)]
+
+
+GAP_DTYPE = np.dtype([(n, "<u4") for n in ("query", "target", "pos", "span", "tstart", "tlen", "columns", "nm", "flags", "n_ops", "n_words")] + [
+    ("score", "<i4"), ("ops", "<u8"), ("words", "<u8")])
+GAP_OP_M, GAP_OP_I, GAP_OP_D = 0, 1, 2
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -143,7 +165,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -268,6 +290,10 @@ def lib():
         l.cdm_pileup_map.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(MapParams), vp, C.POINTER(C.POINTER(MapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(C.c_float)]
         l.cdm_map_free.argtypes = [C.POINTER(MapRec), u32p]
         l.cdm_map_free.restype = None
+        l.cdm_pileup_gapped.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(GapParams), vp, C.POINTER(C.POINTER(GapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(u32p), u64p,
+                                        C.POINTER(C.c_float)]
+        l.cdm_gap_free.argtypes = [C.POINTER(GapRec), u32p, u32p]
+        l.cdm_gap_free.restype = None
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -815,6 +841,36 @@ class Ctx:
             C.memmove(mism.ctypes.data, words, nw * 4)
         lib().cdm_map_free(ptr, words)
         return stats, recs, mism
+
+    def pileup_gapped(self, db, hits, alns, queries, par=None, records=False):
+        """the reads across insertions and deletions (cdm_pileup_gapped): the banded gapped alignment of the hits of the listed queries
+        that left no counted record -> stats[nq, 4] uint64: candidates, rescued, gap_letters, too_long; with records (stats, recs, ops,
+        words): the rescued as an array of GAP_DTYPE in listed query order, then by pos, then in hit order, their operation words
+        (uint32: length << 2 | op) and their mismatch / deletion words (uint32: offset | ref << 24 | read << 28, read 15 = deleted).
+        self.gapped_kernel_ms holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 4), np.uint64)
+        par = par or GapParams.default()
+        ptr, ops, words = C.POINTER(GapRec)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        n_recs, n_ops, n_words, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_float(0.0)
+        ref = (lambda x: C.byref(x)) if records else (lambda x: None)
+        _check(lib().cdm_pileup_gapped(self.h, db.h, hits.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), ref(ptr), ref(n_recs), ref(ops), ref(n_ops), ref(words), ref(n_words),
+                                       C.byref(ms)))
+        self.gapped_kernel_ms = float(ms.value)
+        if not records:
+            return stats
+        n, no, nw = int(n_recs.value), int(n_ops.value), int(n_words.value)
+        assert (n == 0) == (not ptr) and (no == 0) == (not ops) and (nw == 0) == (not words)
+        recs, o, w = np.empty(n, GAP_DTYPE), np.empty(no, np.uint32), np.empty(nw, np.uint32)
+        if n:
+            C.memmove(recs.ctypes.data, ptr, n * C.sizeof(GapRec))
+        if no:
+            C.memmove(o.ctypes.data, ops, no * 4)
+        if nw:
+            C.memmove(w.ctypes.data, words, nw * 4)
+        lib().cdm_gap_free(ptr, ops, words)
+        return stats, recs, o, w
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

@@ -1296,8 +1296,9 @@ bool loadDamageInput(cdm_ctx *ctx, const std::string &path, bool shuffle, bool w
 }
 // The three library calls the pile-up reports share: the contigs (wasExtended 1) and the reads (0) as one DB, kmermatcher and
 // rescorediagonal on it with the reads loop's flags.  The caller frees both results.
-struct PileSet { cdm_seqdb *both = NULL; cdm_alns *alns = NULL; };
-PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId) {
+// keepHits: the prefilter hits stay in the set (the gapped map looks at the ones rescorediagonal refused).
+struct PileSet { cdm_seqdb *both = NULL; cdm_alns *alns = NULL; cdm_hits *hits = NULL; };
+PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, bool keepHits = false) {
     PileSet p; cdm_hits *hits = NULL;
     check(cdm_seqdb_concat(ctx, contigs, reads, 1, 0, &p.both), "contigs and reads as one DB");
     cdm_kmer_params kp;         // the reads loop's kmermatcher flags (stageflags.K_FLAGS)
@@ -1306,10 +1307,10 @@ PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int
     rp.seq_id_thr = minSeqId; rp.eval_thr = 0.001; rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
     check(cdm_kmermatch(ctx, p.both, &kp, &hits), "kmermatcher");
     check(cdm_rescore(ctx, p.both, hits, &rp, &p.alns), "rescorediagonal");
-    cdm_hits_free(hits);
+    if (keepHits) p.hits = hits; else cdm_hits_free(hits);
     return p;
 }
-void freePileSet(PileSet &p) { if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
+void freePileSet(PileSet &p) { if (p.hits) cdm_hits_free(p.hits); if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
 bool haveContigs(const DamageInput *contigs) { return contigs && contigs->db && cdm_seqdb_size(contigs->db); }
 const std::string &contigName(const DamageInput &c, uint64_t i, std::string &tmp) { if (i < c.names.size()) return c.names[i]; tmp = std::to_string(c.keys[i]); return tmp; }
 // bedGraph lines of one contig's runs of equal value, zero runs included: name, start, end (0-based, half-open), value
@@ -1556,10 +1557,12 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
 // over the contigs: one line per counted record in coordinate order, soft clips around the overlap, NM and MD from the mismatch
 // words, one primary line per read.  SEQ is the read as the device compared it - the letters its codes and N bits stand for - so SEQ,
 // CIGAR and MD agree by construction.  As with the four reports the records are seeded UNGAPPED overlaps at the identity threshold:
-// no insertions or deletions, no line for a read that seeds nowhere.
-const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// no insertions or deletions, no line for a read that seeds nowhere.  --gapped 1 adds the seeded pairs that test refused: cdm_pileup_gapped
+// aligns them across insertions and deletions within a band, and the rescued reads come as lines of their own (CIGAR with I and D, MD
+// with ^, a trailing XG:i:<gap letters>), merged into the others by (contig, position), the ungapped line first on equal keys.
+const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 // what a map report writes: the SAM file, with the read group when one is named, without the secondary lines when asked
-struct MapOut { const std::string *sam; const std::string *readGroup; bool primaryOnly; };
+struct MapOut { const std::string *sam; const std::string *readGroup; bool primaryOnly; bool gapped = false; long gapBand = 8, gapMinColumns = 32; float minSeqId = 0.9f; };
 // SAM names a reference sequence once: two contigs of one name end the command
 void mapCheckNames(const DamageInput &contigs) {
     std::vector<std::string> names; std::string tmp;
@@ -1590,6 +1593,29 @@ void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *read
         cdm_map_rec *recs = NULL; uint32_t *mism = NULL; uint64_t nRecs = 0, nMism = 0; float ms = 0.f;
         check(cdm_pileup_map(ctx, ps.both, ps.alns, q.data(), nc, &mp, stats.data(), &recs, &nRecs, &mism, &nMism, &ms), "pile-up map");
         if (getenv("CDM_TIMING")) fprintf(stderr, "  map report: %llu records, %llu lines, %llu mismatches, map kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nRecs, (unsigned long long) nMism, ms);
+        // --gapped 1: the rescued reads, and the order of the two streams merged by (contig, pos), an ungapped record first on equal keys
+        // (entry: index << 1 | rescued)
+        cdm_gap_rec *grecs = NULL; uint32_t *gops = NULL, *gwords = NULL; uint64_t nGap = 0, nGops = 0, nGwords = 0;
+        std::vector<uint64_t> merged;
+        if (o.gapped) {
+            cdm_gap_params gp;        // nucleotide.out's scores and the gap costs of `align`
+            gp.min_seq_id = mp.min_seq_id; gp.skip_extended_targets = mp.skip_extended_targets; gp.band = (uint32_t) o.gapBand; gp.min_columns = (uint32_t) o.gapMinColumns;
+            gp.min_id_permille = (uint32_t) (o.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
+            std::vector<uint64_t> gstats(nc * 4);
+            float gms = 0.f;
+            check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), nc, &gp, gstats.data(), &grecs, &nGap, &gops, &nGops, &gwords, &nGwords, &gms), "gapped pile-up");
+            if (getenv("CDM_TIMING")) {
+                uint64_t cand = 0, gaps = 0;
+                for (uint64_t i = 0; i < nc; i++) { cand += gstats[i * 4]; gaps += gstats[i * 4 + 2]; }
+                fprintf(stderr, "  map report: %llu refused hits aligned, %llu rescued with %llu gap letters, gapped kernels %.3f ms\n", (unsigned long long) cand, (unsigned long long) nGap, (unsigned long long) gaps, gms);
+            }
+            merged.reserve(nRecs + nGap);
+            for (uint64_t i = 0, j = 0; i < nRecs || j < nGap;) {
+                const bool plain = j == nGap || (i < nRecs && (recs[i].query < grecs[j].query || (recs[i].query == grecs[j].query && recs[i].pos <= grecs[j].pos)));
+                merged.push_back(plain ? i++ << 1 : j++ << 1 | 1u);
+            }
+        }
+        const uint64_t nLines = nRecs + nGap;
         // the reads as the device compared them: their packed codes and N bits come down, no byte of the input is looked at
         const uint64_t nr = cdm_seqdb_size(reads->db), words = cdm_seqdb_words(reads->db);
         std::vector<uint32_t> rlens(nr), codes(words + 1); std::vector<uint16_t> nbits(words + 1);
@@ -1603,26 +1629,61 @@ void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *read
 #pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the chunks: a smaller team still visits them all
         for (int t = 0; t < T; t++) {
             std::string &to = part[(size_t) t]; std::string name;
-            for (uint64_t k = nRecs * (uint64_t) t / (uint64_t) T, end = nRecs * (uint64_t) (t + 1) / (uint64_t) T; k < end; k++) {
-                const cdm_map_rec &r = recs[k];
-                if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
-                const uint64_t read = (uint64_t) r.target - nc;       // (reads only as targets: behind the contigs in the joint DB)
-                const bool rev = (r.flags & CDM_MAP_REVERSE) != 0;
-                to += contigName(*reads, read, name);
-                to.push_back('\t'); putNumber(to, (rev ? 16u : 0u) | (r.flags & CDM_MAP_SECONDARY ? 256u : 0u));
-                to.push_back('\t'); to += contigName(*contigs, r.query, name);
-                to.push_back('\t'); putNumber(to, (unsigned long long) r.pos + 1);
+            // what the two kinds of line share: QNAME to MAPQ in front of CIGAR, and RNEXT to QUAL behind it
+            auto lineHead = [&](uint32_t target, uint32_t flags, uint32_t query, uint32_t pos) {
+                to += contigName(*reads, (uint64_t) target - nc, name);       // (reads only as targets: behind the contigs in the joint DB)
+                to.push_back('\t'); putNumber(to, (flags & CDM_MAP_REVERSE ? 16u : 0u) | (flags & CDM_MAP_SECONDARY ? 256u : 0u));
+                to.push_back('\t'); to += contigName(*contigs, query, name);
+                to.push_back('\t'); putNumber(to, (unsigned long long) pos + 1);
                 to += "\t255\t";
+            };
+            auto lineSeq = [&](uint32_t target, uint32_t tlen, bool rev) {
+                const uint64_t read = (uint64_t) target - nc;
+                to += "\t*\t0\t0\t";
+                const uint32_t *cw = codes.data() + woff[read]; const uint16_t *nw = nbits.data() + woff[read];
+                for (uint32_t i = 0; i < tlen; i++) {       // the read in the contig's orientation: complemented from its end when reverse
+                    const uint32_t p = rev ? tlen - 1u - i : i, b = (cw[p >> 4] >> ((p & 15u) * 2u)) & 3u;
+                    to.push_back((nw[p >> 4] >> (p & 15u)) & 1u ? 'N' : LETTER[rev ? 3u - b : b]);
+                }
+            };
+            for (uint64_t k = nLines * (uint64_t) t / (uint64_t) T, end = nLines * (uint64_t) (t + 1) / (uint64_t) T; k < end; k++) {
+                const uint64_t entry = o.gapped ? merged[k] : k << 1;
+                if (entry & 1u) {       // a rescued read: CIGAR from its operations, MD with ^ from its words, XG the gap letters
+                    const cdm_gap_rec &r = grecs[entry >> 1];
+                    if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
+                    lineHead(r.target, r.flags, r.query, r.pos);
+                    if (r.tstart) { putNumber(to, r.tstart); to.push_back('S'); }
+                    uint32_t gaps = 0;
+                    for (uint32_t j = 0; j < r.n_ops; j++) {
+                        const uint32_t w = gops[r.ops + j];
+                        putNumber(to, w >> 2); to.push_back("MID"[w & 3u]);
+                        if (w & 3u) gaps += w >> 2;
+                    }
+                    if (const uint32_t right = r.tlen - r.tstart - r.columns) { putNumber(to, right); to.push_back('S'); }
+                    lineSeq(r.target, r.tlen, (r.flags & CDM_MAP_REVERSE) != 0);
+                    to += "\t*\tNM:i:"; putNumber(to, r.nm);
+                    to += "\tMD:Z:";
+                    uint32_t from = 0; bool inDeletion = false;
+                    for (uint32_t j = 0; j < r.n_words; j++) {      // a deleted letter joins the ^ in front of it when it follows a deleted letter on the contig
+                        const uint32_t w = gwords[r.words + j], c = w & 0xFFFFFFu; const bool deleted = (w >> 28) == 15u;
+                        if (!(deleted && inDeletion && c == from)) { putNumber(to, c - from); if (deleted) to.push_back('^'); }
+                        to.push_back(LETTER[std::min(4u, (w >> 24) & 15u)]);
+                        from = c + 1u; inDeletion = deleted;
+                    }
+                    putNumber(to, r.span - from);
+                    if (o.readGroup) { to += "\tRG:Z:"; to += *o.readGroup; }
+                    to += "\tXG:i:"; putNumber(to, gaps);
+                    to.push_back('\n');
+                    continue;
+                }
+                const cdm_map_rec &r = recs[entry >> 1];
+                if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
+                lineHead(r.target, r.flags, r.query, r.pos);
                 const uint32_t right = r.tlen - r.tstart - r.columns;
                 if (r.tstart) { putNumber(to, r.tstart); to.push_back('S'); }
                 putNumber(to, r.columns); to.push_back('M');
                 if (right) { putNumber(to, right); to.push_back('S'); }
-                to += "\t*\t0\t0\t";
-                const uint32_t *cw = codes.data() + woff[read]; const uint16_t *nw = nbits.data() + woff[read];
-                for (uint32_t i = 0; i < r.tlen; i++) {       // the read in the contig's orientation: complemented from its end when reverse
-                    const uint32_t p = rev ? r.tlen - 1u - i : i, b = (cw[p >> 4] >> ((p & 15u) * 2u)) & 3u;
-                    to.push_back((nw[p >> 4] >> (p & 15u)) & 1u ? 'N' : LETTER[rev ? 3u - b : b]);
-                }
+                lineSeq(r.target, r.tlen, (r.flags & CDM_MAP_REVERSE) != 0);
                 to += "\t*\tNM:i:"; putNumber(to, r.nm);
                 to += "\tMD:Z:";
                 uint32_t from = 0;
@@ -1636,6 +1697,7 @@ void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *read
                 to.push_back('\n');
             }
         }
+        cdm_gap_free(grecs, gops, gwords);
         cdm_map_free(recs, mism);
         laps.lap("map report: records, lines");
     }
@@ -1660,7 +1722,7 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
     PileSet ps;
     if (haveContigs(contigs)) {
         if (ask.map) mapCheckNames(*contigs);
-        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId);
+        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, ask.map && ask.map->gapped);
         laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" :
                  ask.breaks ? "break report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
     }
@@ -1752,12 +1814,18 @@ int contigBreaks(Args &a) {
 }
 int contigMap(Args &a) {
     MapOut o;
-    return contigReport(a, "contig_map", true, "Usage: carpedeam contig_map <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:samFile> [--read-group <id>] [--primary-only 0] [--min-seq-id 0.9] [-k 20] [--threads N]",
+    return contigReport(a, "contig_map", true, "Usage: carpedeam contig_map <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:samFile> [--read-group <id>] [--primary-only 0] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20] [--threads N]",
                         MAP_FLAGS, [&](PileAsk &ask) {
         o.primaryOnly = rangedFlag(a, "contig_map", "--primary-only", 0, 0, 1, "0 writes every line, 1 leaves the secondary lines out") != 0;
         o.readGroup = a.flag.count("--read-group") ? &a.flag["--read-group"] : NULL;
         if (o.readGroup && (o.readGroup->empty() || o.readGroup->find('\t') != std::string::npos))
             unsupported("contig_map: --read-group \"" + *o.readGroup + "\" is not supported by the MI355X path (a read group's ID is at least one character and holds no tab)");
+        o.gapped = rangedFlag(a, "contig_map", "--gapped", 0, 0, 1, "0 writes the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions") != 0;
+        for (const char *flag : {"--gap-band", "--gap-min-columns"})
+            if (!o.gapped && a.flag.count(flag)) unsupported(std::string("contig_map: ") + flag + " without --gapped 1 is not supported by the MI355X path (the flag sets the gapped alignment, which is off)");
+        o.gapBand = rangedFlag(a, "contig_map", "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
+        o.gapMinColumns = rangedFlag(a, "contig_map", "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
+        o.minSeqId = fflag(a, "--min-seq-id", 0.9f);
         o.sam = &a.pos[2];
         ask.map = &o;
     });

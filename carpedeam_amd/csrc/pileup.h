@@ -176,19 +176,21 @@ struct BatchPlan {
 };
 
 // (c) The work items of the m listed queries at dq: k_pileup_chunks, the scan, the number of items.  One stream synchronisation.
+// off: the CSR whose rows are cut into items - the alignment set's, or (cdm_pileup_gapped) the hit set's.
 struct WorkItems {
     DevBuf<uint64_t> items, itemOff; cdmscan::ScanTemp st;
     const uint32_t *queries = nullptr; uint32_t m = 0, chunk = 0; uint64_t n = 0;       // n: work items
     bool alloc(uint32_t nq) { return items.alloc((size_t) nq + 1) && itemOff.alloc((size_t) nq + 1); }
 };
-int workItems(hipStream_t s, const cdm_alns *alns, const uint32_t *dq, uint32_t m, uint32_t chunk, WorkItems &w) {
+int workItems(hipStream_t s, const uint64_t *off, const uint32_t *dq, uint32_t m, uint32_t chunk, WorkItems &w) {
     w.queries = dq; w.m = m; w.chunk = chunk;
-    hipLaunchKernelGGL(k_pileup_chunks, dim3((m + 256) / 256), dim3(256), 0, s, (const uint64_t *) alns->off, dq, m, chunk, w.items.p);
+    hipLaunchKernelGGL(k_pileup_chunks, dim3((m + 256) / 256), dim3(256), 0, s, off, dq, m, chunk, w.items.p);
     if (int rc = cdmscan::exclusiveScan<uint64_t>(s, w.st, w.items.p, w.itemOff.p, (size_t) m + 1)) return rc;
     CDM_HIP(hipMemcpyAsync(&w.n, w.itemOff.p + m, 8, hipMemcpyDeviceToHost, s));
     CDM_HIP(hipStreamSynchronize(s));
     return CDM_OK;
 }
+int workItems(hipStream_t s, const cdm_alns *alns, const uint32_t *dq, uint32_t m, uint32_t chunk, WorkItems &w) { return workItems(s, (const uint64_t *) alns->off, dq, m, chunk, w); }
 
 // the shared part of a call's kernel arguments
 void fillArgs(ItemArgs &a, const SeqMeta *meta, const cdm_seqdb *db, const cdm_alns *alns, float minSeqId, int skipExtended, const WorkItems &w) {

@@ -534,8 +534,8 @@ void cdm_breaks_free(cdm_break *breaks);
  * a set with the coordinates -1 record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more is
  * CDM_ERR_UNSUPPORTED (the record slots are 32 bits wide), and so is a set of 2^40 records or more (the primary is found with one
  * 64-bit maximum per target of columns << 40 | (2^40 - 1 - record index)); neither is reachable at test size, neither is tested.
- * The records are the set's seeded ungapped overlaps at its identity threshold, not a gapped mapping: no insertions or deletions, and
- * no record where no read seeds. */
+ * The records are the set's seeded ungapped overlaps at its identity threshold: no insertions or deletions here (the seeded pairs that
+ * test refused are cdm_pileup_gapped's, below), and no record where no read seeds. */
 #define CDM_MAP_REVERSE   1u
 #define CDM_MAP_SECONDARY 2u
 typedef struct cdm_map_params {
@@ -547,6 +547,67 @@ int  cdm_pileup_map(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
                     const cdm_map_params *par, uint64_t *stats, cdm_map_rec **recs, uint64_t *n_recs, uint32_t **mism, uint64_t *n_mism,
                     float *kernel_ms);
 void cdm_map_free(cdm_map_rec *recs, uint32_t *mism);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The reads across insertions and deletions (not a module of the reference; csrc/pileup_gapped.hip): a banded affine-gap overlap
+ * alignment with traceback on the seeded pairs the ungapped test refused.  `hits` is the prefilter result `alns` was rescored from (or
+ * any hit set of the same DB).  A hit (q, t, score, diagonal) of a listed query q is a CANDIDATE when t != q, t is a sequence of the
+ * DB, t is not left out by skip_extended_targets, the set holds no counted record of (q, t) - the rule of the reductions above with
+ * min_seq_id - and t has at most 4096 letters (a longer t is counted in too_long and not examined).  Every hit is its own candidate.
+ * The alignment of a candidate: the query Q runs forward (n letters), the read R (L letters) is in the query's orientation - reverse-
+ * complemented when hit.score < 0.  Letters are the mapped codes and N bits, never the raw plane.
+ *   diagonals  the hit's diagonal is 16 bits wide; the real diagonals are the ones cdm_rescore probes, u - 65536 d for d = 1 ..
+ *              1 + L / 32768, then u + 65536 d for d = 0 .. n / 65536 (u = (uint16) diagonal), those with a non-empty overlap, in that
+ *              order.  A forward hit's diagonal D is the query-forward diagonal Df = D, a reverse hit's is Df = n - L - D
+ *   band       the cells (i, j), 0 <= i < n, 0 <= j < L, |i - j - Df| <= band
+ *   paths      a path starts with a column (Q[i] over R[j]) at a cell with j = 0 or i = 0 and ends with a column at a cell with
+ *              j = L - 1 or i = n - 1; the read letters in front of the start and behind the end are soft clips
+ *   scores     a column of two equal letters of which neither is N: match; every other column: mismatch; a gap of g letters:
+ *              -(gap_open + gap_extend (g - 1))
+ *   ties       the end cell is the one with the greatest score, then the smallest i, then the smallest j; walking back from it, the
+ *              state a cell was reached from is a column (M) before a query letter without read letter (D) before a read letter without
+ *              query letter (I), and inside a gap its extension before its opening; among the real diagonals the greatest score wins,
+ *              among equals the first in probe order
+ * The candidate is RESCUED when score > 0, columns >= min_columns and matches x 1000 >= min_id_permille x (M columns + inserted +
+ * deleted letters), all integers.  One cdm_gap_rec per rescued candidate:
+ *   query    the index into `queries`                     target   the read's index in db
+ *   pos      the query position of the first column       span     the query letters from pos to the last column (M and D)
+ *   tstart   the read letters in front of the first column, in the query's orientation      tlen   L
+ *   columns  the read letters in M and I                  score    the path's score
+ *   flags    CDM_MAP_REVERSE iff hit.score < 0; CDM_MAP_SECONDARY below
+ *   ops      the index of the record's first word in `ops`; n_ops words there, each length << 2 | op with M = 0, I = 1, D = 2;
+ *            neighbouring operations are merged, the first and the last are M
+ *   words    the index of the record's first word in `words`; n_words words there, ascending in c, the offset on the query from pos:
+ *            c | ref << 24 | read << 28 for a mismatch column (ref, read as in cdm_map_rec) and c | ref << 24 | 15 << 28 for a deleted
+ *            query letter - an MD string with ^ needs nothing but the words
+ *   nm       n_words plus the inserted letters
+ * Order: listed query order, then ascending pos, then the hit's index in the set.  Both word arrays follow that order.
+ * Primary and secondary: a rescued record can be primary only when its target has no counted (ungapped) record on any listed query of
+ * the call; among such a target's rescued records the one with the most columns is primary, among equals the one with the smallest
+ * hit index; every other rescued record carries CDM_MAP_SECONDARY.  So beside cdm_pileup_map's records of the same call every read
+ * still has exactly one primary record, and none of cdm_pileup_map's changes.
+ *   stats   n_queries x 4 uint64, per listed query: 0 candidates, 1 rescued, 2 gap_letters (inserted plus deleted letters of the
+ *           rescued records), 3 too_long
+ *   recs    NULL (statistics only), or receives a malloc'ed array of the records; ops / words (NULL only when recs is) receive the
+ *           two word arrays; all three are released with cdm_gap_free and are the caller's only when the call returns CDM_OK
+ * band outside 1..31, min_id_permille above 1000, match <= 0, mismatch >= 0, gap_extend <= 0 or gap_open < gap_extend (the kernel's
+ * one-pass row is exact only with open >= extend), or one of the four above 64 in magnitude (a path's score is kept in 21 bits beside
+ * its end cell) is CDM_ERR_INVALID, as is a NULL argument, a query index >= the DB's size or listed
+ * twice, and hits or alignments of another DB size.  A listed query with 2^32 hits or more, or a hit set of 2^40 or more, is
+ * CDM_ERR_UNSUPPORTED; the set with the coordinates -1 record is refused as cdm_pileup_map refuses it.
+ * Not covered: reads of more than 4096 letters, a mapping quality, and the four tables above, which still count ungapped records only. */
+typedef struct cdm_gap_params {
+    float    min_seq_id;
+    int32_t  skip_extended_targets;
+    uint32_t band, min_columns, min_id_permille;
+    int32_t  match, mismatch, gap_open, gap_extend;     /* mismatch < 0; the gap costs > 0 */
+} cdm_gap_params;
+typedef struct cdm_gap_rec { uint32_t query, target, pos, span, tstart, tlen, columns, nm, flags, n_ops, n_words; int32_t score;
+                             uint64_t ops, words; } cdm_gap_rec;   /* 64 bytes */
+int  cdm_pileup_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_hits *hits, const cdm_alns *alns, const uint32_t *queries,
+                       uint64_t n_queries, const cdm_gap_params *par, uint64_t *stats, cdm_gap_rec **recs, uint64_t *n_recs,
+                       uint32_t **ops, uint64_t *n_ops, uint32_t **words, uint64_t *n_words, float *kernel_ms);
+void cdm_gap_free(cdm_gap_rec *recs, uint32_t *ops, uint32_t *words);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
