@@ -154,6 +154,26 @@ GAP_DTYPE = np.dtype([(n, "<u4") for n in ("query", "target", "pos", "span", "ts
 GAP_OP_M, GAP_OP_I, GAP_OP_D = 0, 1, 2
 
 
+class IndelParams(C.Structure):
+    """cdm_indel_params: the three thresholds of the site flags, the records' identity threshold, reads only as targets"""
+    _fields_ = [("min_depth", C.c_int32), ("min_count", C.c_int32), ("min_percent", C.c_int32), ("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+    @classmethod
+    def default(cls, min_depth=3, min_count=2, min_percent=20, min_seq_id=0.0, skip_extended_targets=False):
+        """the values `carpedeam contig_indels` passes without flags"""
+        return cls(int(min_depth), int(min_count), int(min_percent), float(min_seq_id), int(bool(skip_extended_targets)))
+
+
+class IndelSite(C.Structure):
+    """cdm_indel_site: one supported place"""
+    _fields_ = [(n, C.c_uint32) for n in ("query", "pos", "info", "count", "cross", "others", "n_letters", "reserved")] + [("letters", C.c_uint64)]
+
+
+INDEL_DTYPE = np.dtype([(n, "<u4") for n in ("query", "pos", "info", "count", "cross", "others", "n_letters", "reserved")] + [("letters", "<u8")])
+INDEL_INS, INDEL_DEL = 1, 2
+INDEL_CALLED, INDEL_SUPPORTED, INDEL_MAJOR = 1, 2, 4
+
+
 EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
@@ -165,7 +185,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -294,6 +314,10 @@ def lib():
                                         C.POINTER(C.c_float)]
         l.cdm_gap_free.argtypes = [C.POINTER(GapRec), u32p, u32p]
         l.cdm_gap_free.restype = None
+        l.cdm_pileup_indels.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(IndelParams), vp, vp, C.POINTER(C.POINTER(IndelSite)), u64p,
+                                        C.POINTER(C.POINTER(C.c_uint8)), u64p, C.POINTER(C.c_float)]
+        l.cdm_indel_free.argtypes = [C.POINTER(IndelSite), C.POINTER(C.c_uint8)]
+        l.cdm_indel_free.restype = None
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -871,6 +895,48 @@ class Ctx:
             C.memmove(w.ctypes.data, words, nw * 4)
         lib().cdm_gap_free(ptr, ops, words)
         return stats, recs, o, w
+
+    def pileup_indels(self, db, alns, queries, recs, ops, par=None, track=False, sites=False):
+        """insertion and deletion sites of the listed queries (cdm_pileup_indels) from the ungapped set and the gapped records and
+        operation words pileup_gapped returned for the same queries -> stats[nq, 10] uint64: reads, columns, rescued, insertions,
+        deletions, inserted_letters, deleted_letters, places, supported, major; with track also cross at every boundary b = 0 .. len - 1,
+        a list of uint32 arrays, one per listed query; with sites also the site records as an array of INDEL_DTYPE and their letters
+        (uint8 codes 0..4).  The order of the extras in the returned tuple is track, sites, letters.  self.indels_kernel_ms holds the
+        device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 10), np.uint64)
+        recs = np.ascontiguousarray(recs, GAP_DTYPE).reshape(-1)
+        ops = np.ascontiguousarray(ops, np.uint32).reshape(-1)
+        lens, cross = None, None
+        if track:
+            if nq and int(q.max()) < db.n:         # (an index beyond the DB is the library's to refuse: nothing is written then)
+                lens = db.meta()[0][q].astype(np.int64)
+            else:
+                lens = np.zeros(nq, np.int64)
+            cross = np.zeros(max(int(lens.sum()), 1), np.uint32)
+        par = par or IndelParams.default()
+        ptr, letters, n_sites, n_letters, ms = C.POINTER(IndelSite)(), C.POINTER(C.c_uint8)(), C.c_uint64(0), C.c_uint64(0), C.c_float(0.0)
+        ref = (lambda x: C.byref(x)) if sites else (lambda x: None)
+        rc = lib().cdm_pileup_indels(self.h, db.h, alns.h, _ptr(q), nq, _ptr(recs) if len(recs) else None, len(recs), _ptr(ops) if len(ops) else None, len(ops), C.byref(par),
+                                     _ptr(stats), _ptr(cross), ref(ptr), ref(n_sites), ref(letters), ref(n_letters), C.byref(ms))
+        self.indels_kernel_ms = float(ms.value)         # (0 behind a refusal: no kernel ran)
+        _check(rc)
+        out = [stats]
+        if track:
+            ends = np.cumsum(lens)
+            out.append([cross[int(e - l):int(e)].copy() for l, e in zip(lens, ends)])
+        if sites:
+            n, nl = int(n_sites.value), int(n_letters.value)
+            assert (n == 0) == (not ptr) and (nl == 0) == (not letters)
+            got, codes = np.empty(n, INDEL_DTYPE), np.empty(nl, np.uint8)
+            if n:
+                C.memmove(got.ctypes.data, ptr, n * C.sizeof(IndelSite))
+            if nl:
+                C.memmove(codes.ctypes.data, letters, nl)
+            lib().cdm_indel_free(ptr, letters)
+            out += [got, codes]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def extend(self, db, alns, par=None, want_scores=False):
         par = par or AncientParams.default()

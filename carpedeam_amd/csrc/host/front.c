@@ -42,6 +42,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_breaks",
                                     /* the reads on the contigs as a SAM file, the records of the same pile-up: not a module of the reference either */
                                     "contig_map",
+                                    /* insertion and deletion sites of the contigs from the gapped records of the same pile-up: not a module of the reference either */
+                                    "contig_indels",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

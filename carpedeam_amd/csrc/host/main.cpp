@@ -1708,13 +1708,101 @@ void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *read
     if (f && fclose(f) != 0) ok = false;
     if (!ok) die("Could not write " + *o.sam);
 }
+// ---- contig_indels: insertion and deletion sites of the contigs and the contigs polished at them (not a module of the reference).
+// The chain of contig_map --gapped 1 - the three calls above, cdm_pileup_gapped with the command's scores and gap costs - then
+// cdm_pileup_indels over the contigs: one summary line per contig, with --sites one line per supported insertion or deletion (S) and
+// whether more than half of the crossing reads carry it (M), with --consensus the contigs with their M sites applied.  Substitutions
+// are not touched: contig_variants --consensus does those.  A read seeded twice on one contig counts twice, as it has two SAM lines.
+// The defaults are those of contig_variants' second allele, reasoned, not measured.  Integers only.
+const FlagSpec INDEL_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-indel-count", 'U', 0, 0}, {"--min-indel-percent", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0},
+                                {"--sites", 'U', 0, 0}, {"--consensus", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// what an indel report writes: the summary always, the other two files when named
+struct IndelOut { long minDepth, minCount, minPercent, gapBand, gapMinColumns; float minSeqId; const std::string *summary, *sites, *consensus; };
+// no contigs: the summary's header line alone, an empty sites file, an empty FASTA
+void indelReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const IndelOut &o, Laps &laps) {
+    std::string text = "name\tkey\tlength\treads\tcolumns\trescued\tinsertions\tdeletions\tinserted_letters\tdeleted_letters\tplaces\tsupported\tmajor\tapplied\tnew_length\n", sitesText, fasta;
+    if (haveContigs(contigs)) {
+        const uint64_t nc = cdm_seqdb_size(contigs->db);
+        std::vector<uint32_t> q(nc), lens(nc);
+        std::iota(q.begin(), q.end(), 0u);
+        cdm_gap_params gp;        // nucleotide.out's scores and the gap costs of `align`, as contig_map --gapped 1
+        gp.min_seq_id = 0.0f; gp.skip_extended_targets = 1; gp.band = (uint32_t) o.gapBand; gp.min_columns = (uint32_t) o.gapMinColumns;
+        gp.min_id_permille = (uint32_t) (o.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
+        std::vector<uint64_t> gstats(nc * 4), stats(nc * 10);
+        cdm_gap_rec *grecs = NULL; uint32_t *gops = NULL, *gwords = NULL; uint64_t nGap = 0, nGops = 0, nGwords = 0; float gms = 0.f, ms = 0.f;
+        check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), nc, &gp, gstats.data(), &grecs, &nGap, &gops, &nGops, &gwords, &nGwords, &gms), "gapped pile-up");
+        cdm_indel_params ip; ip.min_depth = (int32_t) o.minDepth; ip.min_count = (int32_t) o.minCount; ip.min_percent = (int32_t) o.minPercent; ip.min_seq_id = 0.0f; ip.skip_extended_targets = 1;
+        cdm_indel_site *sites = NULL; uint8_t *codes = NULL; uint64_t nSites = 0, nCodes = 0;
+        check(cdm_pileup_indels(ctx, ps.both, ps.alns, q.data(), nc, grecs, nGap, gops, nGops, &ip, stats.data(), NULL, &sites, &nSites, &codes, &nCodes, &ms), "pile-up indel sites");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  indel report: %llu records, %llu rescued, %llu sites, gapped kernels %.3f ms, indel kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nGap, (unsigned long long) nSites, gms, ms);
+        cdm_gap_free(grecs, gops, gwords);
+        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
+        static const char LETTER[] = "ACGTN";
+        std::string tmp;
+        if (o.sites) {      // name, pos (1-based), kind, length, letters, count, cross, others, flags; a deletion shows the contig's letters as the device compared them
+            const uint64_t words = cdm_seqdb_words(contigs->db);
+            std::vector<uint32_t> cw(words + 1), clens(nc); std::vector<uint16_t> nw(words + 1); std::vector<uint64_t> woff(nc + 1, 0);
+            check(cdm_seqdb_export_packed(ctx, contigs->db, cw.data(), nw.data(), clens.data(), NULL, NULL, NULL, NULL), "download of the contigs' codes");
+            for (uint64_t i = 0; i < nc; i++) woff[i + 1] = woff[i] + (lens[i] + 15u) / 16u;
+            for (uint64_t k = 0; k < nSites; k++) {
+                const cdm_indel_site &st = sites[k];
+                const uint32_t kind = st.info & 15u, g = (st.info >> 4) & 0xFFFu, fl = st.info >> 16;
+                sitesText += contigName(*contigs, st.query, tmp);
+                put(sitesText, (unsigned long long) st.pos + 1);
+                sitesText.push_back('\t'); sitesText.push_back(kind == CDM_INDEL_INS ? 'I' : 'D');
+                put(sitesText, g);
+                sitesText.push_back('\t');
+                if (kind == CDM_INDEL_INS) for (uint32_t j = 0; j < st.n_letters; j++) sitesText.push_back(LETTER[std::min<uint32_t>(4u, codes[st.letters + j])]);
+                else for (uint32_t j = 0; j < g; j++) {
+                    const uint64_t p = (uint64_t) st.pos + j, w = woff[st.query] + (p >> 4);
+                    sitesText.push_back((nw[w] >> (p & 15u)) & 1u ? 'N' : LETTER[(cw[w] >> ((p & 15u) * 2u)) & 3u]);
+                }
+                put(sitesText, st.count); put(sitesText, st.cross); put(sitesText, st.others);
+                sitesText.push_back('\t'); sitesText.push_back('S'); if (fl & CDM_INDEL_MAJOR) sitesText.push_back('M');
+                sitesText.push_back('\n');
+            }
+        }
+        // the polished contigs: the M sites in site order behind a cursor; a site inside a stretch an earlier deletion removed is skipped
+        std::vector<uint64_t> at;
+        std::string letters;
+        if (o.consensus) letters = contigLetters(ctx, *contigs, lens, at);
+        uint64_t k = 0;
+        for (uint64_t i = 0; i < nc; i++) {
+            uint64_t next = 0, applied = 0, newLen = 0;
+            if (o.consensus) { fasta.push_back('>'); fasta += contigName(*contigs, i, tmp); fasta.push_back('\n'); }
+            for (; k < nSites && sites[k].query == i; k++) {
+                const cdm_indel_site &st = sites[k];
+                if (!((st.info >> 16) & CDM_INDEL_MAJOR) || st.pos < next) continue;
+                if (o.consensus) fasta.append(letters, at[i] + next, st.pos - next);
+                newLen += st.pos - next; applied++;
+                if ((st.info & 15u) == CDM_INDEL_INS) {
+                    if (o.consensus) for (uint32_t j = 0; j < st.n_letters; j++) fasta.push_back(LETTER[std::min<uint32_t>(4u, codes[st.letters + j])]);
+                    newLen += st.n_letters; next = st.pos;
+                } else next = (uint64_t) st.pos + ((st.info >> 4) & 0xFFFu);
+            }
+            if (o.consensus) fasta.append(letters, at[i] + next, lens[i] + 1ull - next);        // (with the byte that ends the contig)
+            newLen += lens[i] - next;
+            text += contigName(*contigs, i, tmp);
+            put(text, contigs->keys[i]); put(text, lens[i]);
+            for (int c = 0; c < 10; c++) put(text, stats[i * 10 + c]);
+            put(text, applied); put(text, newLen);
+            text.push_back('\n');
+        }
+        cdm_indel_free(sites, codes);
+        laps.lap("indel report: gapped records, sites, tables");
+    }
+    if (!writeText(*o.summary, text)) die("Could not write " + *o.summary);
+    if (o.sites && !writeText(*o.sites, sitesText)) die("Could not write " + *o.sites);
+    if (o.consensus && !writeText(*o.consensus, fasta)) die("Could not write " + *o.consensus);
+}
 // What a pileReports call is asked for (NULL: not asked for): the damage table with its ends, the depth table with its edge and
-// track, the variant and the break reports, the map report with the read set whose names and letters its lines carry.
+// track, the variant, the break and the indel reports, the map report with the read set whose names and letters its lines carry.
 struct PileAsk {
     const std::string *damageOut = NULL; long ends = 0;
     const std::string *depthOut = NULL; long edge = 0; const std::string *trackOut = NULL;
     const VariantOut *variants = NULL; const BreakOut *breaks = NULL;
     const MapOut *map = NULL; const DamageInput *mapReads = NULL;
+    const IndelOut *indels = NULL;
 };
 // The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
 // alignment set.  contigs == NULL: the header lines alone.  Neither DB is freed here.
@@ -1722,9 +1810,9 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
     PileSet ps;
     if (haveContigs(contigs)) {
         if (ask.map) mapCheckNames(*contigs);
-        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, ask.map && ask.map->gapped);
+        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, (ask.map && ask.map->gapped) || ask.indels);
         laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" :
-                 ask.breaks ? "break report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
+                 ask.breaks ? "break report: kmermatcher, rescorediagonal" : ask.indels ? "indel report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
     }
     if (ask.damageOut) damageTable(ctx, contigs, ps, ask.ends, *ask.damageOut, laps);
     if (ask.depthOut) {
@@ -1737,6 +1825,7 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
     if (ask.variants) variantReport(ctx, contigs, ps, *ask.variants, laps);
     if (ask.breaks) breakReport(ctx, contigs, ps, *ask.breaks, laps);
     if (ask.map) mapReport(ctx, contigs, ask.mapReads, ps, *ask.map, laps);
+    if (ask.indels) indelReport(ctx, contigs, ps, *ask.indels, laps);
     freePileSet(ps);
 }
 // The commands with one read set: exactly (or at least) three positional arguments or the usage line, the flag check, what the
@@ -1828,6 +1917,20 @@ int contigMap(Args &a) {
         o.minSeqId = fflag(a, "--min-seq-id", 0.9f);
         o.sam = &a.pos[2];
         ask.map = &o;
+    });
+}
+int contigIndels(Args &a) {
+    IndelOut o;
+    return contigReport(a, "contig_indels", true, "Usage: carpedeam contig_indels <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-indel-count 2] [--min-indel-percent 20] "
+                        "[--gap-band 8] [--gap-min-columns 32] [--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20] [--threads N]", INDEL_FLAGS, [&](PileAsk &ask) {
+        o.minDepth = rangedFlag(a, "contig_indels", "--min-depth", 3, 1, 1000000, "a called place is crossed by 1 to 1000000 reads");
+        o.minCount = rangedFlag(a, "contig_indels", "--min-indel-count", 2, 1, 1000000, "a supported insertion or deletion has 1 to 1000000 reads");
+        o.minPercent = rangedFlag(a, "contig_indels", "--min-indel-percent", 20, 0, 100, "a percentage of the crossing reads is 0 to 100");
+        o.gapBand = rangedFlag(a, "contig_indels", "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
+        o.gapMinColumns = rangedFlag(a, "contig_indels", "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
+        o.minSeqId = fflag(a, "--min-seq-id", 0.9f);
+        o.summary = &a.pos[2]; o.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; o.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
+        ask.indels = &o;
     });
 }
 int readsLoop(Args &a) {
@@ -2331,7 +2434,7 @@ static bool workInChild() {
 int main(int argc, char **argv) {
     // (ancient_assemble_fused is one process from the reads to the FASTA: it has nobody to hand an early answer to)
     if (!(argc >= 2 && !strcmp(argv[1], "ancient_assemble_fused"))) workInChild();
-    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|contig_breaks|contig_map|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
+    if (argc < 2) { fprintf(stderr, "usage: carpedeam <kmermatcher|rescorediagonal|ancient_correction|ancient_read_assemble|ancient_contig_merge|cyclecheck|ancient_reads_loop|ancient_assemble_fused|contig_damage|contig_depth|contig_variants|contig_breaks|contig_map|contig_indels|createdb|mergereads|convert2fasta|createhdb|clust|createsubdb|filterdb|mergeclusters|result2repseq|rmdb|mvdb> <args>\n"); return EXIT_FAILURE; }
     const std::string cmd = argv[1];
     Args a = parse(argc - 2, argv + 2);
     {   // --threads / MMSEQS_NUM_THREADS as in Parameters.cpp:2121-2132: the host side (DB parsing, text codecs) uses them
@@ -2354,6 +2457,7 @@ int main(int argc, char **argv) {
     else if (cmd == "contig_variants") rc = contigVariants(a);
     else if (cmd == "contig_breaks") rc = contigBreaks(a);
     else if (cmd == "contig_map") rc = contigMap(a);
+    else if (cmd == "contig_indels") rc = contigIndels(a);
     else if (cmd == "align" || cmd == "clust" || cmd == "createsubdb" || cmd == "filterdb" || cmd == "mergeclusters" || cmd == "result2repseq" || cmd == "rmdb" || cmd == "mvdb") rc = clusterModules(cmd, a);
     else if (cmd == "createdb") rc = createdb(a);
     else if (cmd == "convert2fasta") rc = convert2fasta(a);

@@ -610,6 +610,69 @@ int  cdm_pileup_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_hits *hits, 
 void cdm_gap_free(cdm_gap_rec *recs, uint32_t *ops, uint32_t *words);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Insertion and deletion sites of the read pile-up (not a module of the reference; csrc/pileup_indels.hip): which insertion and
+ * deletion alleles the rescued reads put on which position of the listed queries, how many reads cross that place at all, which
+ * alleles are supported, and the letters the majority wants inserted.  `alns` is the ungapped set, counted by exactly the rule of the
+ * reductions above; recs / ops are the host arrays cdm_pileup_gapped returned for the same `queries` (the words are not needed).  Every
+ * record given counts, primary or secondary, as every ungapped record counts on every query it lies on.  All figures are integers.
+ * Boundary b of a query of `len` letters, 1 <= b <= len - 1, lies between the positions b - 1 and b, as in cdm_pileup_breaks.
+ *   cross[b]  the counted ungapped records with qs < b <= qe plus the given gapped records with pos < b <= pos + span - 1; cross[0] = 0
+ *   event     one I or D operation of a gapped record, found by walking its operations from pos and tstart: a D of g letters whose
+ *             first deleted query letter is p gives (p, D, g); an I of g letters in front of query position p gives (p, I, g) and
+ *             carries the read offset of its first letter, in the query's orientation.  The operations begin and end with M, so
+ *             pos < p <= pos + span - 1, and an allele's count never exceeds cross[p]
+ *   allele    the events of one (query, p, kind, g); count = their number
+ *   place     one (query, p, kind).  Its best allele has the largest count, among equals the smallest g; others = the place's events
+ *             in its other alleles.  Flags of the best allele:
+ *               CDM_INDEL_CALLED     cross[p] >= min_depth
+ *               CDM_INDEL_SUPPORTED  called, count >= min_count and count * 100 >= min_percent * cross[p] (64 bits)
+ *               CDM_INDEL_MAJOR      supported and 2 * count > cross[p]
+ *   letters   of a best I allele, for every offset k < g: the base counts over the allele's events of the read letter at that offset
+ *             (the mapped code, complemented when the record is reverse; a letter with its N bit set is left out); the largest count
+ *             wins, among equals the lowest code; 4 (N) where every event had an N.  A D allele has no letters: the host has the query
+ *   stats   n_queries x 10 uint64, per listed query:
+ *             0 reads, 1 columns   cdm_pileup_depth's values       2 rescued   the gapped records given
+ *             3 insertions, 4 deletions   events of each kind      5 inserted_letters, 6 deleted_letters
+ *             7 places             8 supported   the query's site records      9 major
+ *   track   NULL, or uint32 [sum of the listed queries' lengths]: per listed query cross[b] for b = 0 .. len - 1, the queries back
+ *           to back in listed order
+ *   sites   NULL, or receives a malloc'ed array of one record per SUPPORTED place in listed query order, then ascending pos, then I
+ *           before D: query = the index into `queries`, pos = p, info = kind | g << 4 | flags << 16 (kind CDM_INDEL_INS or
+ *           CDM_INDEL_DEL), count, cross = cross[p], others, n_letters = g for an I and 0 for a D, letters = the index of the record's
+ *           first letter in `letters`.  *letters receives a malloc'ed array of the codes 0..4, *n_letters their number.  Both arrays
+ *           are released with cdm_indel_free (either may be NULL) and are the caller's only when the call returns CDM_OK.  n_sites,
+ *           letters and n_letters may be NULL only when sites is
+ *   kernel_ms  NULL, or receives the device time of the kernels
+ * The records are caller data and are checked on the host, in one pass, before anything is sent to the device: query < n_queries;
+ * target < the DB's size and tlen == the target's length; records ascending by (query, pos); ops + n_ops within the pool and
+ * n_ops >= 1; every operation M, I or D with a length >= 1; the first and the last M; no two neighbours of one code; M + D = span and
+ * M + I = columns; pos + span <= the query's length and tstart + columns <= tlen; no I or D of more than 62 letters (twice the largest
+ * band, the longest gap a banded path can hold).  The first record that fails is named and the call returns CDM_ERR_INVALID, as for
+ * min_depth or min_count outside 1..1000000, min_percent outside 0..100, a NULL argument, a query index >= the DB's size or listed
+ * twice.  n_queries == 0 is CDM_OK (nothing is launched); n_recs == 0 is valid (cross from the ungapped records, no sites); a set with
+ * the coordinates -1 record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more, or 2^31 operation
+ * words or more, is CDM_ERR_UNSUPPORTED (neither is reachable at test size, neither is tested).
+ * Not covered: substitutions (cdm_pileup_bases), and a read seeded twice on one query counts twice, as it has two records. */
+#define CDM_INDEL_INS 1u
+#define CDM_INDEL_DEL 2u
+#define CDM_INDEL_CALLED 1u
+#define CDM_INDEL_SUPPORTED 2u
+#define CDM_INDEL_MAJOR 4u
+typedef struct cdm_indel_params {
+    int32_t min_depth;        /* 1..1000000 */
+    int32_t min_count;        /* 1..1000000 */
+    int32_t min_percent;      /* 0..100 */
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_indel_params;
+typedef struct cdm_indel_site { uint32_t query, pos, info, count, cross, others, n_letters, reserved; uint64_t letters; } cdm_indel_site;   /* 40 bytes */
+int  cdm_pileup_indels(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                       const cdm_gap_rec *recs, uint64_t n_recs, const uint32_t *ops, uint64_t n_ops, const cdm_indel_params *par,
+                       uint64_t *stats, uint32_t *track, cdm_indel_site **sites, uint64_t *n_sites, uint8_t **letters, uint64_t *n_letters,
+                       float *kernel_ms);
+void cdm_indel_free(cdm_indel_site *sites, uint8_t *letters);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
  * db must be the corrected DB.  Output: new sequence DB (extended sequences get ext=1, others are copied through).
  * scores (optional, may be NULL): for tests, the per-candidate likelihood of the first scoring round
