@@ -185,7 +185,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -318,6 +318,10 @@ def lib():
                                         C.POINTER(C.POINTER(C.c_uint8)), u64p, C.POINTER(C.c_float)]
         l.cdm_indel_free.argtypes = [C.POINTER(IndelSite), C.POINTER(C.c_uint8)]
         l.cdm_indel_free.restype = None
+        gapped = [vp, C.c_uint64, vp, C.c_uint64]       # recs, n_recs, ops, n_ops in front of the parameters
+        l.cdm_pileup_depth_gapped.argtypes = [vp, vp, vp, vp, C.c_uint64] + gapped + [C.POINTER(DepthParams), vp, vp, C.POINTER(C.c_float)]
+        l.cdm_pileup_bases_gapped.argtypes = [vp, vp, vp, vp, C.c_uint64] + gapped + [C.POINTER(BasesParams), vp, vp, C.POINTER(C.POINTER(Site)), u64p, C.POINTER(C.c_float)]
+        l.cdm_pileup_breaks_gapped.argtypes = [vp, vp, vp, vp, C.c_uint64] + gapped + [C.POINTER(BreaksParams), vp, vp, C.POINTER(C.POINTER(Break)), u64p, C.POINTER(C.c_float)]
         l.cdm_seqdb_concat.argtypes = [vp, vp, vp, C.c_uint8, C.c_uint8, C.POINTER(vp)]
         l.cdm_pileup_chunk_records.argtypes = []
         l.cdm_pileup_chunk_records.restype = C.c_uint32
@@ -353,6 +357,13 @@ def lib():
 
 
 _env_seen = None
+
+
+def _gapped_args(gapped):
+    """(recs, ops) -> the four arguments recs, n_recs, ops, n_ops of the *_gapped calls (a pointer of data_as keeps its array alive)"""
+    recs = np.ascontiguousarray(gapped[0], GAP_DTYPE).reshape(-1)
+    ops = np.ascontiguousarray(gapped[1], np.uint32).reshape(-1)
+    return _ptr(recs) if len(recs) else None, len(recs), _ptr(ops) if len(ops) else None, len(ops)
 
 
 def pileup_chunk_records():
@@ -751,9 +762,11 @@ class Ctx:
         _check(lib().cdm_pileup_profile(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(counts), _ptr(reads), _ptr(columns)))
         return counts, reads, columns
 
-    def pileup_depth(self, db, alns, queries, edge=0, min_seq_id=0.0, skip_extended_targets=False, track=False):
+    def pileup_depth(self, db, alns, queries, edge=0, min_seq_id=0.0, skip_extended_targets=False, track=False, gapped=None):
         """depth statistics of the listed queries (cdm_pileup_depth) -> stats[nq, 8] uint64: reads, columns, breadth, window, covered,
-        sum, sumsq, max; with track also the depth at every position, a list of uint32 arrays, one per listed query"""
+        sum, sumsq, max; with track also the depth at every position, a list of uint32 arrays, one per listed query.  gapped: None, or
+        (recs, ops) as pileup_gapped returned them for the same queries - cdm_pileup_depth_gapped, whose device time
+        self.depth_kernel_ms then holds"""
         q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
         nq = len(q)
         stats = np.zeros((nq, 8), np.uint64)
@@ -765,15 +778,22 @@ class Ctx:
                 lens = np.zeros(nq, np.int64)
             depth = np.zeros(max(int(lens.sum()), 1), np.uint32)
         par = DepthParams(int(edge), float(min_seq_id), int(bool(skip_extended_targets)))
-        _check(lib().cdm_pileup_depth(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(depth)))
+        if gapped is None:
+            _check(lib().cdm_pileup_depth(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(depth)))
+        else:
+            ms = C.c_float(0.0)
+            rc = lib().cdm_pileup_depth_gapped(self.h, db.h, alns.h, _ptr(q), nq, *_gapped_args(gapped), C.byref(par), _ptr(stats), _ptr(depth), C.byref(ms))
+            self.depth_kernel_ms = float(ms.value)          # (0 behind a refusal: no kernel ran)
+            _check(rc)
         if not track:
             return stats
         ends = np.cumsum(lens)
         return stats, [depth[int(e - l):int(e)].copy() for l, e in zip(lens, ends)]
 
     def pileup_bases(self, db, alns, queries, mask_ends=0, min_depth=3, min_alt_count=2, min_alt_percent=20, min_seq_id=0.0, skip_extended_targets=False,
-                     counts=False, sites=False):
-        """base counts and variant sites of the listed queries (cdm_pileup_bases) -> stats[nq, 8] uint64: reads, columns, bases,
+                     counts=False, sites=False, gapped=None):
+        """base counts and variant sites of the listed queries (cdm_pileup_bases; with gapped = (recs, ops) as pileup_gapped returned them
+        for the same queries cdm_pileup_bases_gapped) -> stats[nq, 8] uint64: reads, columns, bases,
         mismatches, called, differs, variable, flagged; with counts also a list of uint32 [length, 8] arrays, one per listed query
         (forward A,C,G,T, reverse A,C,G,T); with sites also the site records as an array of SITE_DTYPE.  The order of the extras in the
         returned tuple is counts, sites.  self.bases_kernel_ms holds the device time of the call's kernels"""
@@ -789,9 +809,13 @@ class Ctx:
             table = np.zeros((max(int(lens.sum()), 1), 8), np.uint32)
         par = BasesParams(int(mask_ends), int(min_depth), int(min_alt_count), int(min_alt_percent), float(min_seq_id), int(bool(skip_extended_targets)))
         ptr, n_sites, ms = C.POINTER(Site)(), C.c_uint64(0), C.c_float(0.0)
-        _check(lib().cdm_pileup_bases(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(table), C.byref(ptr) if sites else None,
-                                      C.byref(n_sites) if sites else None, C.byref(ms)))
-        self.bases_kernel_ms = float(ms.value)
+        tail = (C.byref(par), _ptr(stats), _ptr(table), C.byref(ptr) if sites else None, C.byref(n_sites) if sites else None, C.byref(ms))
+        if gapped is None:
+            rc = lib().cdm_pileup_bases(self.h, db.h, alns.h, _ptr(q), nq, *tail)
+        else:
+            rc = lib().cdm_pileup_bases_gapped(self.h, db.h, alns.h, _ptr(q), nq, *_gapped_args(gapped), *tail)
+        self.bases_kernel_ms = float(ms.value)          # (0 behind a refusal of the gapped call: no kernel ran)
+        _check(rc)
         out = [stats]
         if counts:
             ends = np.cumsum(lens)
@@ -807,8 +831,9 @@ class Ctx:
         return out[0] if len(out) == 1 else tuple(out)
 
     def pileup_breaks(self, db, alns, queries, anchor=16, edge=50, min_span=1, min_span_percent=0, min_seq_id=0.0, skip_extended_targets=False,
-                      track=False, breaks=False):
-        """break points of the listed queries (cdm_pileup_breaks) -> stats[nq, 8] uint64: reads, columns, window, weak, breaks, joins,
+                      track=False, breaks=False, gapped=None):
+        """break points of the listed queries (cdm_pileup_breaks; with gapped = (recs, ops) as pileup_gapped returned them for the same
+        queries cdm_pileup_breaks_gapped) -> stats[nq, 8] uint64: reads, columns, window, weak, breaks, joins,
         min_span, sum_span; with track also the span at every boundary b = 0 .. len - 1, a list of uint32 arrays, one per listed query;
         with breaks also the break records as an array of BREAK_DTYPE.  The order of the extras in the returned tuple is track, breaks.
         self.breaks_kernel_ms holds the device time of the call's kernels"""
@@ -824,9 +849,13 @@ class Ctx:
             span = np.zeros(max(int(lens.sum()), 1), np.uint32)
         par = BreaksParams(int(anchor), int(edge), int(min_span), int(min_span_percent), float(min_seq_id), int(bool(skip_extended_targets)))
         ptr, n_breaks, ms = C.POINTER(Break)(), C.c_uint64(0), C.c_float(0.0)
-        _check(lib().cdm_pileup_breaks(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(span), C.byref(ptr) if breaks else None,
-                                       C.byref(n_breaks) if breaks else None, C.byref(ms)))
-        self.breaks_kernel_ms = float(ms.value)
+        tail = (C.byref(par), _ptr(stats), _ptr(span), C.byref(ptr) if breaks else None, C.byref(n_breaks) if breaks else None, C.byref(ms))
+        if gapped is None:
+            rc = lib().cdm_pileup_breaks(self.h, db.h, alns.h, _ptr(q), nq, *tail)
+        else:
+            rc = lib().cdm_pileup_breaks_gapped(self.h, db.h, alns.h, _ptr(q), nq, *_gapped_args(gapped), *tail)
+        self.breaks_kernel_ms = float(ms.value)         # (0 behind a refusal of the gapped call: no kernel ran)
+        _check(rc)
         out = [stats]
         if track:
             ends = np.cumsum(lens)

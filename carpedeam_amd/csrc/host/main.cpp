@@ -1311,6 +1311,32 @@ PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int
     return p;
 }
 void freePileSet(PileSet &p) { if (p.hits) cdm_hits_free(p.hits); if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
+// --gapped 0|1 with --gap-band and --gap-min-columns, as contig_map, contig_depth, contig_variants and contig_breaks take them: the
+// reads rescued across insertions and deletions (cdm_pileup_gapped) beside the ungapped overlaps.  whatGapped: what 0 and 1 mean to
+// the module.  Either --gap-* flag without --gapped 1 is refused: it sets an alignment that is off.
+struct GapOpts { bool on = false; long band = 8, minColumns = 32; float minSeqId = 0.9f; };
+GapOpts gapOpts(Args &a, const char *module, const char *whatGapped) {
+    GapOpts g;
+    g.on = rangedFlag(a, module, "--gapped", 0, 0, 1, whatGapped) != 0;
+    for (const char *flag : {"--gap-band", "--gap-min-columns"})
+        if (!g.on && a.flag.count(flag)) unsupported(std::string(module) + ": " + flag + " without --gapped 1 is not supported by the MI355X path (the flag sets the gapped alignment, which is off)");
+    g.band = rangedFlag(a, module, "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
+    g.minColumns = rangedFlag(a, module, "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
+    g.minSeqId = fflag(a, "--min-seq-id", 0.9f);
+    return g;
+}
+const char *const TABLE_GAPPED = "0 counts the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions";
+// The rescued reads of a PileSet that kept its hits, for the *_gapped reductions: cdm_pileup_gapped over the listed contigs with
+// contig_map's scores and gap costs (nucleotide.out's scores, the gap costs of `align`).  The arrays are released with cdm_gap_free.
+struct Rescued { cdm_gap_rec *recs = NULL; uint32_t *ops = NULL, *words = NULL; uint64_t n = 0, nOps = 0, nWords = 0, candidates = 0; float ms = 0.f; };
+void rescueReads(cdm_ctx *ctx, const PileSet &ps, const std::vector<uint32_t> &q, const GapOpts &g, Rescued &r) {
+    cdm_gap_params gp;
+    gp.min_seq_id = 0.0f; gp.skip_extended_targets = 1; gp.band = (uint32_t) g.band; gp.min_columns = (uint32_t) g.minColumns;
+    gp.min_id_permille = (uint32_t) (g.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
+    std::vector<uint64_t> gstats(q.size() * 4);
+    check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), q.size(), &gp, gstats.data(), &r.recs, &r.n, &r.ops, &r.nOps, &r.words, &r.nWords, &r.ms), "gapped pile-up");
+    for (size_t i = 0; i < q.size(); i++) r.candidates += gstats[i * 4];
+}
 bool haveContigs(const DamageInput *contigs) { return contigs && contigs->db && cdm_seqdb_size(contigs->db); }
 const std::string &contigName(const DamageInput &c, uint64_t i, std::string &tmp) { if (i < c.names.size()) return c.names[i]; tmp = std::to_string(c.keys[i]); return tmp; }
 // bedGraph lines of one contig's runs of equal value, zero runs included: name, start, end (0-based, half-open), value
@@ -1359,17 +1385,28 @@ void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, lo
 // ---- contig_depth: per-contig depth, breadth and depth variance from the same pile-up (not a module of the reference).  Per read set
 // the three calls above, then cdm_pileup_depth over the contigs: as with the damage tables, coverage by seeded UNGAPPED overlaps at the
 // identity threshold, not a gapped mapping.  One TSV line per contig, integers only: the caller divides (mean = sum / window,
-// variance = (sumsq - sum^2 / window) / (window - 1)).
-const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// variance = (sumsq - sum^2 / window) / (window - 1)).  --gapped 1 (here, in contig_variants and in contig_breaks): the set keeps its
+// hits, cdm_pileup_gapped rescues the reads across insertions and deletions, and the *_gapped reduction counts them as well.
+const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 long depthEdge(Args &a, const char *module) { return rangedFlag(a, module, "--depth-edge", 0, 0, 1048576, "0 to 1048576 positions are left out at either end of a contig"); }
 // one read set's statistics (nc x 8) and, when asked for, the depth of every contig position back to back
-void depthSample(cdm_ctx *ctx, const DamageInput &contigs, const PileSet &ps, long edge, std::vector<uint64_t> &stats, std::vector<uint32_t> *track) {
+// gap (--gapped 1; the set kept its hits): the rescued reads count as well
+void depthSample(cdm_ctx *ctx, const DamageInput &contigs, const PileSet &ps, long edge, std::vector<uint64_t> &stats, std::vector<uint32_t> *track, const GapOpts *gap = NULL) {
     const uint64_t nc = cdm_seqdb_size(contigs.db);
     std::vector<uint32_t> q(nc);
     std::iota(q.begin(), q.end(), 0u);
     stats.assign(nc * 8, 0);
     if (track) track->assign(cdm_seqdb_residues(contigs.db) + 1, 0);
     cdm_depth_params dp; dp.edge = (int32_t) edge; dp.min_seq_id = 0.0f; dp.skip_extended_targets = 1;
+    if (gap && gap->on) {
+        Rescued r; float ms = 0.f;
+        rescueReads(ctx, ps, q, *gap, r);
+        check(cdm_pileup_depth_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &dp, stats.data(), track ? track->data() : NULL, &ms), "pile-up depth");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  depth report: %llu records, %llu candidates, %llu rescued, gapped kernels %.3f ms, depth kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
+                                          (unsigned long long) r.candidates, (unsigned long long) r.n, r.ms, ms);
+        cdm_gap_free(r.recs, r.ops, r.words);
+        return;
+    }
     check(cdm_pileup_depth(ctx, ps.both, ps.alns, q.data(), nc, &dp, stats.data(), track ? track->data() : NULL), "pile-up depth");
     if (getenv("CDM_TIMING")) fprintf(stderr, "  depth report: %llu records, depth kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 17));
 }
@@ -1413,7 +1450,8 @@ void depthTrackFile(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<
 // positions.  As with the other two reports the pile-up is seeded UNGAPPED overlaps at the identity threshold: no indels, and no call
 // where no read seeds.  Integers only.
 const FlagSpec VARIANT_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0}, {"--sites", 'U', 0, 0},
-                                  {"--consensus", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+                                  {"--consensus", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0},
+                                  {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 struct VariantOpts { long maskEnds, minDepth, minAltCount, minAltPercent; };
 VariantOpts variantOpts(Args &a, const char *module) {
     VariantOpts o;
@@ -1424,7 +1462,7 @@ VariantOpts variantOpts(Args &a, const char *module) {
     return o;
 }
 // what a variant report writes: the summary always, the other two files when named
-struct VariantOut { VariantOpts opt; const std::string *summary, *sites, *consensus; };
+struct VariantOut { VariantOpts opt; const std::string *summary, *sites, *consensus; GapOpts gap; };       // gap.on: the rescued reads count as well (the set kept its hits)
 // no contigs: the summary's header line alone, an empty sites file, an empty FASTA
 void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const VariantOut &v, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns\tbases\tmismatches\tcalled\tdiffers\tvariable\n", sitesText, fasta;
@@ -1437,8 +1475,17 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
         bp.min_alt_percent = (int32_t) v.opt.minAltPercent; bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
         const bool wantSites = v.sites || v.consensus;
         cdm_site *sites = NULL; uint64_t nSites = 0; float ms = 0.f;
-        check(cdm_pileup_bases(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu sites, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nSites, ms);
+        if (v.gap.on) {
+            Rescued r;
+            rescueReads(ctx, ps, q, v.gap, r);
+            check(cdm_pileup_bases_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
+            if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu candidates, %llu rescued, %llu sites, gapped kernels %.3f ms, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
+                                              (unsigned long long) r.candidates, (unsigned long long) r.n, (unsigned long long) nSites, r.ms, ms);
+            cdm_gap_free(r.recs, r.ops, r.words);
+        } else {
+            check(cdm_pileup_bases(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
+            if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu sites, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nSites, ms);
+        }
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
         std::string tmp;
         for (uint64_t i = 0; i < nc; i++) {
@@ -1483,7 +1530,7 @@ void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, 
 // spanning coverage of every boundary.  As with the other three reports the pile-up is seeded UNGAPPED overlaps at the identity
 // threshold: reads shorter than twice the anchor span nothing, and there is no break call where no read seeds.  Integers only.
 const FlagSpec BREAK_FLAGS[] = {{"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0}, {"--split", 'U', 0, 0},
-                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 struct BreakOpts { long anchor, edge, minSpan, minSpanPercent; };
 // The default anchor is reasoned, not measured: a read with w columns beyond a false join expects 0.75 w mismatches there, and at the
 // identity threshold t a read of L columns is dropped when 0.75 w > (1 - t) L; w = 16 covers L <= 120 at t = 0.9.
@@ -1498,7 +1545,7 @@ BreakOpts breakOpts(Args &a, const char *module) {
     return o;
 }
 // what a break report writes: the summary always, the other two files when named
-struct BreakOut { BreakOpts opt; long minPiece; const std::string *summary, *split, *track; };
+struct BreakOut { BreakOpts opt; long minPiece; const std::string *summary, *split, *track; GapOpts gap; };      // gap.on: the rescued reads count as well (the set kept its hits)
 // no contigs: the summary's header line alone, an empty FASTA, an empty track
 void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const BreakOut &o, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns\twindow\tweak\tbreaks\tjoins\tmin_span\tsum_span\n", fasta, bed;
@@ -1511,8 +1558,17 @@ void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, co
         cdm_breaks_params bp; bp.anchor = (int32_t) o.opt.anchor; bp.edge = (int32_t) o.opt.edge; bp.min_span = (int32_t) o.opt.minSpan; bp.min_span_percent = (int32_t) o.opt.minSpanPercent;
         bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
         cdm_break *br = NULL; uint64_t nBr = 0; float ms = 0.f;
-        check(cdm_pileup_breaks(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu breaks, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nBr, ms);
+        if (o.gap.on) {
+            Rescued r;
+            rescueReads(ctx, ps, q, o.gap, r);
+            check(cdm_pileup_breaks_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
+            if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu candidates, %llu rescued, %llu breaks, gapped kernels %.3f ms, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
+                                              (unsigned long long) r.candidates, (unsigned long long) r.n, (unsigned long long) nBr, r.ms, ms);
+            cdm_gap_free(r.recs, r.ops, r.words);
+        } else {
+            check(cdm_pileup_breaks(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
+            if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu breaks, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nBr, ms);
+        }
         check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
         std::string tmp, letters;
         std::vector<uint64_t> at;
@@ -1810,7 +1866,8 @@ void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int
     PileSet ps;
     if (haveContigs(contigs)) {
         if (ask.map) mapCheckNames(*contigs);
-        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, (ask.map && ask.map->gapped) || ask.indels);
+        const bool keepHits = (ask.map && ask.map->gapped) || ask.indels || (ask.variants && ask.variants->gap.on) || (ask.breaks && ask.breaks->gap.on);
+        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, keepHits);
         laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" :
                  ask.breaks ? "break report: kmermatcher, rescorediagonal" : ask.indels ? "indel report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
     }
@@ -1853,9 +1910,10 @@ int contigDamage(Args &a) {
                         [&](PileAsk &ask) { ask.ends = damageEnds(a, "contig_damage"); ask.damageOut = &a.pos[2]; });
 }
 int contigDepth(Args &a) {
-    if (a.pos.size() < 3) die("Usage: carpedeam contig_depth <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> [<i:reads> ...] <o:tsvFile> [--depth-edge 0] [--min-seq-id 0.9] [-k 20] [--depth-track <bedGraph>]");
+    if (a.pos.size() < 3) die("Usage: carpedeam contig_depth <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> [<i:reads> ...] <o:tsvFile> [--depth-edge 0] [--min-seq-id 0.9] [-k 20] [--depth-track <bedGraph>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32]");
     checkFlags("contig_depth", a, DEPTH_FLAGS);
     const long edge = depthEdge(a, "contig_depth");
+    const GapOpts gap = gapOpts(a, "contig_depth", TABLE_GAPPED);
     const size_t samples = a.pos.size() - 2;
     const bool wantTrack = a.flag.count("--depth-track") != 0;
     if (wantTrack && samples > 1) unsupported("contig_depth: --depth-track with " + std::to_string(samples) + " read sets is not supported by the MI355X path (the track is written for one read set)");
@@ -1869,9 +1927,9 @@ int contigDepth(Args &a) {
     for (size_t s = 0; have && s < samples; s++) {      // each read set is freed before the next
         DamageInput reads;
         if (!loadDamageInput(ctx, a.pos[1 + s], true, false, reads)) die("contig_depth: " + a.pos[1 + s] + " holds no reads");
-        PileSet ps = pileupAlignments(ctx, contigs.db, reads.db, k, minSeqId);
+        PileSet ps = pileupAlignments(ctx, contigs.db, reads.db, k, minSeqId, gap.on);
         laps.lap("depth report: reads up, kmermatcher, rescorediagonal");
-        depthSample(ctx, contigs, ps, edge, stats[s], wantTrack ? &track : NULL);
+        depthSample(ctx, contigs, ps, edge, stats[s], wantTrack ? &track : NULL, &gap);
         freePileSet(ps); cdm_seqdb_free(reads.db);
         laps.lap("depth report: depth");
     }
@@ -1885,8 +1943,9 @@ int contigDepth(Args &a) {
 int contigVariants(Args &a) {
     VariantOut v;
     return contigReport(a, "contig_variants", true, "Usage: carpedeam contig_variants <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-alt-count 2] [--min-alt-percent 20] [--mask-ends 0] "
-                        "[--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20]", VARIANT_FLAGS, [&](PileAsk &ask) {
+                        "[--sites <tsvFile>] [--consensus <fastaFile>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", VARIANT_FLAGS, [&](PileAsk &ask) {
         v.opt = variantOpts(a, "contig_variants");
+        v.gap = gapOpts(a, "contig_variants", TABLE_GAPPED);
         v.summary = &a.pos[2]; v.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; v.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
         ask.variants = &v;
     });
@@ -1894,8 +1953,9 @@ int contigVariants(Args &a) {
 int contigBreaks(Args &a) {
     BreakOut o;
     return contigReport(a, "contig_breaks", true, "Usage: carpedeam contig_breaks <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--break-anchor 16] [--break-edge 50] [--min-span 1] [--min-span-percent 0] "
-                        "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--min-seq-id 0.9] [-k 20]", BREAK_FLAGS, [&](PileAsk &ask) {
+                        "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", BREAK_FLAGS, [&](PileAsk &ask) {
         o.opt = breakOpts(a, "contig_breaks");
+        o.gap = gapOpts(a, "contig_breaks", TABLE_GAPPED);
         o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
         o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
         ask.breaks = &o;
@@ -1909,12 +1969,8 @@ int contigMap(Args &a) {
         o.readGroup = a.flag.count("--read-group") ? &a.flag["--read-group"] : NULL;
         if (o.readGroup && (o.readGroup->empty() || o.readGroup->find('\t') != std::string::npos))
             unsupported("contig_map: --read-group \"" + *o.readGroup + "\" is not supported by the MI355X path (a read group's ID is at least one character and holds no tab)");
-        o.gapped = rangedFlag(a, "contig_map", "--gapped", 0, 0, 1, "0 writes the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions") != 0;
-        for (const char *flag : {"--gap-band", "--gap-min-columns"})
-            if (!o.gapped && a.flag.count(flag)) unsupported(std::string("contig_map: ") + flag + " without --gapped 1 is not supported by the MI355X path (the flag sets the gapped alignment, which is off)");
-        o.gapBand = rangedFlag(a, "contig_map", "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
-        o.gapMinColumns = rangedFlag(a, "contig_map", "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
-        o.minSeqId = fflag(a, "--min-seq-id", 0.9f);
+        const GapOpts g = gapOpts(a, "contig_map", "0 writes the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions");
+        o.gapped = g.on; o.gapBand = g.band; o.gapMinColumns = g.minColumns; o.minSeqId = g.minSeqId;
         o.sam = &a.pos[2];
         ask.map = &o;
     });

@@ -1,8 +1,9 @@
 // What the reductions over the read pile-up share (pileup.hip: cdm_pileup_profile; pileup_depth.hip: cdm_pileup_depth and
 // cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map): the rule by which a record counts, the
 // work items (listed query, chunk of its records) and the tiles (listed query, DP_TILE positions) with their lookups, and the host
-// steps of a call - query sizes, batch cut, work items, sliced launches, the timed synchronisation, the caller's record array.  Every
-// step is defined here once.
+// steps of a call - query sizes, batch cut, work items, sliced launches, the timed synchronisation, the caller's record array - and
+// what the users of cdm_pileup_gapped's records share: the walk over a record's operations and the host's check of them.  Every step
+// is defined here once.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -118,7 +119,90 @@ __device__ __forceinline__ void addReadsColumns(unsigned long long *reads, unsig
     if (lane == 0 && rd) { atomicAdd(reads, (unsigned long long) rd); atomicAdd(columns, cl); }
 }
 
+// ---------------------------------------------------------------------------------------------- gapped records
+// What the users of cdm_pileup_gapped's records share (pileup_indels.hip: cdm_pileup_indels; pileup_depth.hip and pileup_bases.hip:
+// the three *_gapped reductions): the operation codes, the walk over a record's operations, and further down the host's check.
+constexpr uint32_t ID_MAX_GAP = 62;         // letters of an I or D: 2 x the largest band
+constexpr uint32_t ID_OP_M = 0, ID_OP_I = 1, ID_OP_D = 2;
+
+// The walk over a gapped record's operations from p = pos and off = tstart: match(p, off, g) for every M of g letters - column j < g
+// sits on query position p + j with the read's oriented offset off + j -, event(p, kind, g, off) for every I and D.
+// indelCheckRecords: n_ops words inside the pool, M + D = span, M + I = columns
+template <class Match, class Event> __device__ __forceinline__ void gappedWalk(const cdm_gap_rec &r, const uint32_t *__restrict__ ops, Match match, Event event) {
+    uint32_t p = r.pos, off = r.tstart;
+    for (uint32_t j = 0; j < r.n_ops; j++) {
+        const uint32_t w = ops[r.ops + j], g = w >> 2, op = w & 3u;
+        if (op == ID_OP_M) { match(p, off, g); p += g; off += g; }
+        else if (op == ID_OP_I) { event(p, ID_OP_I, g, off); off += g; }
+        else { event(p, ID_OP_D, g, off); p += g; }
+    }
+}
+// the I and D operations alone
+template <class Event> __device__ __forceinline__ void indelWalk(const cdm_gap_rec &r, const uint32_t *__restrict__ ops, Event event) {
+    gappedWalk(r, ops, [](uint32_t, uint32_t, uint32_t) {}, event);
+}
+
 // ---------------------------------------------------------------------------------------------- host
+// One pass over the caller's gapped records and their operation words (include/carpedeam_hip.h): CDM_OK, or CDM_ERR_INVALID with the
+// first record that fails.  qLen: the listed queries' lengths; tLen: the length of every sequence of the DB.
+int indelCheckRecords(const char *who, const cdm_gap_rec *recs, uint64_t nRecs, const uint32_t *ops, uint64_t nOps, const std::vector<uint32_t> &qLen, const std::vector<uint32_t> &tLen) {
+    for (uint64_t i = 0; i < nRecs; i++) {
+        const cdm_gap_rec &r = recs[i];
+        auto bad = [&](const char *what) { cdm_set_error("%s: gapped record %llu: %s", who, (unsigned long long) i, what); return CDM_ERR_INVALID; };
+        if (r.query >= qLen.size()) return bad("its query is not an index into the listed queries");
+        if (r.target >= tLen.size()) return bad("its target is not a sequence of the DB");
+        if (r.tlen != tLen[r.target]) return bad("tlen is not the length of its target");
+        if (i && (r.query < recs[i - 1].query || (r.query == recs[i - 1].query && r.pos < recs[i - 1].pos))) return bad("the records do not ascend by (query, pos)");
+        if (r.n_ops < 1 || r.ops > nOps || r.n_ops > nOps - r.ops) return bad("its operations are not words of the pool");
+        uint64_t span = 0, columns = 0;
+        for (uint32_t j = 0; j < r.n_ops; j++) {
+            const uint32_t w = ops[r.ops + j], g = w >> 2, op = w & 3u;
+            if (op > ID_OP_D || g < 1) return bad("an operation that is not M, I or D of at least one letter");
+            if ((j == 0 || j + 1 == r.n_ops) && op != ID_OP_M) return bad("its first or last operation is not M");
+            if (j && (ops[r.ops + j - 1] & 3u) == op) return bad("two neighbouring operations of one code");
+            if (op != ID_OP_M && g > ID_MAX_GAP) return bad("an insertion or deletion of more than 62 letters");
+            if (op != ID_OP_I) span += g;
+            if (op != ID_OP_D) columns += g;
+        }
+        if (span != r.span || columns != r.columns) return bad("its operations do not sum to span and columns");
+        if ((uint64_t) r.pos + r.span > qLen[r.query]) return bad("pos + span lies beyond its query");
+        if ((uint64_t) r.tstart + r.columns > r.tlen) return bad("tstart + columns lies beyond its target");
+    }
+    return CDM_OK;
+}
+
+// The caller's gapped records of a call, as the host sequences take them.  check(): the records against the DB's lengths, before
+// anything else goes to the device or is launched - the lengths come down in one plain copy.  upload(): both arrays in the stream.
+// end(): the records are sorted by listed query, so those of the batch of listed queries in front of q1 are the range [g0, end(g0, q1)).
+struct GappedRecords {
+    const cdm_gap_rec *recs = nullptr; uint64_t nRecs = 0; const uint32_t *ops = nullptr; uint64_t nOps = 0;
+    DevBuf<cdm_gap_rec> dRecs; DevBuf<uint32_t> dOps;
+    int check(const char *who, const cdm_seqdb *db, const uint32_t *queries, uint64_t nq) const {
+        if (!nRecs) return CDM_OK;
+        std::vector<uint32_t> tLen(db->n), qLen(nq);
+        CDM_HIP(hipMemcpy(tLen.data(), db->len, (size_t) db->n * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < nq; i++) qLen[i] = tLen[queries[i]];
+        return indelCheckRecords(who, recs, nRecs, ops, nOps, qLen, tLen);
+    }
+    int upload(hipStream_t s, const char *who) {
+        if (!nRecs) return CDM_OK;
+        if (!dRecs.alloc(nRecs) || !dOps.alloc(nOps)) { cdm_set_error("%s: out of device memory for %llu gapped records and %llu operations", who, (unsigned long long) nRecs, (unsigned long long) nOps); return CDM_ERR_HIP; }
+        CDM_HIP(hipMemcpyAsync(dRecs.p, recs, (size_t) nRecs * sizeof(cdm_gap_rec), hipMemcpyHostToDevice, s));
+        CDM_HIP(hipMemcpyAsync(dOps.p, ops, (size_t) nOps * 4, hipMemcpyHostToDevice, s));
+        return CDM_OK;
+    }
+    uint64_t end(uint64_t g0, uint64_t q1) const { while (g0 < nRecs && recs[g0].query < q1) g0++; return g0; }
+    // a listed query whose ungapped plus gapped records reach 2^32 is refused (the 32-bit `what` hold fewer)
+    int checkCounts(const char *who, const char *what, const uint32_t *queries, const std::vector<uint64_t> &ungapped) const {
+        for (uint64_t g = 0; g < nRecs;) {
+            const uint64_t q = recs[g].query, g1 = end(g, q + 1);
+            if ((ungapped[q] + (g1 - g)) >> 32) { cdm_set_error("%s: query %u has %llu records; the 32-bit %s hold fewer than 2^32", who, queries[q], (unsigned long long) (ungapped[q] + (g1 - g)), what); return CDM_ERR_UNSUPPORTED; }
+            g = g1;
+        }
+        return CDM_OK;
+    }
+};
+
 // the argument checks the entry points share
 int pileupCheckArgs(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries) {
     if (alns->n != db->n) { cdm_set_error("%s: alignment CSR has %llu queries, DB has %llu", who, (unsigned long long) alns->n, (unsigned long long) db->n); return CDM_ERR_INVALID; }

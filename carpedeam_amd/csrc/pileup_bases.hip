@@ -7,6 +7,8 @@
 // instruction that carry the same base add to a contiguous run of one plane (an interleaved [position][8] table would touch one word
 // in each of 64 separate 32-byte cells).  A second kernel reads the planes by tiles of positions, classifies, reduces the query's
 // figures and marks the flagged positions; one prefix sum over the marks places the site records, which a third kernel writes.
+// cdm_pileup_bases_gapped is the same host sequence with the caller's gapped records (cdm_pileup_gapped's) counted into the same planes
+// by k_base_counts_gapped.
 #include "pileup.h"
 
 namespace {
@@ -26,6 +28,9 @@ struct BasesArgs : TiledArgs {      // (items: counting; tiles: classification a
     uint32_t *place;                // [nPos + 1]: 0/1 per flagged position, after the scan the position's first site record
     uint32_t *counts;               // NULL, or [nPos][8]
     cdm_site *sites;                // k_base_emit: [place[nPos]]
+    const cdm_gap_rec *grec;        // cdm_pileup_bases_gapped: the batch's gapped records [nG] (query: the index into the call's list)
+    const uint32_t *gops;           // the caller's whole operation pool
+    uint32_t nG;
 };
 // counting: one wave per item (listed query, chunk of its records) of this launch's slice.  Each lane loads one record and evaluates
 // the filter; the wave then walks the counted records one at a time, its lanes on the columns lane, lane + 64, ...
@@ -59,6 +64,56 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_base_counts(BasesArgs a, uint
         }
     }
     addReadsColumns(&a.stats[(uint64_t) qi * 8], &a.stats[(uint64_t) qi * 8 + 1], nReads, nCols, lane);
+}
+
+// The gapped records (cdm_pileup_bases_gapped; include/carpedeam_hip.h) into the same planes: one wave per item of 64 records of this
+// launch's slice.  Each lane loads one record; the wave then walks the records one at a time, their fields broadcast, the operation
+// words loaded wave-uniformly, and for every M operation the lanes take its columns lane, lane + 64, ... - what k_base_counts does
+// with the columns of an ungapped record.  An inserted letter has no query position and a deleted one no read letter: neither counts.
+// reads and columns (the M columns) go to the query's stats row once per wave where its records share a query - they are sorted by
+// query -, else once per record.  indelCheckRecords (pileup.h): pos + span <= the query's length, tstart + columns <= tlen = the
+// target's length and the operation words lie in the pool, below 2^31 of them, so every index below stays inside the query's planes,
+// the read's words and the pool.
+__global__ __launch_bounds__(64 * PU_WAVES) void k_base_counts_gapped(BasesArgs a, uint64_t first, uint64_t nThis) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
+    if (local >= nThis) return;
+    const uint64_t rb = (first + local) * 64;
+    const bool have = rb + lane < a.nG;
+    const uint32_t m = a.maskEnds;
+    uint32_t myQi = 0, myPos = 0, myOff = 0, myLen = 0, myW = 0, myRev = 0, myOps = 0, myN = 0, myCols = 0;
+    if (have) {
+        const cdm_gap_rec r = a.grec[rb + lane];
+        myQi = r.query - a.firstQuery; myPos = r.pos; myOff = r.tstart; myLen = r.tlen; myW = a.meta[r.target].woff; myRev = r.flags & CDM_MAP_REVERSE ? 1u : 0u;
+        myOps = (uint32_t) r.ops; myN = r.n_ops;
+    }
+    const unsigned long long all = __ballot(have);
+    for (unsigned long long live = all; live; live &= live - 1) {       // (wave-uniform: the shuffles below see all 64 lanes)
+        const int src = __ffsll((long long) live) - 1;
+        const uint32_t qi = __shfl(myQi, src, 64), len = __shfl(myLen, src, 64), w = __shfl(myW, src, 64), rev = __shfl(myRev, src, 64);
+        const uint32_t o0 = __shfl(myOps, src, 64), n = __shfl(myN, src, 64);
+        uint32_t p = __shfl(myPos, src, 64), off = __shfl(myOff, src, 64), cols = 0;
+        uint32_t *__restrict__ plane0 = a.planes + a.base[qi];
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t word = a.gops[__builtin_amdgcn_readfirstlane(o0 + j)], g = word >> 2, op = word & 3u;
+            if (op == ID_OP_M) {
+                for (uint32_t c = lane; c < g; c += 64) {
+                    const uint32_t oc = off + c, rp = rev ? len - 1u - oc : oc;       // the position in the read's own orientation
+                    if (cdm_isN(a.nmask, w, rp)) continue;
+                    if (m && (rp < m || len - 1u - rp < m)) continue;
+                    uint32_t b = cdm_base(a.codes, w, rp);
+                    if (rev) b = 3u - b;                  // the read base as the query's strand sees it
+                    atomicAdd(&plane0[(uint64_t) (rev * 4u + b) * a.nPos + p + c], 1u);     // (result unused: an atomic without return)
+                }
+                p += g; off += g; cols += g;
+            } else if (op == ID_OP_I) off += g;
+            else p += g;
+        }
+        if (lane == src) myCols = cols;
+    }
+    const uint32_t qi0 = __shfl(myQi, __ffsll((long long) all) - 1, 64);        // (local < nThis: the item holds a record)
+    if (!__ballot(have && myQi != qi0)) addReadsColumns(&a.stats[(uint64_t) qi0 * 8], &a.stats[(uint64_t) qi0 * 8 + 1], have ? 1u : 0u, (unsigned long long) myCols, lane);
+    else if (have) { atomicAdd(&a.stats[(uint64_t) myQi * 8], 1ull); atomicAdd(&a.stats[(uint64_t) myQi * 8 + 1], (unsigned long long) myCols); }
 }
 
 // one position's verdict from its eight counters and the query's letter (ref: its code, 4 for N)
@@ -145,14 +200,19 @@ __global__ __launch_bounds__(DP_NT) void k_base_emit(BasesArgs a, uint64_t first
 }
 }  // namespace
 
-static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_bases_params *par, uint64_t *stats, uint32_t *counts,
-                          cdm_site **sites, uint64_t *nSitesOut, float *kernelMs) {
+// The host sequence of cdm_pileup_bases (who; gr without records) and of cdm_pileup_bases_gapped (gr: the caller's gapped records,
+// checked before anything goes to the device).
+static int cdm_bases_impl(cdm_ctx *ctx, const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, GappedRecords &gr, const cdm_bases_params *par,
+                          uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *nSitesOut, float *kernelMs) {
     hipStream_t s = ctx->stream;
     const uint32_t chunk = pileupChunk();
     const uint64_t bound = basesPositions();
+    if (int rc = gr.check(who, db, queries, nq)) return rc;
     QuerySizes qs;
-    if (int rc = querySizes(ctx, db, alns, queries, nq, "cdm_pileup_bases", "counters", qs)) return rc;
-    float msTotal = 0.f; uint64_t countsAt = 0;
+    if (int rc = querySizes(ctx, db, alns, queries, nq, who, "counters", qs)) return rc;
+    if (int rc = gr.checkCounts(who, "counters", queries, qs.recs)) return rc;
+    if (int rc = gr.upload(s, who)) return rc;
+    float msTotal = 0.f; uint64_t countsAt = 0, g0 = 0;
     for (uint64_t b0 = 0; b0 < nq;) {
         // the batch: listed queries while their positions stay within the bound; a single query longer than the bound goes alone
         BatchPlan plan; WorkItems work; cdmscan::ScanTemp stPlace;
@@ -160,7 +220,7 @@ static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
         const uint32_t m = plan.m; const uint64_t nPos = plan.cells, nTiles = plan.nTiles;
         DevBuf<uint32_t> planes, place, dCounts; DevBuf<unsigned long long> dStats; DevBuf<cdm_site> dSites;
         if (!work.alloc(m) || !plan.alloc() || !planes.alloc((size_t) nPos * 8) || !place.alloc((size_t) nPos + 1) || !dStats.alloc((size_t) m * 8) || (counts && !dCounts.alloc((size_t) nPos * 8))) {
-            cdm_set_error("cdm_pileup_bases: out of device memory for the counters of %llu positions of %u queries", (unsigned long long) nPos, m); return CDM_ERR_HIP;
+            cdm_set_error("%s: out of device memory for the counters of %llu positions of %u queries", who, (unsigned long long) nPos, m); return CDM_ERR_HIP;
         }
         if (int rc = plan.upload(s)) return rc;
         CDM_HIP(hipMemsetAsync(planes.p, 0, (size_t) nPos * 32, s));
@@ -172,8 +232,12 @@ static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
         a.codes = db->codes; a.nmask = db->nmask; a.maskEnds = (uint32_t) par->mask_ends; a.minDepth = (uint32_t) par->min_depth;
         a.minAlt = (uint32_t) par->min_alt_count; a.minPct = (uint32_t) par->min_alt_percent; a.firstQuery = (uint32_t) b0;
         a.nPos = nPos; a.planes = planes.p; a.stats = dStats.p; a.place = place.p; a.counts = counts ? dCounts.p : nullptr; a.sites = nullptr;
+        // the gapped records are sorted by query: the batch's are one contiguous range
+        const uint64_t g1 = gr.end(g0, b0 + m);
+        a.grec = gr.dRecs.p ? gr.dRecs.p + g0 : nullptr; a.gops = gr.dOps.p; a.nG = (uint32_t) (g1 - g0);      // (fewer than 2^31 operation words: fewer records)
         hipEventRecord(ctx->ev0, s);
         launchWaveItems(s, k_base_counts, a, work.n);
+        launchWaveItems(s, k_base_counts_gapped, a, ((uint64_t) a.nG + 63) / 64);
         launchTiles(s, k_base_sites, a, nTiles);
         uint32_t nSites = 0;
         if (sites) {
@@ -184,34 +248,56 @@ static int cdm_bases_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
         CDM_LAUNCH_CHECK();
         CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
         if (counts && nPos) CDM_HIP(hipMemcpyAsync(counts + countsAt * 8, dCounts.p, (size_t) nPos * 32, hipMemcpyDeviceToHost, s));
-        if (int rc = finishTimed(ctx, "cdm_pileup_bases", "kernels", msTotal)) return rc;
+        if (int rc = finishTimed(ctx, who, "kernels", msTotal)) return rc;
         if (nSites) {       // the records of this batch behind those of the batches before it
-            if (!dSites.alloc(nSites)) { cdm_set_error("cdm_pileup_bases: out of device memory for %u site records", nSites); return CDM_ERR_HIP; }
+            if (!dSites.alloc(nSites)) { cdm_set_error("%s: out of device memory for %u site records", who, nSites); return CDM_ERR_HIP; }
             a.sites = dSites.p;
             hipEventRecord(ctx->ev0, s);
             launchTiles(s, k_base_emit, a, nTiles);
             hipEventRecord(ctx->ev1, s);
             CDM_LAUNCH_CHECK();
-            if (int rc = appendRecords(s, "cdm_pileup_bases", "site", sites, nSitesOut, (const cdm_site *) dSites.p, nSites)) return rc;
-            if (int rc = finishTimed(ctx, "cdm_pileup_bases", "emission", msTotal)) return rc;
+            if (int rc = appendRecords(s, who, "site", sites, nSitesOut, (const cdm_site *) dSites.p, nSites)) return rc;
+            if (int rc = finishTimed(ctx, who, "emission", msTotal)) return rc;
         }
-        countsAt += nPos; b0 += m;
+        countsAt += nPos; b0 += m; g0 = g1;
     }
     if (kernelMs) *kernelMs = msTotal;
     return CDM_OK;
 }
 
+// the checks of the two entry points
+static int basesCheck(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_bases_params *par) {
+    if (par->mask_ends < 0 || par->mask_ends > BS_MAX_MASK) { cdm_set_error("%s: mask_ends = %d; 0 to %d positions are left out at either end of a read", who, par->mask_ends, BS_MAX_MASK); return CDM_ERR_INVALID; }
+    if (par->min_depth < 1) { cdm_set_error("%s: min_depth = %d; a called position has at least one base", who, par->min_depth); return CDM_ERR_INVALID; }
+    if (par->min_alt_count < 1) { cdm_set_error("%s: min_alt_count = %d; a second allele has at least one base", who, par->min_alt_count); return CDM_ERR_INVALID; }
+    if (par->min_alt_percent < 0 || par->min_alt_percent > 100) { cdm_set_error("%s: min_alt_percent = %d; a percentage of the depth is 0 to 100", who, par->min_alt_percent); return CDM_ERR_INVALID; }
+    return pileupCheckArgs(who, db, alns, queries, n_queries);
+}
+
 extern "C" int cdm_pileup_bases(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_bases_params *par,
                                 uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *n_sites, float *kernel_ms) {
-    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_bases");
-    if (!ctx || !db || !alns || !par || (sites && !n_sites) || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_bases: NULL argument"); return CDM_ERR_INVALID; }
-    if (par->mask_ends < 0 || par->mask_ends > BS_MAX_MASK) { cdm_set_error("cdm_pileup_bases: mask_ends = %d; 0 to %d positions are left out at either end of a read", par->mask_ends, BS_MAX_MASK); return CDM_ERR_INVALID; }
-    if (par->min_depth < 1) { cdm_set_error("cdm_pileup_bases: min_depth = %d; a called position has at least one base", par->min_depth); return CDM_ERR_INVALID; }
-    if (par->min_alt_count < 1) { cdm_set_error("cdm_pileup_bases: min_alt_count = %d; a second allele has at least one base", par->min_alt_count); return CDM_ERR_INVALID; }
-    if (par->min_alt_percent < 0 || par->min_alt_percent > 100) { cdm_set_error("cdm_pileup_bases: min_alt_percent = %d; a percentage of the depth is 0 to 100", par->min_alt_percent); return CDM_ERR_INVALID; }
-    if (int rc = pileupCheckArgs("cdm_pileup_bases", db, alns, queries, n_queries)) return rc;
+    static const char *const WHO = "cdm_pileup_bases";
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (sites && !n_sites) || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = basesCheck(WHO, db, alns, queries, n_queries, par)) return rc;
+    GappedRecords none;
     return runWithRecords(ctx, n_queries, sites, n_sites, kernel_ms, [&](cdm_site **got, uint64_t *nGot, float *ms) {
-        return cdm_bases_impl(ctx, db, alns, queries, n_queries, par, stats, counts, got, nGot, ms);
+        return cdm_bases_impl(ctx, WHO, db, alns, queries, n_queries, none, par, stats, counts, got, nGot, ms);
+    });
+}
+
+extern "C" int cdm_pileup_bases_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_gap_rec *recs, uint64_t n_recs,
+                                       const uint32_t *ops, uint64_t n_ops, const cdm_bases_params *par, uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *n_sites,
+                                       float *kernel_ms) {
+    static const char *const WHO = "cdm_pileup_bases_gapped";
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (n_recs && (!recs || !ops)) || (sites && !n_sites) || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = basesCheck(WHO, db, alns, queries, n_queries, par)) return rc;
+    if (n_ops >> 31) { cdm_set_error("%s: %llu operation words; the 32-bit record slots hold fewer than 2^31", WHO, (unsigned long long) n_ops); return CDM_ERR_UNSUPPORTED; }
+    GappedRecords gr; gr.recs = recs; gr.nRecs = n_recs; gr.ops = ops; gr.nOps = n_ops;
+    return runWithRecords(ctx, n_queries, sites, n_sites, kernel_ms, [&](cdm_site **got, uint64_t *nGot, float *ms) {
+        return cdm_bases_impl(ctx, WHO, db, alns, queries, n_queries, gr, par, stats, counts, got, nGot, ms);
     });
 }
 

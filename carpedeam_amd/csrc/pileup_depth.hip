@@ -7,7 +7,8 @@
 // qe; len + 1 cells per listed query, the last one its closing cell), every query's cells sum to zero, and ONE device-wide prefix
 // sum over the batch's cells turns the marks into depths - no segmented scan.  A third kernel walks the positions in tiles and
 // reduces the statistics.  The cells live modulo 2^32: a depth is below the query's record count, and a query with 2^32 records or
-// more is refused.
+// more is refused.  cdm_pileup_depth_gapped and cdm_pileup_breaks_gapped are the same two host sequences with the caller's gapped
+// records (cdm_pileup_gapped's) marked into the same cells by a kernel of their own, depthMarkGapped.
 #include "pileup.h"
 
 namespace {
@@ -22,6 +23,9 @@ struct DepthArgs : TiledArgs {      // (items: marking; tiles: statistics)
     uint32_t *cells;                // [base[nq]]
     unsigned long long *stats;      // [nq][8]
     uint32_t *track;                // NULL, or [base[nq] - nq]: the depths without the closing cells
+    const cdm_gap_rec *grec;        // the *_gapped calls: the batch's gapped records [nG] (query: the index into the call's list)
+    const uint32_t *gops;           // the caller's whole operation pool
+    uint32_t nG, firstQuery;        // firstQuery: the batch's first listed query
 };
 // The marks of one item (listed query, chunk of its records) by one wave, lanes take records: +1 at qs and -1 behind qe in the depth
 // cells; with SPAN (cdm_pileup_breaks, below) also +1 at qs + w and -1 at qe + 2 - w in a second plane of the same
@@ -55,6 +59,51 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_depth_marks(DepthArgs a, uint
     const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
     if (local >= nThis) return;
     depthMarkItem<false>(a, first + local, lane, 0u, 0ull);
+}
+
+// The marks of the gapped records (cdm_pileup_depth_gapped, cdm_pileup_breaks_gapped; include/carpedeam_hip.h), a thread per record
+// into the cells the ungapped marks use, in front of the one prefix sum: +1 at p and -1 at p + g for every M operation of g letters at
+// query position p - a deleted letter gets no depth.  With SPAN one mark pair in the span plane: with C M columns on the query
+// positions m_1 < .. < m_C, a record of C >= 2 w spans the boundaries m_w + 1 .. m_(C - w + 1), found in a second walk (the words are
+// few and stay in cache).  reads and columns (C) go to the query's stats row, one atomic of each per wave where its lanes share a
+// query - the records are sorted by query.  indelCheckRecords (pileup.h): pos + span <= the query's length, so every cell lies inside
+// the query's, the closing cell included.
+template <bool SPAN>
+__device__ __forceinline__ void depthMarkGapped(const DepthArgs &a, uint64_t i, int lane, uint32_t w, uint64_t plane) {
+    const bool live = i < a.nG;
+    uint32_t qi = 0, C = 0;
+    if (live) {
+        const cdm_gap_rec r = a.grec[i];
+        qi = r.query - a.firstQuery;
+        uint32_t *cell = a.cells + a.base[qi];
+        gappedWalk(r, a.gops, [&](uint32_t p, uint32_t, uint32_t g) {
+            C += g;
+            atomicAdd(&cell[p], 1u);                            // (results unused: atomics without return)
+            atomicAdd(&cell[p + g], 0xFFFFFFFFu);
+        }, [](uint32_t, uint32_t, uint32_t, uint32_t) {});
+        if (SPAN && C >= 2u * w) {
+            // the w-th and the (C - w + 1)-th M column, counted from 1: column k lies in the M operation that holds the columns
+            // seen + 1 .. seen + g
+            const uint32_t kLo = w, kHi = C - w + 1u;
+            uint32_t seen = 0, mLo = 0, mHi = 0;
+            gappedWalk(r, a.gops, [&](uint32_t p, uint32_t, uint32_t g) {
+                if (kLo > seen && kLo <= seen + g) mLo = p + (kLo - seen - 1u);
+                if (kHi > seen && kHi <= seen + g) mHi = p + (kHi - seen - 1u);
+                seen += g;
+            }, [](uint32_t, uint32_t, uint32_t, uint32_t) {});
+            atomicAdd(&cell[plane + mLo + 1u], 1u);             // mLo < mHi + 1 <= pos + span <= the query's length
+            atomicAdd(&cell[plane + mHi + 1u], 0xFFFFFFFFu);
+        }
+    }
+    const unsigned long long all = __ballot(live);
+    if (!all) return;
+    const int head = __ffsll((long long) all) - 1;
+    const uint32_t qi0 = (uint32_t) __shfl((int) qi, head, 64);
+    if (!__ballot(live && qi != qi0)) addReadsColumns(&a.stats[(uint64_t) qi0 * 8], &a.stats[(uint64_t) qi0 * 8 + 1], live ? 1u : 0u, live ? C : 0ull, lane);
+    else if (live) { atomicAdd(&a.stats[(uint64_t) qi * 8], 1ull); atomicAdd(&a.stats[(uint64_t) qi * 8 + 1], (unsigned long long) C); }
+}
+__global__ __launch_bounds__(DP_NT) void k_depth_gapped(DepthArgs a, uint64_t first) {
+    depthMarkGapped<false>(a, (first + blockIdx.x) * DP_NT + threadIdx.x, threadIdx.x & 63, 0u, 0ull);
 }
 
 // statistics: one block per item (listed query, tile of DP_TILE positions) of this launch's slice, on the scanned cells:
@@ -119,6 +168,10 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_break_marks(BreakArgs a, uint
     const uint64_t local = (uint64_t) blockIdx.x * PU_WAVES + wave;
     if (local >= nThis) return;
     depthMarkItem<true>(a.d, first + local, lane, a.anchor, a.plane);
+}
+// and the marks of the gapped records, a thread per record, into both planes
+__global__ __launch_bounds__(DP_NT) void k_break_gapped(BreakArgs a, uint64_t first) {
+    depthMarkGapped<true>(a.d, (first + blockIdx.x) * DP_NT + threadIdx.x, threadIdx.x & 63, a.anchor, a.plane);
 }
 
 // the item (listed query, tile of DP_TILE boundaries) of a block with the query's scanned cells: depth[i] = dep[i] and span[i] = spn[i]
@@ -233,13 +286,26 @@ __global__ void k_break_flags(BreakArgs a) {
 
 }  // namespace
 
-static int cdm_depth_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_depth_params *par, uint64_t *stats, uint32_t *depth) {
+// the gapped records of the batch [b0, b0 + m) into the kernel arguments: the range [g0, g1) of the sorted records; -> g1
+static uint64_t depthGappedRange(DepthArgs &a, const GappedRecords &gr, uint64_t g0, uint64_t b0, uint32_t m) {
+    const uint64_t g1 = gr.end(g0, b0 + m);
+    a.grec = gr.dRecs.p ? gr.dRecs.p + g0 : nullptr; a.gops = gr.dOps.p; a.nG = (uint32_t) (g1 - g0); a.firstQuery = (uint32_t) b0;        // (fewer than 2^31 operation words: fewer records)
+    return g1;
+}
+
+// The host sequence of cdm_pileup_depth (who; gr without records) and of cdm_pileup_depth_gapped (gr: the caller's gapped records,
+// checked before anything goes to the device).
+static int cdm_depth_impl(cdm_ctx *ctx, const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, GappedRecords &gr, const cdm_depth_params *par,
+                          uint64_t *stats, uint32_t *depth, float *kernelMs) {
     hipStream_t s = ctx->stream;
     const uint32_t chunk = pileupChunk(), edge = (uint32_t) par->edge;
     const uint64_t bound = depthCells();
+    if (int rc = gr.check(who, db, queries, nq)) return rc;
     QuerySizes qs;
-    if (int rc = querySizes(ctx, db, alns, queries, nq, "cdm_pileup_depth", "depth cells", qs)) return rc;
-    float msTotal = 0.f; uint64_t trackAt = 0;
+    if (int rc = querySizes(ctx, db, alns, queries, nq, who, "depth cells", qs)) return rc;
+    if (int rc = gr.checkCounts(who, "depth cells", queries, qs.recs)) return rc;
+    if (int rc = gr.upload(s, who)) return rc;
+    float msTotal = 0.f; uint64_t trackAt = 0, g0 = 0;
     for (uint64_t b0 = 0; b0 < nq;) {
         // the batch: listed queries while their cells stay within the bound; a single query longer than the bound goes alone
         BatchPlan plan; WorkItems work; cdmscan::ScanTemp stCells;
@@ -247,7 +313,7 @@ static int cdm_depth_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
         const uint32_t m = plan.m; const uint64_t nCells = plan.cells, nTrack = nCells - m;
         DevBuf<uint32_t> cells, track; DevBuf<unsigned long long> dStats;
         if (!work.alloc(m) || !plan.alloc() || !cells.alloc(nCells) || !dStats.alloc((size_t) m * 8) || (depth && !track.alloc(nTrack))) {
-            cdm_set_error("cdm_pileup_depth: out of device memory for the %llu cells of %u queries", (unsigned long long) nCells, m); return CDM_ERR_HIP;
+            cdm_set_error("%s: out of device memory for the %llu cells of %u queries", who, (unsigned long long) nCells, m); return CDM_ERR_HIP;
         }
         if (int rc = plan.upload(s)) return rc;
         CDM_HIP(hipMemsetAsync(cells.p, 0, (size_t) nCells * 4, s));
@@ -256,36 +322,44 @@ static int cdm_depth_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *aln
         DepthArgs a;
         fillArgs(a, qs.meta.p, db, alns, par->min_seq_id, par->skip_extended_targets, work, plan);
         a.edge = edge; a.cells = cells.p; a.stats = dStats.p; a.track = depth ? track.p : nullptr;
+        g0 = depthGappedRange(a, gr, g0, b0, m);
         hipEventRecord(ctx->ev0, s);
         launchWaveItems(s, k_depth_marks, a, work.n);
+        launchTiles(s, k_depth_gapped, a, ((uint64_t) a.nG + DP_NT - 1) / DP_NT);
         if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stCells, cells.p, cells.p, (size_t) nCells)) return rc;     // (in place: scan.h)
         launchTiles(s, k_depth_stats, a, plan.nTiles);
         hipEventRecord(ctx->ev1, s);
         CDM_LAUNCH_CHECK();
         CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
         if (depth && nTrack) CDM_HIP(hipMemcpyAsync(depth + trackAt, track.p, (size_t) nTrack * 4, hipMemcpyDeviceToHost, s));
-        if (int rc = finishTimed(ctx, "cdm_pileup_depth", "kernels", msTotal)) return rc;
+        if (int rc = finishTimed(ctx, who, "kernels", msTotal)) return rc;
         for (uint32_t i = 0; i < m; i++) {
             uint64_t *row = stats + (b0 + i) * 8;
             const uint64_t L = qs.len[b0 + i];
             row[3] = L > 2ull * edge ? L - 2ull * edge : L;
             // max x sum bounds sumsq from above: where it does not fit 64 bits, sumsq may have wrapped
-            if (((unsigned __int128) row[7] * row[5]) >> 64) { cdm_set_error("cdm_pileup_depth: query %u: max depth %llu x depth sum %llu does not fit 64 bits (the bound of sumsq)", queries[b0 + i], (unsigned long long) row[7], (unsigned long long) row[5]); return CDM_ERR_UNSUPPORTED; }
+            if (((unsigned __int128) row[7] * row[5]) >> 64) { cdm_set_error("%s: query %u: max depth %llu x depth sum %llu does not fit 64 bits (the bound of sumsq)", who, queries[b0 + i], (unsigned long long) row[7], (unsigned long long) row[5]); return CDM_ERR_UNSUPPORTED; }
         }
         trackAt += nTrack; b0 += m;
     }
     ctx->lastMs[17] = msTotal;
+    if (kernelMs) *kernelMs = msTotal;
     return CDM_OK;
 }
 
-static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, const cdm_breaks_params *par, uint64_t *stats, uint32_t *track,
-                           cdm_break **breaks, uint64_t *nBreaksOut, float *kernelMs) {
+// The host sequence of cdm_pileup_breaks (who; gr without records) and of cdm_pileup_breaks_gapped (gr: the caller's gapped records,
+// checked before anything goes to the device).
+static int cdm_breaks_impl(cdm_ctx *ctx, const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t nq, GappedRecords &gr, const cdm_breaks_params *par,
+                           uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *nBreaksOut, float *kernelMs) {
     hipStream_t s = ctx->stream;
     const uint32_t chunk = pileupChunk();
     const uint64_t bound = depthCells();
+    if (int rc = gr.check(who, db, queries, nq)) return rc;
     QuerySizes qs;
-    if (int rc = querySizes(ctx, db, alns, queries, nq, "cdm_pileup_breaks", "cells", qs)) return rc;
-    float msTotal = 0.f; uint64_t trackAt = 0;
+    if (int rc = querySizes(ctx, db, alns, queries, nq, who, "cells", qs)) return rc;
+    if (int rc = gr.checkCounts(who, "cells", queries, qs.recs)) return rc;
+    if (int rc = gr.upload(s, who)) return rc;
+    float msTotal = 0.f; uint64_t trackAt = 0, g0 = 0;
     for (uint64_t b0 = 0; b0 < nq;) {
         // the batch: listed queries while the cells of their two planes stay within the bound; a single longer query goes alone
         BatchPlan plan; WorkItems work; cdmscan::ScanTemp stCells, stPlace;
@@ -295,7 +369,7 @@ static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
         for (uint32_t i = 0; i < m; i++) init[(size_t) i * 8 + 6] = ~0ull;
         DevBuf<uint32_t> cells, dTrack, place; DevBuf<unsigned long long> dStats; DevBuf<cdm_break> dBreaks;
         if (!work.alloc(m) || !plan.alloc() || !cells.alloc((size_t) N * 2) || !place.alloc((size_t) N + 1) || !dStats.alloc((size_t) m * 8) || (track && !dTrack.alloc(nTrack))) {
-            cdm_set_error("cdm_pileup_breaks: out of device memory for the %llu cells of %u queries", (unsigned long long) N * 2, m); return CDM_ERR_HIP;
+            cdm_set_error("%s: out of device memory for the %llu cells of %u queries", who, (unsigned long long) N * 2, m); return CDM_ERR_HIP;
         }
         if (int rc = plan.upload(s)) return rc;
         CDM_HIP(hipMemcpyAsync(dStats.p, init.data(), (size_t) m * 64, hipMemcpyHostToDevice, s));        // (zeros; min_span all ones)
@@ -307,8 +381,10 @@ static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
         a.d.edge = (uint32_t) par->edge; a.d.cells = cells.p; a.d.stats = dStats.p; a.d.track = track ? dTrack.p : nullptr;
         a.plane = N; a.anchor = (uint32_t) par->anchor; a.minSpan = (uint32_t) par->min_span; a.minPct = (uint32_t) par->min_span_percent; a.firstQuery = (uint32_t) b0;
         a.place = place.p; a.out = nullptr; a.nRuns = 0;
+        g0 = depthGappedRange(a.d, gr, g0, b0, m);
         hipEventRecord(ctx->ev0, s);
         launchWaveItems(s, k_break_marks, a, work.n);
+        launchTiles(s, k_break_gapped, a, ((uint64_t) a.d.nG + DP_NT - 1) / DP_NT);
         if (int rc = cdmscan::exclusiveScan<uint32_t>(s, stCells, cells.p, cells.p, (size_t) N * 2)) return rc;      // (in place: scan.h; both planes, each summing to zero)
         launchTiles(s, k_break_classify, a, nTiles);
         // The runs are numbered whether or not the caller takes the records: `joins` needs every run's `uncovered`.
@@ -317,9 +393,9 @@ static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
         CDM_HIP(hipMemcpyAsync(&nRuns, place.p + N, 4, hipMemcpyDeviceToHost, s));
         hipEventRecord(ctx->ev1, s);
         CDM_LAUNCH_CHECK();
-        if (int rc = finishTimed(ctx, "cdm_pileup_breaks", "kernels", msTotal)) return rc;
+        if (int rc = finishTimed(ctx, who, "kernels", msTotal)) return rc;
         if (nRuns) {
-            if (!dBreaks.alloc(nRuns)) { cdm_set_error("cdm_pileup_breaks: out of device memory for %u break records", nRuns); return CDM_ERR_HIP; }
+            if (!dBreaks.alloc(nRuns)) { cdm_set_error("%s: out of device memory for %u break records", who, nRuns); return CDM_ERR_HIP; }
             a.out = dBreaks.p; a.nRuns = nRuns;
             hipEventRecord(ctx->ev0, s);
             hipLaunchKernelGGL(k_break_init, CDM_GRID(((uint64_t) nRuns + 255) / 256, 256), dim3(256), 0, s, a);
@@ -328,11 +404,11 @@ static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
             hipEventRecord(ctx->ev1, s);
             CDM_LAUNCH_CHECK();
             // the records of this batch behind those of the batches before it
-            if (breaks) { if (int rc = appendRecords(s, "cdm_pileup_breaks", "break", breaks, nBreaksOut, (const cdm_break *) dBreaks.p, nRuns)) return rc; }
+            if (breaks) { if (int rc = appendRecords(s, who, "break", breaks, nBreaksOut, (const cdm_break *) dBreaks.p, nRuns)) return rc; }
         }
         CDM_HIP(hipMemcpyAsync(stats + b0 * 8, dStats.p, (size_t) m * 64, hipMemcpyDeviceToHost, s));
         if (track && nTrack) CDM_HIP(hipMemcpyAsync(track + trackAt, dTrack.p, (size_t) nTrack * 4, hipMemcpyDeviceToHost, s));
-        if (int rc = finishTimed(ctx, "cdm_pileup_breaks", "emission", msTotal, nRuns != 0)) return rc;
+        if (int rc = finishTimed(ctx, who, "emission", msTotal, nRuns != 0)) return rc;
         for (uint32_t i = 0; i < m; i++) { uint64_t *row = stats + (b0 + i) * 8; if (row[2] == 0) row[6] = 0; }       // (an empty window has no smallest span)
         trackAt += nTrack; b0 += m;
     }
@@ -340,28 +416,69 @@ static int cdm_breaks_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
     return CDM_OK;
 }
 
+// the checks of the two depth entry points, and of the two break point entry points
+static int depthCheck(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_depth_params *par) {
+    if (par->edge < 0) { cdm_set_error("%s: edge = %d; the positions left out at either end of a contig are 0 or more", who, par->edge); return CDM_ERR_INVALID; }
+    return pileupCheckArgs(who, db, alns, queries, n_queries);
+}
+static int breaksCheck(const char *who, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_breaks_params *par) {
+    if (par->anchor < 1 || par->anchor > BK_MAX_ANCHOR) { cdm_set_error("%s: anchor = %d; a spanning read has 1 to %d columns on either side of a boundary", who, par->anchor, BK_MAX_ANCHOR); return CDM_ERR_INVALID; }
+    if (par->edge < par->anchor || par->edge > BK_MAX_EDGE) { cdm_set_error("%s: edge = %d; anchor (%d) to %d boundaries are left out at either end of a query", who, par->edge, par->anchor, BK_MAX_EDGE); return CDM_ERR_INVALID; }
+    if (par->min_span < 1 || par->min_span > BK_MAX_SPAN) { cdm_set_error("%s: min_span = %d; a boundary is held by 1 to %d spanning reads", who, par->min_span, BK_MAX_SPAN); return CDM_ERR_INVALID; }
+    if (par->min_span_percent < 0 || par->min_span_percent > 100) { cdm_set_error("%s: min_span_percent = %d; a percentage of the depth is 0 to 100", who, par->min_span_percent); return CDM_ERR_INVALID; }
+    return pileupCheckArgs(who, db, alns, queries, n_queries);
+}
+
 extern "C" int cdm_pileup_depth(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_depth_params *par,
                                 uint64_t *stats, uint32_t *depth) {
-    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_depth");
-    if (!ctx || !db || !alns || !par || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_depth: NULL argument"); return CDM_ERR_INVALID; }
-    if (par->edge < 0) { cdm_set_error("cdm_pileup_depth: edge = %d; the positions left out at either end of a contig are 0 or more", par->edge); return CDM_ERR_INVALID; }
-    if (int rc = pileupCheckArgs("cdm_pileup_depth", db, alns, queries, n_queries)) return rc;
+    static const char *const WHO = "cdm_pileup_depth";
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = depthCheck(WHO, db, alns, queries, n_queries, par)) return rc;
     if (n_queries == 0) return CDM_OK;
     CDM_HIP(hipSetDevice(ctx->device));
-    return cdm_depth_impl(ctx, db, alns, queries, n_queries, par, stats, depth);
+    GappedRecords none;
+    return cdm_depth_impl(ctx, WHO, db, alns, queries, n_queries, none, par, stats, depth, NULL);
+}
+
+extern "C" int cdm_pileup_depth_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_gap_rec *recs, uint64_t n_recs,
+                                       const uint32_t *ops, uint64_t n_ops, const cdm_depth_params *par, uint64_t *stats, uint32_t *depth, float *kernel_ms) {
+    static const char *const WHO = "cdm_pileup_depth_gapped";
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (n_recs && (!recs || !ops)) || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = depthCheck(WHO, db, alns, queries, n_queries, par)) return rc;
+    if (n_ops >> 31) { cdm_set_error("%s: %llu operation words; the 32-bit record slots hold fewer than 2^31", WHO, (unsigned long long) n_ops); return CDM_ERR_UNSUPPORTED; }
+    if (n_queries == 0) return CDM_OK;
+    CDM_HIP(hipSetDevice(ctx->device));
+    GappedRecords gr; gr.recs = recs; gr.nRecs = n_recs; gr.ops = ops; gr.nOps = n_ops;
+    return cdm_depth_impl(ctx, WHO, db, alns, queries, n_queries, gr, par, stats, depth, kernel_ms);
 }
 
 extern "C" int cdm_pileup_breaks(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_breaks_params *par,
                                  uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *n_breaks, float *kernel_ms) {
-    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, "cdm_pileup_breaks");
-    if (!ctx || !db || !alns || !par || (breaks && !n_breaks) || (n_queries && (!queries || !stats))) { cdm_set_error("cdm_pileup_breaks: NULL argument"); return CDM_ERR_INVALID; }
-    if (par->anchor < 1 || par->anchor > BK_MAX_ANCHOR) { cdm_set_error("cdm_pileup_breaks: anchor = %d; a spanning read has 1 to %d columns on either side of a boundary", par->anchor, BK_MAX_ANCHOR); return CDM_ERR_INVALID; }
-    if (par->edge < par->anchor || par->edge > BK_MAX_EDGE) { cdm_set_error("cdm_pileup_breaks: edge = %d; anchor (%d) to %d boundaries are left out at either end of a query", par->edge, par->anchor, BK_MAX_EDGE); return CDM_ERR_INVALID; }
-    if (par->min_span < 1 || par->min_span > BK_MAX_SPAN) { cdm_set_error("cdm_pileup_breaks: min_span = %d; a boundary is held by 1 to %d spanning reads", par->min_span, BK_MAX_SPAN); return CDM_ERR_INVALID; }
-    if (par->min_span_percent < 0 || par->min_span_percent > 100) { cdm_set_error("cdm_pileup_breaks: min_span_percent = %d; a percentage of the depth is 0 to 100", par->min_span_percent); return CDM_ERR_INVALID; }
-    if (int rc = pileupCheckArgs("cdm_pileup_breaks", db, alns, queries, n_queries)) return rc;
+    static const char *const WHO = "cdm_pileup_breaks";
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (breaks && !n_breaks) || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = breaksCheck(WHO, db, alns, queries, n_queries, par)) return rc;
+    GappedRecords none;
     return runWithRecords(ctx, n_queries, breaks, n_breaks, kernel_ms, [&](cdm_break **got, uint64_t *nGot, float *ms) {
-        return cdm_breaks_impl(ctx, db, alns, queries, n_queries, par, stats, track, got, nGot, ms);
+        return cdm_breaks_impl(ctx, WHO, db, alns, queries, n_queries, none, par, stats, track, got, nGot, ms);
+    });
+}
+
+extern "C" int cdm_pileup_breaks_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries, const cdm_gap_rec *recs, uint64_t n_recs,
+                                        const uint32_t *ops, uint64_t n_ops, const cdm_breaks_params *par, uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *n_breaks,
+                                        float *kernel_ms) {
+    static const char *const WHO = "cdm_pileup_breaks_gapped";
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (alns) CDM_REFUSE_UNDEFINED_ALNS(alns, WHO);
+    if (!ctx || !db || !alns || !par || (n_recs && (!recs || !ops)) || (breaks && !n_breaks) || (n_queries && (!queries || !stats))) { cdm_set_error("%s: NULL argument", WHO); return CDM_ERR_INVALID; }
+    if (int rc = breaksCheck(WHO, db, alns, queries, n_queries, par)) return rc;
+    if (n_ops >> 31) { cdm_set_error("%s: %llu operation words; the 32-bit record slots hold fewer than 2^31", WHO, (unsigned long long) n_ops); return CDM_ERR_UNSUPPORTED; }
+    GappedRecords gr; gr.recs = recs; gr.nRecs = n_recs; gr.ops = ops; gr.nOps = n_ops;
+    return runWithRecords(ctx, n_queries, breaks, n_breaks, kernel_ms, [&](cdm_break **got, uint64_t *nGot, float *ms) {
+        return cdm_breaks_impl(ctx, WHO, db, alns, queries, n_queries, gr, par, stats, track, got, nGot, ms);
     });
 }
 

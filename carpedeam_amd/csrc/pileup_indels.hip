@@ -12,16 +12,14 @@
 //             the query's figures and marks the supported; two scans place the site records and their letter slots
 //   letters   a wave per supported site: the lanes take the events of an inserted allele, the base counts of its g offsets go to LDS
 //             as [62][4], the first g lanes vote
-// The records are caller data: indelCheckRecords refuses, on the host, every record the walks above could follow out of bounds.
+// The records are caller data: indelCheckRecords (pileup.h) refuses, on the host, every record the walks above could follow out of bounds.
 #include "pileup.h"
 #include "radix.h"
 
 namespace {
 
 constexpr uint64_t ID_CELLS_DEFAULT = 1ull << 28, ID_CELLS_MAX = 1ull << 32;
-constexpr uint32_t ID_MAX_GAP = 62;         // letters of an I or D: 2 x the largest band, and 6 bits of the key
-constexpr int ID_G_BITS = 6, ID_POS_SHIFT = 7, ID_QUERY_SHIFT = 31, ID_STATS = 10;
-constexpr uint32_t ID_OP_M = 0, ID_OP_I = 1, ID_OP_D = 2;
+constexpr int ID_G_BITS = 6, ID_POS_SHIFT = 7, ID_QUERY_SHIFT = 31, ID_STATS = 10;      // (ID_MAX_GAP = 62, pileup.h, fits the 6 bits of the key)
 
 // CDM_INDEL_POSITIONS=<cells> (tests): small inputs in several batches
 uint64_t indelPositions() { return envCount("CDM_INDEL_POSITIONS", ID_CELLS_DEFAULT, ID_CELLS_MAX); }
@@ -68,18 +66,6 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_indel_marks(IndelArgs a, uint
         atomicAdd(&cell[(uint32_t) o.qe + 1u], 0xFFFFFFFFu);          // qs <= qe < qLen: at the most the query's closing cell
     }
     addReadsColumns(&a.stats[(uint64_t) qi * ID_STATS], &a.stats[(uint64_t) qi * ID_STATS + 1], nReads, nCols, lane);
-}
-
-// the walk over a gapped record's operations: event(p, kind, g, read offset) for every I and D.  indelCheckRecords: n_ops words inside
-// the pool, M + D = span, M + I = columns
-template <class Event> __device__ __forceinline__ void indelWalk(const cdm_gap_rec &r, const uint32_t *__restrict__ ops, Event event) {
-    uint32_t p = r.pos, off = r.tstart;
-    for (uint32_t j = 0; j < r.n_ops; j++) {
-        const uint32_t w = ops[r.ops + j], g = w >> 2, op = w & 3u;
-        if (op == ID_OP_M) { p += g; off += g; }
-        else if (op == ID_OP_I) { event(p, ID_OP_I, g, off); off += g; }
-        else { event(p, ID_OP_D, g, off); p += g; }
-    }
 }
 
 // gapped records, a thread per record: its two marks, the number of its events, the query's five figures (one atomic of each per wave
@@ -260,34 +246,6 @@ __global__ __launch_bounds__(64 * PU_WAVES) void k_indel_letters(IndelArgs a, ui
 }
 
 // ---------------------------------------------------------------------------------------------- host
-// One pass over the caller's records and their operation words (include/carpedeam_hip.h): CDM_OK, or CDM_ERR_INVALID with the first
-// record that fails.  qLen: the listed queries' lengths; tLen: the length of every sequence of the DB.
-int indelCheckRecords(const char *who, const cdm_gap_rec *recs, uint64_t nRecs, const uint32_t *ops, uint64_t nOps, const std::vector<uint32_t> &qLen, const std::vector<uint32_t> &tLen) {
-    for (uint64_t i = 0; i < nRecs; i++) {
-        const cdm_gap_rec &r = recs[i];
-        auto bad = [&](const char *what) { cdm_set_error("%s: gapped record %llu: %s", who, (unsigned long long) i, what); return CDM_ERR_INVALID; };
-        if (r.query >= qLen.size()) return bad("its query is not an index into the listed queries");
-        if (r.target >= tLen.size()) return bad("its target is not a sequence of the DB");
-        if (r.tlen != tLen[r.target]) return bad("tlen is not the length of its target");
-        if (i && (r.query < recs[i - 1].query || (r.query == recs[i - 1].query && r.pos < recs[i - 1].pos))) return bad("the records do not ascend by (query, pos)");
-        if (r.n_ops < 1 || r.ops > nOps || r.n_ops > nOps - r.ops) return bad("its operations are not words of the pool");
-        uint64_t span = 0, columns = 0;
-        for (uint32_t j = 0; j < r.n_ops; j++) {
-            const uint32_t w = ops[r.ops + j], g = w >> 2, op = w & 3u;
-            if (op > ID_OP_D || g < 1) return bad("an operation that is not M, I or D of at least one letter");
-            if ((j == 0 || j + 1 == r.n_ops) && op != ID_OP_M) return bad("its first or last operation is not M");
-            if (j && (ops[r.ops + j - 1] & 3u) == op) return bad("two neighbouring operations of one code");
-            if (op != ID_OP_M && g > ID_MAX_GAP) return bad("an insertion or deletion of more than 62 letters");
-            if (op != ID_OP_I) span += g;
-            if (op != ID_OP_D) columns += g;
-        }
-        if (span != r.span || columns != r.columns) return bad("its operations do not sum to span and columns");
-        if ((uint64_t) r.pos + r.span > qLen[r.query]) return bad("pos + span lies beyond its query");
-        if ((uint64_t) r.tstart + r.columns > r.tlen) return bad("tstart + columns lies beyond its target");
-    }
-    return CDM_OK;
-}
-
 void launchHeads(hipStream_t s, void (*kernel)(HeadArgs, uint64_t), const HeadArgs &h) { launchTiles(s, kernel, h, ((uint64_t) h.n + DP_NT - 1) / DP_NT); }
 
 }  // namespace
@@ -298,23 +256,13 @@ static int cdm_indels_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
     hipStream_t s = ctx->stream;
     const uint32_t chunk = pileupChunk();
     const uint64_t bound = indelPositions();
-    // the records are checked before anything goes up or is launched: the lengths they are held against come down in two plain copies
-    std::vector<uint32_t> tLen, qLen(nq);
-    if (nRecs) {
-        tLen.resize(db->n);
-        CDM_HIP(hipMemcpy(tLen.data(), db->len, (size_t) db->n * 4, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < nq; i++) qLen[i] = tLen[queries[i]];
-        if (int rc = indelCheckRecords(WHO, recs, nRecs, ops, nOps, qLen, tLen)) return rc;
-        std::vector<uint32_t>().swap(tLen);
-    }
+    // the records are checked before anything goes up or is launched
+    GappedRecords gr; gr.recs = recs; gr.nRecs = nRecs; gr.ops = ops; gr.nOps = nOps;
+    if (int rc = gr.check(WHO, db, queries, nq)) return rc;
     QuerySizes qs;
     if (int rc = querySizes(ctx, db, alns, queries, nq, WHO, "cells", qs)) return rc;
-    DevBuf<cdm_gap_rec> dRecs; DevBuf<uint32_t> dOps;
-    if (nRecs) {
-        if (!dRecs.alloc(nRecs) || !dOps.alloc(nOps)) { cdm_set_error("%s: out of device memory for %llu gapped records and %llu operations", WHO, (unsigned long long) nRecs, (unsigned long long) nOps); return CDM_ERR_HIP; }
-        CDM_HIP(hipMemcpyAsync(dRecs.p, recs, (size_t) nRecs * sizeof(cdm_gap_rec), hipMemcpyHostToDevice, s));
-        CDM_HIP(hipMemcpyAsync(dOps.p, ops, (size_t) nOps * 4, hipMemcpyHostToDevice, s));
-    }
+    if (int rc = gr.upload(s, WHO)) return rc;
+    const DevBuf<cdm_gap_rec> &dRecs = gr.dRecs; const DevBuf<uint32_t> &dOps = gr.dOps;
     float msTotal = 0.f; uint64_t trackAt = 0, g0 = 0;
     for (uint64_t b0 = 0; b0 < nq;) {
         // the batch: listed queries while their cells stay within the bound; a single query longer than the bound goes alone.  The gapped
@@ -322,8 +270,7 @@ static int cdm_indels_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *al
         BatchPlan plan; WorkItems work; cdmscan::ScanTemp stCells, stEv, stAllele, stPlace, stSite, stLetter;
         plan.cut(qs.len, b0, 1u, [](uint64_t len) { return len + 1ull; }, bound);
         const uint32_t m = plan.m; const uint64_t nCells = plan.cells, nTrack = nCells - m;
-        uint64_t g1 = g0;
-        while (g1 < nRecs && recs[g1].query < b0 + m) g1++;
+        const uint64_t g1 = gr.end(g0, b0 + m);
         const uint32_t nG = (uint32_t) (g1 - g0);       // (fewer than 2^31 operation words: fewer records)
         const uint64_t recTiles = ((uint64_t) nG + DP_NT - 1) / DP_NT;
         DevBuf<uint32_t> cells, dTrack, evAt; DevBuf<unsigned long long> dStats;

@@ -595,7 +595,8 @@ void cdm_map_free(cdm_map_rec *recs, uint32_t *mism);
  * its end cell) is CDM_ERR_INVALID, as is a NULL argument, a query index >= the DB's size or listed
  * twice, and hits or alignments of another DB size.  A listed query with 2^32 hits or more, or a hit set of 2^40 or more, is
  * CDM_ERR_UNSUPPORTED; the set with the coordinates -1 record is refused as cdm_pileup_map refuses it.
- * Not covered: reads of more than 4096 letters, a mapping quality, and the four tables above, which still count ungapped records only. */
+ * Not covered: reads of more than 4096 letters and a mapping quality.  The depth, variant and break tables take these records through
+ * their *_gapped calls, below; cdm_pileup_profile counts ungapped records only. */
 typedef struct cdm_gap_params {
     float    min_seq_id;
     int32_t  skip_extended_targets;
@@ -671,6 +672,42 @@ int  cdm_pileup_indels(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, 
                        uint64_t *stats, uint32_t *track, cdm_indel_site **sites, uint64_t *n_sites, uint8_t **letters, uint64_t *n_letters,
                        float *kernel_ms);
 void cdm_indel_free(cdm_indel_site *sites, uint8_t *letters);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The rescued reads in the depth, variant and break tables (not modules of the reference; csrc/pileup_depth.hip, csrc/pileup_bases.hip):
+ * cdm_pileup_depth, cdm_pileup_bases and cdm_pileup_breaks over the ungapped set PLUS gapped records.  recs / ops are the host arrays
+ * cdm_pileup_gapped returned for the same `queries`, exactly as cdm_pileup_indels takes them.  The parameter structs, result layouts,
+ * record types, free functions and flag meanings are those of the three calls above; every ungapped record counts exactly as there,
+ * and every gapped record given counts as well, primary or secondary (a read counts on every query it lies on).
+ * A record's operations are walked from p = pos and o = tstart: M of g letters gives the columns j < g, column j on query position
+ * p + j with the read's oriented offset o + j, then both advance; I advances o; D advances p.  With C the number of M columns,
+ * m_1 < .. < m_C their query positions, and r = reverse ? tlen - 1 - offset : offset the position in the read's own orientation:
+ *   depth     depth[i] += 1 for every M column on position i.  A deleted query letter gets no depth from the read (it has no base
+ *             there; the default of samtools depth), so depth[i] >= the sum of position i's eight counters still holds
+ *   reads     stats 0 of all three: the ungapped value plus one per gapped record of the query
+ *   columns   stats 1 of all three: the ungapped value plus C per record - still the sum of depth over the query
+ *   span      a gapped record with C >= 2 w, w = anchor, spans the boundaries m_w + 1 <= b <= m_(C - w + 1): at least w M columns
+ *             strictly left of b and at least w at or right of it; for a record of one M operation this is qs + w <= b <= qe + 1 - w.
+ *             Weak boundaries, runs, uncovered, depth_left, depth_right and the flags come from the summed depth and span exactly as
+ *             in cdm_pileup_breaks: a deleted stretch that reads span has depth 0 and a positive span, is not weak and gives no break
+ *   bases     an M column on position i is left out when the read's N bit is set at r, and - with mask_ends = m > 0 - when r < m or
+ *             tlen - 1 - r < m; otherwise counts[i][rev * 4 + b] += 1 with b the read's mapped code at r, complemented when reverse.
+ *             Inserted letters have no query position and count nowhere.  Classification, stats 2..7 and the sites are unchanged
+ *   kernel_ms NULL, or receives the device time of the kernels, those over the gapped records included (0 behind a refusal)
+ * The records are caller data and get cdm_pileup_indels' one-pass host check before anything goes to the device: the first record that
+ * fails is named and the call returns CDM_ERR_INVALID.  With n_recs == 0 each call returns what its ungapped counterpart returns,
+ * array for array; n_queries == 0 is CDM_OK (nothing is launched).  A listed query whose ungapped plus gapped records reach 2^32, or
+ * 2^31 operation words or more, is CDM_ERR_UNSUPPORTED (the cells are 32 bits wide; not reachable at test size, not tested).
+ * Not covered: cdm_pileup_profile (the damage table is a rate, and the rescued reads are a small share of it), and a mapping quality. */
+int  cdm_pileup_depth_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                             const cdm_gap_rec *recs, uint64_t n_recs, const uint32_t *ops, uint64_t n_ops, const cdm_depth_params *par,
+                             uint64_t *stats, uint32_t *depth, float *kernel_ms);
+int  cdm_pileup_bases_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                             const cdm_gap_rec *recs, uint64_t n_recs, const uint32_t *ops, uint64_t n_ops, const cdm_bases_params *par,
+                             uint64_t *stats, uint32_t *counts, cdm_site **sites, uint64_t *n_sites, float *kernel_ms);
+int  cdm_pileup_breaks_gapped(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                              const cdm_gap_rec *recs, uint64_t n_recs, const uint32_t *ops, uint64_t n_ops, const cdm_breaks_params *par,
+                              uint64_t *stats, uint32_t *track, cdm_break **breaks, uint64_t *n_breaks, float *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ancient_read_assemble.  Replaces the loops at src/assembler/ancientReadsResults.cpp:178-581.
