@@ -178,7 +178,7 @@ EXPORTS = [
     "cdm_last_error", "cdm_ctx_create", "cdm_ctx_destroy", "cdm_ctx_sync", "cdm_ctx_stream", "cdm_ctx_last_kernel_ms",
     "cdm_seqdb_upload", "cdm_seqdb_synth", "cdm_seqdb_size", "cdm_seqdb_residues", "cdm_seqdb_max_len", "cdm_seqdb_meta",
     "cdm_seqdb_download", "cdm_seqdb_download_stream", "cdm_seqdb_free", "cdm_seqdb_select_ext", "cdm_seqdb_select_assembled", "cdm_seqdb_index_copy", "cdm_seqdb_words", "cdm_seqdb_copy_packed", "cdm_seqdb_from_packed", "cdm_damage_load", "cdm_damage_get", "cdm_kmermatch", "cdm_hits_upload", "cdm_hits_count",
-    "cdm_hits_download", "cdm_hits_free", "cdm_rescore", "cdm_alns_upload", "cdm_alns_count", "cdm_alns_download", "cdm_alns_free",
+    "cdm_hits_download", "cdm_hits_free", "cdm_rescore", "cdm_rescore_tile", "cdm_alns_undefined", "cdm_alns_ry_download", "cdm_alns_upload", "cdm_alns_count", "cdm_alns_download", "cdm_alns_free",
     "cdm_evalue", "cdm_bit_score", "cdm_gapped_evalue", "cdm_correct", "cdm_extend",
     "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kpart_free", "cdm_dev_copy",
     "cdm_seqdb_from_packed_ext", "cdm_seqdb_copy_ext", "cdm_seqdb_export_packed", "cdm_seqdb_import_packed", "cdm_contig_merge", "cdm_cyclecheck", "cdm_seqdb_has_raw", "cdm_seqdb_copy_raw", "cdm_seqdb_attach_raw",
@@ -272,6 +272,11 @@ def lib():
         l.cdm_hits_upload.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
         l.cdm_hits_download.argtypes = [vp, vp, vp, vp]
         l.cdm_rescore.argtypes = [vp, vp, vp, C.POINTER(RescoreParams), C.POINTER(vp)]
+        l.cdm_rescore_tile.argtypes = []
+        l.cdm_rescore_tile.restype = C.c_uint32
+        l.cdm_alns_undefined.argtypes = [vp]
+        l.cdm_alns_undefined.restype = C.c_uint64
+        l.cdm_alns_ry_download.argtypes = [vp, vp, vp]
         l.cdm_rescore_hamming.argtypes = [vp, vp, vp, C.POINTER(HammingParams), C.POINTER(vp)]
         l.cdm_align_hits.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.c_uint64, vp, vp]
         l.cdm_align_mode.argtypes = []
@@ -489,6 +494,17 @@ class Hits(_Csr):
 
 class Alns(_Csr):
     free, count_fn, download_fn, dtype = "cdm_alns_free", "cdm_alns_count", "cdm_alns_download", ALN_DTYPE
+
+    @property
+    def undefined_records(self):
+        """identity records written with the coordinates -1 (cdm_alns_undefined)"""
+        return int(lib().cdm_alns_undefined(self.h))
+
+    def download_ry(self):
+        """the purine/pyrimidine mismatch count of every record of a set made by Ctx.rescore (0xFFFF = not counted)"""
+        ry = np.empty(self.count, np.uint16)
+        _check(lib().cdm_alns_ry_download(self.ctx.h, self.h, _ptr(ry)))
+        return ry
 
 
 KPART_SLICES = 256          # CDM_KPART_SLICES
@@ -722,6 +738,11 @@ class Ctx:
         h = C.c_void_p()
         _check(lib().cdm_rescore(self.h, db.h, hits.h, C.byref(par), C.byref(h)))
         return Alns(self, h, db.n)
+
+    @staticmethod
+    def rescore_tile():
+        """hits per block of cdm_rescore's kernel"""
+        return int(lib().cdm_rescore_tile())
 
     def rescore_hamming(self, db, hits, par=None):
         par = par or HammingParams.linclust()

@@ -245,6 +245,16 @@ extern "C" int cdm_alns_download(cdm_ctx *ctx, const cdm_alns *a, uint64_t *offs
     CDM_HIP(hipStreamSynchronize(ctx->stream));
     return CDM_OK;
 }
+extern "C" uint32_t cdm_rescore_tile(void) { return cdm_rescore_tile_impl(); }
+extern "C" uint64_t cdm_alns_undefined(const cdm_alns *a) { return a->undefinedRecords; }
+extern "C" int cdm_alns_ry_download(cdm_ctx *ctx, const cdm_alns *a, uint16_t *ry) {
+    if (!ctx || !a || !ry) { cdm_set_error("cdm_alns_ry_download: NULL argument"); return CDM_ERR_INVALID; }
+    if (!a->ryMism) { cdm_set_error("cdm_alns_ry_download: the set carries no purine/pyrimidine counts"); return CDM_ERR_INVALID; }
+    CDM_HIP(hipSetDevice(ctx->device));
+    if (a->count) CDM_HIP(hipMemcpyAsync(ry, a->ryMism, a->count * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    CDM_HIP(hipStreamSynchronize(ctx->stream));
+    return CDM_OK;
+}
 extern "C" void cdm_alns_free(cdm_alns *a) { if (!a) return; cdmFree(a->off); cdmFree(a->rec); if (a->ryMism) cdmFree(a->ryMism); delete a; }
 
 // ------------------------------------------------------------------------------------------------ stage wrappers

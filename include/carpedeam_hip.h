@@ -275,6 +275,13 @@ typedef struct cdm_aln {
 } cdm_aln;
 
 int cdm_rescore(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_hits *hits, const cdm_rescore_params *par, cdm_alns **out);
+/* What cdm_rescore keeps beside the records, and the size of its kernel's tile (for tests that place inputs on tile boundaries):
+ * hits per block of the scoring kernel; the number of identity records written with the coordinates -1 (a sequence that scores 0
+ * against itself); the purine/pyrimidine mismatch count of every record, cdm_alns_count values (0xFFFF = not counted; fails with
+ * CDM_ERR_INVALID for a set that has none, i.e. one made by cdm_alns_upload). */
+uint32_t cdm_rescore_tile(void);
+uint64_t cdm_alns_undefined(const cdm_alns *a);
+int cdm_alns_ry_download(cdm_ctx *ctx, const cdm_alns *a, uint16_t *ry);
 /* rescorediagonal --rescore-mode 0 --wrapped-scoring 1 (query DB == target DB): linclust's Hamming-distance pre-clustering of the
  * assembled contigs (lib/mmseqs/data/workflow/linclust.sh:27-31; rescorediagonal.cpp:145-356 in that mode,
  * DistanceCalculator::computeUngappedWrappedAlignment, DistanceCalculator.h:57-91).  Output: the hits that pass, as prefilter
