@@ -180,7 +180,7 @@ EXPORTS = [
     "cdm_seqdb_download", "cdm_seqdb_download_stream", "cdm_seqdb_free", "cdm_seqdb_select_ext", "cdm_seqdb_select_assembled", "cdm_seqdb_index_copy", "cdm_seqdb_words", "cdm_seqdb_copy_packed", "cdm_seqdb_from_packed", "cdm_damage_load", "cdm_damage_get", "cdm_kmermatch", "cdm_hits_upload", "cdm_hits_count",
     "cdm_hits_download", "cdm_hits_free", "cdm_rescore", "cdm_rescore_tile", "cdm_alns_undefined", "cdm_alns_ry_download", "cdm_alns_upload", "cdm_alns_count", "cdm_alns_download", "cdm_alns_free",
     "cdm_evalue", "cdm_bit_score", "cdm_gapped_evalue", "cdm_correct", "cdm_extend",
-    "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kpart_free", "cdm_dev_copy",
+    "cdm_kmermatch_part", "cdm_kmermatch_split_begin", "cdm_kpart_outgoing", "cdm_kmermatch_split_finish", "cdm_kpart_info", "cdm_kpart_stale", "cdm_kpart_gather", "cdm_kpart_sort", "cdm_kpart_vote", "cdm_kpart_cont_cap", "cdm_kmer_slot_split", "cdm_kpart_free", "cdm_dev_copy",
     "cdm_seqdb_from_packed_ext", "cdm_seqdb_copy_ext", "cdm_seqdb_export_packed", "cdm_seqdb_import_packed", "cdm_contig_merge", "cdm_cyclecheck", "cdm_seqdb_has_raw", "cdm_seqdb_copy_raw", "cdm_seqdb_attach_raw",
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
@@ -302,6 +302,7 @@ def lib():
         l.cdm_kpart_free.argtypes = [vp]
         l.cdm_kpart_free.restype = None
         l.cdm_dev_copy.argtypes = [vp, vp, vp, C.c_uint64]
+        l.cdm_kmer_slot_split.argtypes = [C.c_int, C.POINTER(C.c_int)]
         l.cdm_seqdb_from_packed_ext.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]
         l.cdm_seqdb_copy_ext.argtypes = [vp, vp, vp]
         l.cdm_pileup_profile.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(PileupParams), vp, vp, vp]
@@ -374,6 +375,13 @@ def _gapped_args(gapped):
 def pileup_chunk_records():
     """records per work item of cdm_pileup_profile's kernel as the next call cuts them (CDM_PILEUP_CHUNK; tests)"""
     return int(lib().cdm_pileup_chunk_records())
+
+
+def kmer_slot_split(k):
+    """k-mer bits that sort 1 on the slot layout leaves to the grouping kernel at this k (cdm_kmer_slot_split; reads CDM_SLOT_LOWBITS)"""
+    n = C.c_int(-1)
+    _check(lib().cdm_kmer_slot_split(int(k), C.byref(n)))
+    return n.value
 
 
 def pool_stats():

@@ -158,12 +158,19 @@ __device__ __forceinline__ void sortGroupRegs(int gm, int lane, const MakeComp &
     bitonicRegs<R, W>(v, lane);
     done(v);
 }
-template <typename W, typename MakeComp, typename Done>
+// MAXR: the largest network the caller can reach (gm <= 64 MAXR); the ones beyond it are not instantiated - a kernel's register
+// allocation is the maximum over its branches, taken or not
+template <typename W, int MAXR = 8, typename MakeComp, typename Done>
 __device__ __forceinline__ void sortGroup(int gm, int lane, const MakeComp &mk, const Done &done) {
-    if (gm <= 64) sortGroupRegs<1, W>(gm, lane, mk, done);
-    else if (gm <= 128) sortGroupRegs<2, W>(gm, lane, mk, done);
-    else if (gm <= 256) sortGroupRegs<4, W>(gm, lane, mk, done);
-    else sortGroupRegs<8, W>(gm, lane, mk, done);
+    static_assert(MAXR == 1 || MAXR == 2 || MAXR == 4 || MAXR == 8, "networks of 64, 128, 256 and 512 words");
+    if (MAXR == 1 || gm <= 64) sortGroupRegs<1, W>(gm, lane, mk, done);
+    else if constexpr (MAXR >= 2) {
+        if (MAXR == 2 || gm <= 128) sortGroupRegs<2, W>(gm, lane, mk, done);
+        else if constexpr (MAXR >= 4) {
+            if (MAXR == 4 || gm <= 256) sortGroupRegs<4, W>(gm, lane, mk, done);
+            else if constexpr (MAXR >= 8) sortGroupRegs<8, W>(gm, lane, mk, done);
+        }
+    }
 }
 // value of lane - 1 (wave_shr:1), lane 0 keeps its own
 __device__ __forceinline__ uint64_t prevLane64(uint64_t a) {
@@ -180,7 +187,9 @@ __device__ __forceinline__ uint64_t readLane64(uint64_t a, int l) {
 // their keys agree in the bits of hiMask.  groupFn(g0, gm) finishes the group of whole buckets in the window slots
 // [g0, g0 + gm).  w.ord[i] = ordinal of slot i's bucket in the window.
 // WIN / FIRST: slots of the window / of its first batch (the defaults are WV_WIN / WV_FIRST).
-template <typename T, int WIN = WV_WIN, int FIRST = WV_FIRST, typename Fetch, typename Put, typename KeyAt, typename GroupFn>
+// Two capacities: maxBucket (run time) is the largest single bucket the wave finishes - a longer one goes to the list -, GROUP (compile
+// time) bounds a group of SEVERAL buckets, which never exceeds maxBucket either.  groupFn sees gm <= maxBucket.
+template <typename T, int WIN = WV_WIN, int FIRST = WV_FIRST, int GROUP = BK_GROUP, typename Fetch, typename Put, typename KeyAt, typename GroupFn>
 __device__ __forceinline__ void waveBuckets(uint64_t r0, uint64_t n, int own, uint32_t maxBucket, uint64_t hiMask, const BigList &big, WaveLdsT<WIN> &w, int lane,
                                             const Fetch &fetch, const Put &put, const KeyAt &keyAt, const GroupFn &groupFn) {
     constexpr int WV_WIN = WIN, WV_FIRST = FIRST, WV_WORDS = WIN / 64;      // (shadow the defaults)
@@ -219,7 +228,7 @@ __device__ __forceinline__ void waveBuckets(uint64_t r0, uint64_t n, int own, ui
     const int p0 = firstSetFrom(w, 0, ownEnd);
     int loaded = min(avail, WV_FIRST);
     int eLast = firstSetFrom(w, sLast + 1, loaded);
-    if (eLast < 0 && loaded < avail) {
+    if constexpr (WV_FIRST < WV_WIN) if (eLast < 0 && loaded < avail) {      // (FIRST == WIN: the whole window came with the first batch)
         loadRows(std::integral_constant<int, WV_WORDS - WV_FIRST / 64>(), WV_FIRST / 64, std::false_type());
         waveLdsSync();
         loaded = avail;
@@ -236,7 +245,7 @@ __device__ __forceinline__ void waveBuckets(uint64_t r0, uint64_t n, int own, ui
     }
     int g0 = p0;
     while (g0 < eOwn) {
-        const int lim = min(g0 + min(BK_GROUP, (int) maxBucket), eOwn);       // (a group of several buckets never exceeds the capacity either)
+        const int lim = min(g0 + min(GROUP, (int) maxBucket), eOwn);       // (a group of several buckets never exceeds the bucket capacity either)
         int e = (lim == eOwn) ? eOwn : lastSetIn(w, g0, lim);
         if (e < 0) { e = firstSetFrom(w, g0 + 1, eOwn); if (e < 0) e = eOwn; }     // one bucket larger than a group
         const int gm = e - g0;

@@ -239,23 +239,33 @@ struct BucketGroupArgs : GroupParams {
 #endif
 // With slot tuples (8 bytes per window slot, no value array) twice the owned range costs the LDS the (key, value) window did: 256 owned
 // slots in a window of 512 take the kernel from 59 to 53 ms at 50 M reads (384 / 640, 512 / 768 and a 768-slot window for buckets of
-// up to 512 all lose: 64-66 ms; profiles/r05_probe_grouping_geometry.txt).
+// up to 512 all lose: 64-66 ms; profiles/r05_probe_grouping_geometry.txt).  Round 9 (profiles/slot_split_geometry.txt): with 27 k-mer
+// bits sorted globally a bucket spans half the k-mers, but a window for buckets of up to 128 (256 / 384 / 320, 8 blocks per CU) sends 88 M
+// tuples of the bench's 4.05 G to the caller's list where this one sends 10 thousand - buckets are sums of whole k-mer runs, their tail
+// does not halve - and groups of up to 128 cost more than they save (50.7 against 45.4 ms): geometry and group capacity stay.
 #ifndef CDM_GKS_OWN
 #define CDM_GKS_OWN 256
 #define CDM_GKS_WIN 512
 #define CDM_GKS_FIRST 384
 #endif
+#ifndef CDM_GKS_GROUP
+#define CDM_GKS_GROUP 256     // largest group of several buckets of the slot instance (a single bucket: up to WIN - OWN)
+#endif
 template <typename LY> struct GkGeom {
     static constexpr int OWN = LY::bySlot ? CDM_GKS_OWN : CDM_GK_OWN, WIN = LY::bySlot ? CDM_GKS_WIN : CDM_GK_WIN, FIRST = LY::bySlot ? CDM_GKS_FIRST : CDM_GK_FIRST, MAXB = WIN - OWN;
-    // (the network writes all 64 R slots of ss, R = 1, 2, 4, 8: the largest bucket is one of those sizes)
-    static_assert(WIN % 64 == 0 && FIRST % 64 == 0 && FIRST < WIN && OWN <= FIRST && WIN <= (1 << bucket::WV_IDX) && (MAXB == 64 || MAXB == 128 || MAXB == 256 || MAXB == 512), "grouping kernel geometry");
+    // GROUP: the capacity of a group of several buckets (bucket::waveBuckets; at most a bucket's); CAP: the most elements one network
+    // sorts = the words of sSAll (the network writes all 64 R slots of it, R = CAP / 64 at the most).  The slot instance is built with
+    // that largest R; the (key, value) layouts' instances are left as they were, all four networks (their R = 8 is as unreachable).
+    static constexpr int GROUP = LY::bySlot ? CDM_GKS_GROUP : bucket::BK_GROUP, CAP = MAXB, MAXR = LY::bySlot ? CAP / 64 : 8;
+    static_assert(WIN % 64 == 0 && FIRST % 64 == 0 && FIRST <= WIN && OWN <= FIRST && WIN <= (1 << bucket::WV_IDX) && (MAXB == 64 || MAXB == 128 || MAXB == 256 || MAXB == 512), "grouping kernel geometry");
+    static_assert(GROUP >= 64 && GROUP <= MAXB && GROUP <= (1 << bucket::BK_ORD), "grouping kernel group capacity");
 };
 #ifndef CDM_GK_MINW
 #define CDM_GK_MINW 0      // waves per SIMD the register allocation of the grouping kernel leaves room for (scripts/build_variant.py sweeps it; 0: 6 with slot tuples - the 6 blocks of 4 waves per CU its LDS lets run -, no request with (key, value) pairs in the window)
 #endif
 // LDS the kernel declares per block (a block of BK_NT threads is one wave per SIMD: blocks per CU = waves per SIMD)
 template <typename LY> constexpr size_t gkLdsBytes() {
-    return (size_t) bucket::BK_WAVES * ((size_t) GkGeom<LY>::WIN * 8 + (LY::bySlot ? 1 : (size_t) GkGeom<LY>::WIN) * sizeof(typename LY::V) + (size_t) GkGeom<LY>::MAXB * 4 + sizeof(bucket::WaveLdsT<GkGeom<LY>::WIN>) +
+    return (size_t) bucket::BK_WAVES * ((size_t) GkGeom<LY>::WIN * 8 + (LY::bySlot ? 1 : (size_t) GkGeom<LY>::WIN) * sizeof(typename LY::V) + (size_t) GkGeom<LY>::CAP * 4 + sizeof(bucket::WaveLdsT<GkGeom<LY>::WIN>) +
                                       (LY::bySlot ? (size_t) REC_CAP : 1) * 12);
 }
 // A request the LDS cannot meet is not approximated by the compiler but dropped ("failed to meet occupancy target"): the slot instance
@@ -269,10 +279,11 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
     static_assert(bucket::BK_NT == 256 && (size_t) gkMinWaves<LY>() * gkLdsBytes<LY>() <= CU_LDS_BYTES, "the launch bound asks for more blocks per CU than the kernel's LDS lets run: the compiler would drop the request");
     using namespace bucket;
     typedef typename LY::V V;
-    constexpr int GK_WIN = GkGeom<LY>::WIN, GK_FIRST = GkGeom<LY>::FIRST, GK_MAXB = GkGeom<LY>::MAXB;
+    constexpr int GK_WIN = GkGeom<LY>::WIN, GK_FIRST = GkGeom<LY>::FIRST, GK_CAP = GkGeom<LY>::CAP;
     __shared__ uint64_t sKeyAll[BK_WAVES][GK_WIN];
     __shared__ V sValAll[BK_WAVES][LY::bySlot ? 1 : GK_WIN];       // (slot tuples: no value array)
-    __shared__ uint32_t sSAll[BK_WAVES][GK_MAXB];
+    __shared__ uint32_t sSAll[BK_WAVES][GK_CAP];
+    static_assert(GK_CAP >= 64 * GkGeom<LY>::MAXR || !LY::bySlot, "the largest network of the instance writes 64 R words of sSAll");
     __shared__ WaveLdsT<GK_WIN> wAll[BK_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r0 = ((uint64_t) blockIdx.x * BK_WAVES + wave) * (uint64_t) a.own;
@@ -299,7 +310,7 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
     const uint64_t blockBase = (uint64_t) blockIdx.x * BK_WAVES * (uint64_t) a.own;
     if constexpr (LY::bySlot) bh = a.blockHead[blockIdx.x];
     auto digitAt = [&](uint64_t g) -> uint32_t { const long long off = (long long) (g - blockBase); return (off >= (long long) bh.lo && off < (long long) bh.hi) ? bh.td : headDigit(a.geom, g); };
-    waveBuckets<Tup, GK_WIN, GK_FIRST>(r0, a.n, a.own, a.maxBucket, hmask & ~lowMask, a.big, w, lane,
+    waveBuckets<Tup, GK_WIN, GK_FIRST, GkGeom<LY>::GROUP>(r0, a.n, a.own, a.maxBucket, hmask & ~lowMask, a.big, w, lane,
         [&](uint64_t g) {
             Tup t;
             if constexpr (LY::bySlot) { t.k = a.keys[g]; t.v = digitAt(g); }       // (raw: the window holds far more tuples than the wave owns)
@@ -318,8 +329,8 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
         [&](int g0, int gm) {
 
             // word of the network: (bucket ordinal within the group, low k-mer bits, position within the group)
-            const int idxBits = gm > 256 ? 9 : 8, ord0 = w.ord[g0];
-            sortGroup<W>(gm, lane,
+            const int idxBits = (GK_CAP > 256 && gm > 256) ? 9 : 8, ord0 = w.ord[g0];
+            sortGroup<W, GkGeom<LY>::MAXR>(gm, lane,
                 [&](int i) {
                     const uint64_t low = LY::bySlot ? (uint64_t) ((uint32_t) (sKey[g0 + i] >> rx::SLOT_KEY_SHIFT)) & lowMask : sKey[g0 + i] & lowMask;      // (a slot tuple's k-mer bits sit above its index)
                     return (W) ((((W) (w.ord[g0 + i] - ord0) << lowBits | (W) low) << idxBits) | (W) i);

@@ -35,6 +35,19 @@ inline bool slotLayoutFits(const Db &d) {
     if (!packedLayoutFits(d)) return false;
     return d.n * (uint64_t) slotsPerSeq(d.maxLen, d.k) < (1ull << 32);
 }
+// LayoutSlot's split of sort 1: how many of the 2k k-mer bits the global passes leave to the grouping kernel.  The head pass drops the
+// empty slots, so every globally sorted bit is a k-mer bit: the head digit and two full passes inside its segments sort 27 of them
+// (the 12-byte layouts spend one of their 27 on the unused-slot bit 2k), and a bucket of equal high bits spans half the k-mers.
+inline int slotLowBits(int k) { return std::max(0, 2 * k - 3 * RADIX_BITS); }
+// ... and what CDM_SLOT_LOWBITS=<n> may ask for instead (A/B runs, tests): at most two passes behind the head digit.  The grouping
+// kernel's sort word - 8 bits of bucket ordinal, the n low bits, 9 of position - fits the word chosen for n whatever n that admits:
+// 32 bits up to 15 low bits, and n <= 2k - 9 <= 31 keeps 17 + n below 64.  So no n is refused for the word.
+constexpr int GROUP_WORD32_LOWBITS = 15;     // (kmermatch.hip groupBuckets: every layout's choice of the word)
+static_assert(8 + GROUP_WORD32_LOWBITS + 9 <= 32 && 8 + SLOT_REM_BITS + 9 <= 64, "the grouping kernel's sort word");
+inline bool slotLowBitsServed(int k, int n) {
+    const int rem = 2 * k - RADIX_BITS - n;
+    return n >= 0 && rem >= 0 && rem <= 2 * RADIX_BITS;
+}
 // bits of a group key below the representative: id, diagonal, strand
 inline uint32_t repShiftOf(const Db &d) { return bitsFor(d.n) + bitsFor(2ull * d.maxLen + 2) + 1; }
 // does this DB take the wide group key (the representative not in the members' keys)?

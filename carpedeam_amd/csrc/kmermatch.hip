@@ -38,6 +38,19 @@ static_assert(RADIX_BITS == rx::BITS && SLOT_REM_BITS == rx::SLOT_REM, "kmer_pla
 // the numbers kmer_plan.h looks at (device: with the device's memory, for the plans that ask whether the tuples fit)
 inline uint64_t deviceBytes() { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) return tot; (void) hipGetLastError(); return 0; }
 inline Db planDb(const cdm_seqdb *db, int k, bool device = false) { Db d; d.n = db->n; d.maxLen = db->maxLen; d.residues = db->residues; d.k = k; if (device) d.deviceBytes = deviceBytes(); return d; }
+// the slot layout's split of sort 1 at this k: kmer_plan.h's, or what CDM_SLOT_LOWBITS=<n> asks for (A/B: 2k + 1 - 27 is the split of
+// the rounds before 9) - refused where the passes or the grouping kernel's sort word do not serve it
+inline int slotSplit(int k, int &lowBits) {
+    lowBits = slotLowBits(k);
+    if (const char *e = cdmGetenv("CDM_SLOT_LOWBITS")) {
+        char *end = nullptr; const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 0 || v > 64 || !slotLowBitsServed(k, (int) v)) {
+            cdm_set_error("cdm_kmermatch: CDM_SLOT_LOWBITS=%s: k = %d takes 0 <= 2k - %d - n <= %d global bits behind the head digit", e, k, RADIX_BITS, 2 * RADIX_BITS); return CDM_ERR_INVALID;
+        }
+        lowBits = (int) v;
+    }
+    return CDM_OK;
+}
 
 // One kmermatcher run, in phases so that a multi-GPU run can exchange between them (shard.py / cdm_kmermatch_part):
 //   phaseA     extraction (of this rank's k-mer range), sort 1, grouping -> group keys in k-mer order (startIo), live, nKept
@@ -361,7 +374,9 @@ int sortAndGroup() {
     // With low bits left over the passes cover bits [lowBits, 2k]: bit 2k is set only in unused slots, which end up last.
     // 27 high bits = 3 onesweep passes of 9 bits (library radix sorts default to 8 bits per pass; 9 still fits the LDS and three
     // 9-bit passes take 29 ms per 2^30 tuples where four 8-bit ones take 35).
+    // The slot layout's head pass drops the unused slots: its 27 bits are all k-mer bits (slotLowBits, kmer_plan.h; CDM_SLOT_LOWBITS).
     lowBits = lsdOnly ? 0 : std::max(0, 2 * k + 1 - 27);
+    if constexpr (LY::bySlot) if (int rc = slotSplit(k, lowBits)) return rc;
     hipEventRecord(ctx->ev0, s);
     if (int rc = sortRegionOne()) return rc;
     hipEventRecord(ctx->ev1, s);
@@ -489,7 +504,7 @@ int groupBuckets() {
     if (kmerSlots) hipMemsetAsync(startIo + live, 0xFF, (size_t) (kmerSlots - live) * 8, s);     // unused slots: no group key
     DevBuf<BlockHead> heads;        // (freed behind the synchronise below)
     // 8 bits of bucket ordinal + low bits + 9 of position in one word
-    if (!(lowBits <= 15 ? launchFused<uint32_t>(own, maxBucket, bigList, bigCnt, heads) : launchFused<uint64_t>(own, maxBucket, bigList, bigCnt, heads))) return CDM_ERR_HIP;
+    if (!(lowBits <= GROUP_WORD32_LOWBITS ? launchFused<uint32_t>(own, maxBucket, bigList, bigCnt, heads) : launchFused<uint64_t>(own, maxBucket, bigList, bigCnt, heads))) return CDM_ERR_HIP;
     unsigned int nBig = 0; unsigned long long recOver = 0;
     hipMemcpyAsync(&nBig, bigCnt.p, 4, hipMemcpyDeviceToHost, s);
     if (stagedWaves) hipMemcpyAsync(&recOver, recFlag.p, 8, hipMemcpyDeviceToHost, s);
@@ -1259,6 +1274,12 @@ extern "C" int cdm_kpart_vote(cdm_ctx *ctx, cdm_kpart *h, const uint32_t *cont, 
     return h->job->voteWith(cont, stale, out);
 }
 extern "C" int cdm_kpart_cont_cap(void) { return CONT_CAP; }
+extern "C" int cdm_kmer_slot_split(int k, int *low_bits) {
+    if (!low_bits) { cdm_set_error("cdm_kmer_slot_split: invalid argument"); return CDM_ERR_INVALID; }
+    Db d; d.n = 1; d.maxLen = 64; d.residues = 64; d.k = k;      // (a DB of one length that the layout serves at this k, if any k-mer size does)
+    if (!slotLayoutFits(d)) { cdm_set_error("cdm_kmer_slot_split: the slot layout takes 14 <= k <= 20 (got %d)", k); return CDM_ERR_INVALID; }
+    return slotSplit(k, *low_bits);
+}
 extern "C" int cdm_dev_copy(cdm_ctx *ctx, void *dst, const void *src, uint64_t bytes) {
     CDM_HIP(hipSetDevice(ctx->device));
     if (bytes) CDM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));

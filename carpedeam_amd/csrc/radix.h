@@ -33,6 +33,16 @@ static_assert(NT >= BINS && TILE <= 65536, "radix pass geometry");
 #endif
 constexpr int LB = CDM_RX_LB;
 constexpr unsigned long long ST_AGG = 1ull << 62, ST_PREFIX = 2ull << 62, ST_MASK = (1ull << 62) - 1ull;
+// The status word of k_rx_pass as a type: two flag bits on top (0 nothing yet, 1 the tile's count, 2 its inclusive prefix) and the count
+// below them.  A tile's count needs 14 bits and a chain's prefix stays below the chain's total, so where that total is below 2^30 the
+// 32-bit word serves: half the bytes published, fetched and zeroed per tile (512 words, written twice).  Same protocol, same relaxed
+// agent-scope atomics.  CDM_RX_STATUS=u64 keeps the 64-bit word everywhere (A/B, tests).
+template <typename S> struct StatusWord {
+    static constexpr int FLAG_SHIFT = (int) sizeof(S) * 8 - 2;
+    static constexpr S AGG = (S) 1 << FLAG_SHIFT, PREFIX = (S) 2 << FLAG_SHIFT, MASK = ((S) 1 << FLAG_SHIFT) - (S) 1;
+};
+constexpr uint64_t STATUS32_LIMIT = 1ull << 30;        // a chain whose total is below this may use the 32-bit word
+inline bool status32Allowed() { const char *e = cdmGetenv("CDM_RX_STATUS"); return !(e && !strcmp(e, "u64")); }
 
 // the two buffers a sort alternates between: where the data is now, and the other one
 template <typename T> struct DoubleBuf {
@@ -98,13 +108,14 @@ struct PassArgs {
     const K *kin; K *kout; const V *vin; V *vout; uint64_t n;
     int shift, bits;
     const unsigned long long *digitBase;        // [BINS] ([BINS][BINS] in PASS_SEG)
-    unsigned long long *status;                 // [tiles][BINS], zeroed
+    void *status;                               // [tiles][BINS] status words of the kernel's S, zeroed
     unsigned int *ticket;                       // zeroed
     const unsigned long long *seg = nullptr; const unsigned int *segTile = nullptr;     // PASS_SEG: [BINS + 1] each
     uint32_t keepLo = 0, keepHi = 0xFFFFFFFFu;  // PASS_HEAD: keys whose digit lies outside [keepLo, keepHi) are dropped like empty slots (a rank's range of the k-mer space)
 };
-template <typename K, typename V, int MODE = PASS_PLAIN>
+template <typename K, typename V, int MODE = PASS_PLAIN, typename S = unsigned long long>
 __global__ __launch_bounds__(NT) void k_rx_pass(PassArgs<K, V> a) {
+    typedef StatusWord<S> SW;
     static_assert(MODE == PASS_PLAIN || (sizeof(K) == 8 && !HasValue<V>::value), "the head and segment passes sort 64-bit keys only");
     static_assert(MODE != PASS_HEAD || TILE <= 8192, "the head pass keeps a key's index in its tile in 13 bits of the exchange word");
     // one 64 KB exchange buffer, used for the keys and then for the values: two blocks per CU
@@ -169,10 +180,10 @@ __global__ __launch_bounds__(NT) void k_rx_pass(PassArgs<K, V> a) {
     }
     uint32_t tot;
     const uint32_t ex = cdm_block_excl_sum<uint32_t>(run, tot);
-    unsigned long long *st = a.status + tile * BINS + tid;
+    S *st = static_cast<S *>(a.status) + tile * BINS + tid;
     if (isDigit) {
         sTileOff[tid] = (uint16_t) ex;
-        __hip_atomic_store(st, (chain == 0 ? ST_PREFIX : ST_AGG) | (unsigned long long) run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(st, (S) ((chain == 0 ? SW::PREFIX : SW::AGG) | (S) run), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     K *sK = reinterpret_cast<K *>(sBuf);
@@ -194,24 +205,24 @@ __global__ __launch_bounds__(NT) void k_rx_pass(PassArgs<K, V> a) {
     if (isDigit) {
         unsigned long long exclG = 0;
         if (chain != 0) {
-            const unsigned long long *q = st - BINS;
+            const S *q = st - BINS;
             uint64_t left = chain;
             bool done = false;
             while (!done) {
-                unsigned long long v[LB];
+                S v[LB];
 #pragma unroll
-                for (int u = 0; u < LB; u++) v[u] = (uint64_t) u < left ? __hip_atomic_load(q - (size_t) u * BINS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ST_PREFIX;
+                for (int u = 0; u < LB; u++) v[u] = (uint64_t) u < left ? __hip_atomic_load(q - (size_t) u * BINS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : SW::PREFIX;
 #pragma unroll
                 for (int u = 0; u < LB; u++) {
                     if (done) break;
-                    unsigned long long x = v[u];
-                    while ((x >> 62) == 0ull) x = __hip_atomic_load(q - (size_t) u * BINS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    exclG += x & ST_MASK;
-                    if ((x >> 62) == 2ull) done = true;
+                    S x = v[u];
+                    while ((x >> SW::FLAG_SHIFT) == (S) 0) x = __hip_atomic_load(q - (size_t) u * BINS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    exclG += (unsigned long long) (x & SW::MASK);
+                    if ((x >> SW::FLAG_SHIFT) == (S) 2) done = true;
                 }
                 q -= LB * (size_t) BINS; left = left > LB ? left - LB : 0;
             }
-            __hip_atomic_store(st, ST_PREFIX | (exclG + run), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(st, (S) (SW::PREFIX | (S) (exclG + run)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         sGlobal[tid] = digitBase[tid] + exclG - ex;         // output position of the pair at exchange slot p with this digit: sGlobal + p
     }
@@ -245,6 +256,14 @@ __global__ __launch_bounds__(NT) void k_rx_pass(PassArgs<K, V> a) {
             if (p < items) a.vout[sGlobal[dig[r]] + (unsigned long long) p] = sV[p];
         }
     }
+}
+
+// one pass with the status word the chains' totals allow (the caller zeroes tiles x BINS words of that width first: statusBytes)
+inline size_t statusBytes(uint64_t tiles, bool s32) { return (size_t) tiles * BINS * (s32 ? 4 : 8); }
+template <typename K, typename V, int MODE>
+inline void launchPass(hipStream_t s, unsigned tiles, bool s32, const PassArgs<K, V> &pa) {
+    if (s32) hipLaunchKernelGGL((k_rx_pass<K, V, MODE, uint32_t>), dim3(tiles), dim3(NT), 0, s, pa);
+    else hipLaunchKernelGGL((k_rx_pass<K, V, MODE, unsigned long long>), dim3(tiles), dim3(NT), 0, s, pa);
 }
 
 // ---- stable compaction: the pairs whose key is not ~0 (empty slot), in order, to the front of (kout, vout); *total = how many.
@@ -345,14 +364,15 @@ inline int sortPairs(hipStream_t s, int cuCount, K *k0, K *k1, V *v0, V *v1, uin
     hipLaunchKernelGGL(k_rx_offsets<0>, dim3(1), dim3(BINS), 0, s, hist.p, passes);
     hipEvent_t ev[2 * MAXPASS];
     if (passMs) for (int i = 0; i < 2 * passes; i++) hipEventCreate(&ev[i]);
+    const bool s32 = n < STATUS32_LIMIT && status32Allowed();       // (one chain over all tiles: a digit's prefix is below n)
     for (int p = 0; p < passes; p++) {
-        hipMemsetAsync(status.p, 0, tiles * BINS * 8, s);
+        hipMemsetAsync(status.p, 0, statusBytes(tiles, s32), s);
         PassArgs<K, V> pa;
         pa.kin = inFirst ? k0 : k1; pa.kout = inFirst ? k1 : k0; pa.vin = inFirst ? v0 : v1; pa.vout = inFirst ? v1 : v0; pa.n = n;
         pa.shift = beginBit + p * BITS; pa.bits = std::min(BITS, endBit - pa.shift);
         pa.digitBase = hist.p + (size_t) p * BINS; pa.status = status.p; pa.ticket = ticket.p + p;
         if (passMs) hipEventRecord(ev[2 * p], s);
-        hipLaunchKernelGGL((k_rx_pass<K, V>), dim3((unsigned) tiles), dim3(NT), 0, s, pa);
+        launchPass<K, V, PASS_PLAIN>(s, (unsigned) tiles, s32, pa);
         if (passMs) hipEventRecord(ev[2 * p + 1], s);
         inFirst = !inFirst;
     }
@@ -410,10 +430,17 @@ __global__ __launch_bounds__(NT) void k_rx_hist_head(const uint64_t *__restrict_
     __syncthreads();
     for (int i = threadIdx.x; i < BINS; i += NT) { const unsigned int c = sHist[i]; if (c) atomicAdd(&hist[i], (unsigned long long) c); }
 }
-// hist[BINS] -> seg[d] = first tuple of segment d (seg[BINS] = all of them), segTile[d] = its first tile (segTile[BINS] = all tiles)
+// hist[BINS] -> seg[d] = first tuple of segment d (seg[BINS] = all of them), segTile[d] = its first tile (segTile[BINS] = all tiles,
+// segTile[BINS + 1] = the largest segment's tuples, clipped to 32 bits)
 template <int UNUSED = 0>
 __global__ __launch_bounds__(BINS) void k_rx_seg_layout(const unsigned long long *__restrict__ hist, unsigned long long *__restrict__ seg, unsigned int *__restrict__ segTile) {
+    __shared__ unsigned int sMax;
+    if (threadIdx.x == 0) sMax = 0u;
+    __syncthreads();
     const unsigned long long c = hist[threadIdx.x];
+    atomicMax(&sMax, (unsigned int) min(c, 0xFFFFFFFFull));       // the largest segment (clipped), segTile[BINS + 1]: the host picks the status word by it
+    __syncthreads();
+    if (threadIdx.x == 0) segTile[BINS + 1] = sMax;
     unsigned long long tot; unsigned int tt;
     const unsigned long long ex = cdm_block_excl_sum<unsigned long long>(c, tot);
     const unsigned int tiles = (unsigned int) ((c + TILE - 1) / TILE);
@@ -484,7 +511,7 @@ inline int sortSlotKeys(hipStream_t s, int cuCount, uint64_t *k0, uint64_t *k1, 
     if (segPasses > 2) { cdm_set_error("slot key sort: %d global key bits behind the head digit (two passes take %d)", rem, 2 * BITS); return CDM_ERR_INVALID; }
     const uint64_t tilesHead = (n + TILE - 1) / TILE;
     DevBuf<unsigned long long> hist, segHist, segTables, status; DevBuf<unsigned int> ticket, segTile;
-    if (!hist.alloc(BINS) || !ticket.alloc(4) || !segTile.alloc(BINS + 1)) { cdm_set_error("slot key sort: out of device memory"); return CDM_ERR_HIP; }
+    if (!hist.alloc(BINS) || !ticket.alloc(4) || !segTile.alloc(BINS + 2)) { cdm_set_error("slot key sort: out of device memory"); return CDM_ERR_HIP; }
     hipMemsetAsync(ticket.p, 0, 16, s);
     if (headHist) {
         hipMemcpyAsync(hist.p, headHist, BINS * 8, hipMemcpyDeviceToDevice, s);
@@ -505,9 +532,12 @@ inline int sortSlotKeys(hipStream_t s, int cuCount, uint64_t *k0, uint64_t *k1, 
     if (keepLo > 0) hipMemsetAsync(hist.p, 0, (size_t) std::min<uint32_t>(keepLo, BINS) * 8, s);
     if (keepHi < (uint32_t) BINS) hipMemsetAsync(hist.p + keepHi, 0, (size_t) (BINS - keepHi) * 8, s);
     hipLaunchKernelGGL(k_rx_seg_layout<0>, dim3(1), dim3(BINS), 0, s, (const unsigned long long *) hist.p, segDev, segTile.p);
-    unsigned int tilesSeg = 0;
-    hipMemcpyAsync(&live, segDev + BINS, 8, hipMemcpyDeviceToHost, s); hipMemcpyAsync(&tilesSeg, segTile.p + BINS, 4, hipMemcpyDeviceToHost, s);
+    unsigned int tilesAndMax[2] = {0u, 0xFFFFFFFFu};
+    hipMemcpyAsync(&live, segDev + BINS, 8, hipMemcpyDeviceToHost, s); hipMemcpyAsync(tilesAndMax, segTile.p + BINS, 8, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) { cdm_set_error("slot key sort (head histogram) failed: %s", hipGetErrorString(hipGetLastError())); return CDM_ERR_HIP; }
+    const unsigned int tilesSeg = tilesAndMax[0];
+    // all three passes chain inside a head digit: the head pass's prefix of a digit and a segment pass's prefix are below that segment's tuples
+    const bool s32 = (uint64_t) tilesAndMax[1] < STATUS32_LIMIT && status32Allowed();
     if (live > n) { cdm_set_error("slot key sort: internal error: %llu keys counted in %llu slots", live, (unsigned long long) n); return CDM_ERR_HIP; }
     if (live == 0) return CDM_OK;
     if (!status.alloc(std::max<uint64_t>(tilesHead, tilesSeg) * BINS)) { cdm_set_error("slot key sort: out of device memory"); return CDM_ERR_HIP; }
@@ -515,12 +545,12 @@ inline int sortSlotKeys(hipStream_t s, int cuCount, uint64_t *k0, uint64_t *k1, 
     if (passMs) for (int i = 0; i < 2 * (1 + segPasses); i++) hipEventCreate(&ev[i]);
     // ---- the head pass
     {
-        hipMemsetAsync(status.p, 0, tilesHead * BINS * 8, s);
+        hipMemsetAsync(status.p, 0, statusBytes(tilesHead, s32), s);
         PassArgs<uint64_t, NoValue> pa;
         pa.kin = k0; pa.kout = k1; pa.vin = nullptr; pa.vout = nullptr; pa.n = n; pa.shift = shift; pa.bits = headBits; pa.digitBase = segDev; pa.status = status.p; pa.ticket = ticket.p;
         pa.keepLo = keepLo; pa.keepHi = keepHi;
         if (passMs) hipEventRecord(ev[0], s);
-        hipLaunchKernelGGL((k_rx_pass<uint64_t, NoValue, PASS_HEAD>), dim3((unsigned) tilesHead), dim3(NT), 0, s, pa);
+        launchPass<uint64_t, NoValue, PASS_HEAD>(s, (unsigned) tilesHead, s32, pa);
         if (passMs) hipEventRecord(ev[1], s);
     }
     // ---- the passes inside the segments
@@ -533,13 +563,13 @@ inline int sortSlotKeys(hipStream_t s, int cuCount, uint64_t *k0, uint64_t *k1, 
         hipLaunchKernelGGL(k_rx_seg_tables<0>, dim3(BINS * segPasses), dim3(BINS), 0, s, (const unsigned long long *) segHist.p, segPasses, segTables.p);
         uint64_t *in = k1, *out = k0;
         for (int p = 0; p < segPasses; p++) {
-            hipMemsetAsync(status.p, 0, (size_t) tilesSeg * BINS * 8, s);
+            hipMemsetAsync(status.p, 0, statusBytes(tilesSeg, s32), s);
             PassArgs<uint64_t, NoValue> pa;
             pa.kin = in; pa.kout = out; pa.vin = nullptr; pa.vout = nullptr; pa.n = live;
             pa.shift = SLOT_KEY_SHIFT + lowBits + p * BITS; pa.bits = std::min(BITS, SLOT_KEY_SHIFT + shift - pa.shift);
             pa.digitBase = segTables.p + (size_t) p * BINS * BINS; pa.status = status.p; pa.ticket = ticket.p + 1 + p; pa.seg = segDev; pa.segTile = segTile.p;
             if (passMs) hipEventRecord(ev[2 + 2 * p], s);
-            hipLaunchKernelGGL((k_rx_pass<uint64_t, NoValue, PASS_SEG>), dim3(tilesSeg), dim3(NT), 0, s, pa);
+            launchPass<uint64_t, NoValue, PASS_SEG>(s, tilesSeg, s32, pa);
             if (passMs) hipEventRecord(ev[3 + 2 * p], s);
             std::swap(in, out);
         }

@@ -234,6 +234,10 @@ int cdm_kpart_gather_at(cdm_ctx *ctx, cdm_kpart *h, int nb, const uint64_t *boun
 int cdm_kpart_sort(cdm_ctx *ctx, cdm_kpart *h, const void *dev_keys, uint64_t n_keys, uint32_t *head, uint64_t info[2]);
 int cdm_kpart_vote(cdm_ctx *ctx, cdm_kpart *h, const uint32_t *cont, const uint32_t *stale, cdm_hits **out);
 int cdm_kpart_cont_cap(void);
+/* sort 1 on the 8-byte slot layout (a DB of one read length, 14 <= k <= 20): *low_bits = how many of the 2k k-mer bits the global radix
+ * passes leave to the grouping kernel - max(0, 2k - 27), or what the A/B switch CDM_SLOT_LOWBITS=<n> asks for.  CDM_ERR_INVALID for a k
+ * the layout does not take and for a switch outside 0 <= 2k - 9 - n <= 18.  Needs no device. */
+int cdm_kmer_slot_split(int k, int *low_bits);
 void cdm_kpart_free(cdm_kpart *h);
 /* tuning: head room of the library's device-memory cache for callers whose inputs grow from call to call (the contig iterations of
  * the workflow loop): large blocks are allocated `factor` times the request, so the next, larger request fits a cached block instead of
