@@ -14,6 +14,10 @@
 // goes the tuple way - k_unit_sort's hard list, k_block_sort, the radix sort - into the sorted array, and k_rle_segment turns those
 // segments into entries.  The tuple path itself (k_unit_sort for everything, k_seg_count / k_seg_place) stays: the multi-GPU split
 // votes on it, CDM_KMER_VOTE=tuples selects it, and it is what a run falls back to when the entry buffer overflows.
+//
+// Since round 10 most units are not a block's but a WAVE's: units of a quarter of the range, a table of 256 slots, one wave per unit
+// and five times as many units in flight per CU (k_unit_agg's geometry is its template's; kmermatch.hip AGG_WAVE holds the instances).
+// What such a unit cannot hold goes to the block instances, and from there as above.
 #pragma once
 #include "runsort.h"
 
@@ -50,9 +54,15 @@ struct AggArgs {
     const uint64_t *sorted;         // the tuple path's output (k_rle_segment reads the segments the tuple sorters finished)
     const unsigned long long *list; const unsigned int *count;      // the units of this size class (start, end, first record)
     bucket::BigList hard;
-    unsigned int nextClass = 0;     // (host side: which size class the next launch is for)
+    const uint32_t *recRep = nullptr;   // representative of every record (= segRep of its segment: read with the staged records)
+    // the wave-sized instance only: a unit it cannot finish (too many distinct triples or segments) is appended to the size class that
+    // holds it - the same (start, end, first record) triple - and the block instances, launched after it, take it from there
+    runsort::UnitClassLists next = {{nullptr, nullptr, nullptr}, nullptr, {0, 0, 0}, nullptr};
     int wideWord = 0;               // (host side: the entry sort needs the 128-bit word)
+    int cuCount = 0, waveGeom = -1; // (host side: the wave-sized instance in use, -1: none - CDM_AGG=block)
 };
+// The block instances: table slots, distinct-triple limit, bits of an entry's index / of a segment's ordinal in the sort word (the
+// widest of all instances: what kmermatch.hip's "does the word fit" asks)
 constexpr int AG_H = 1024, AG_D = 512, AG_IDX = 9, AG_ORD = 11;
 // Room in the entry array is taken from the one global cursor in CHUNKS of this many entries, a block (k_unit_agg) or a wave
 // (k_rle_segment) handing them out to its units from there: one atomic per unit on a single word - 1.9 M units and 0.5 M segments in the
@@ -60,63 +70,117 @@ constexpr int AG_H = 1024, AG_D = 512, AG_IDX = 9, AG_ORD = 11;
 // 6.3 ms for 0.52 M segments of 34 tuples on average, whether a block or a wave took a segment).  What a chunk's end leaves unused
 // stays unused: the caller's capacity holds a chunk per block / wave on top (aggChunkSlack).
 constexpr unsigned long long AG_CHUNK = 2048;
-inline unsigned long long aggChunkSlack(unsigned long long units, unsigned long long segments, int cuCount) {
-    const unsigned long long g = (unsigned long long) cuCount * 64;
-    return (3 * std::min(units + 1, g) + std::min(segments + 1, g)) * AG_CHUNK;
+// gridPerClass: blocks of a k_unit_agg launch (every block holds a chunk of its own): 64 per CU for the block form alone, 32 per CU
+// for each of the four launches once the wave-sized instance runs in front - 4 x 32 + 64 = 192 chunks per CU, where the block form alone
+// holds 3 x 64 + 64 = 256
+inline unsigned int aggGridPerCu(bool waveUnits) { return waveUnits ? 32u : 64u; }
+inline unsigned long long aggChunkSlack(unsigned long long units, unsigned long long segments, int cuCount, bool waveUnits) {
+    const unsigned long long g = (unsigned long long) cuCount * 64, gu = (unsigned long long) cuCount * aggGridPerCu(waveUnits);
+    return ((waveUnits ? 4 : 3) * std::min(units + 1, gu) + std::min(segments + 1, g)) * AG_CHUNK;
 }
-static_assert((1 << AG_IDX) >= AG_D && (1 << AG_ORD) > runsort::U_T, "aggregation geometry");
 __device__ __forceinline__ uint32_t aggHash(uint64_t k) { return (uint32_t) ((k * 0x9E3779B97F4A7C15ull) >> 40); }
 
-// ITEMS: tuples a thread fetches before it starts inserting (all loads of a round are in flight together; CAP / NT of the size class)
 #ifndef CDM_AGG_MINW
 #define CDM_AGG_MINW 4
 #endif
-// (waves per SIMD the register allocation leaves room for: unbounded the kernel takes 112-130 VGPRs - the register network of the
-// entry sort - and runs 3-4 waves per SIMD where its LDS allows 5; swept 3 / 4 / 5 / 6: 85.3 / 83.8 / 87.0 / 84.6 ms of sort 2 - within the noise; halving the
+// (waves per SIMD the register allocation of the BLOCK instances leaves room for: unbounded the kernel takes 112-130 VGPRs - the register
+// network of the entry sort - and runs 3-4 waves per SIMD where its LDS allows 5; swept 3 / 4 / 5 / 6: 85.3 / 83.8 / 87.0 / 84.6 ms of sort 2 - within the noise; halving the
 // occupancy with an LDS pad costs 30 ms: the kernel runs on the latency of its gathers and LDS round trips)
-// W: word of the entry sort, (ordinal, id, diagonal, index in the compacted table) - 64 bits while that fits, 128 beyond
-template <int NT, int ITEMS, typename W = uint64_t>
-__global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
+//
+// The geometry is the template's:
+//   NT     threads of a block;  ITEMS  tuples a thread fetches before it starts inserting (all loads of a batch are in flight together)
+//   H      slots of the hash table;  DL  most distinct triples of a unit (the entry sort's network holds DL words: 64 lanes x 1 / 2 / 4 / 8)
+//   RPT    records a thread stages per round (a round holds NT * RPT records: an average unit of the 50 M-read step has 279 / 75
+//          in the block / wave form and needs one round)
+//   NO     most segments (ordinals) of a unit the instance takes (the block form: every unit's, a range of UT slots starts at most UT)
+//   MINW   waves per SIMD the register allocation leaves room for
+//   W      word of the entry sort, (ordinal, id, diagonal, index in the compacted table) - 64 bits while that fits, 128 beyond
+// The block instances (256 threads, H = AG_H, DL = AG_D) take the units of the three size classes as before.  The WAVE-SIZED instance
+// (64 or 128 threads, a table of 256 or 512 slots) runs in front of them on the units of a quarter / half of the range that are small
+// enough: with one wave the barriers cost nothing and the entry sort idles nobody, and a CU holds 20-30 independent units in flight
+// where the block form holds 4.  A unit it cannot finish it hands on (AggArgs::next).
+//
+// Global round trips a unit waits for, one behind the other (an average unit: one staging round):
+//   1. the staging batch: dst, recVal, segOfRec, recRep of NT * RPT records and the start of the record behind them (the end of a full
+//      round's tuples) - all independent loads, issued together
+//   2. the key gather (ITEMS loads per thread in flight)
+// and per further round 1 and 2 again.  The unit's list entry and segOfRec[first record] are loaded one unit ahead (the entry before the
+// previous unit's staging, the segment before its compaction); a chunk of the entry array is taken once per ~20 units.
+template <int NT, int ITEMS, int H, int DL, int RPT, int NO, int MINW, typename W = uint64_t>
+__global__ __launch_bounds__(NT, MINW) void k_unit_agg(AggArgs a) {
     using namespace runsort;
+    constexpr int R = NT * RPT;                                 // records of a staging round
+    constexpr int MAXR = DL <= 64 ? 1 : DL <= 128 ? 2 : DL <= 256 ? 4 : 8;
+    static_assert((1 << AG_IDX) >= DL && (1 << AG_ORD) > NO && DL <= H, "aggregation geometry: the sort word holds (ordinal, id, diagonal, index)");
+    static_assert((R & (R - 1)) == 0 && (H & (H - 1)) == 0 && NT % 64 == 0, "aggregation geometry: powers of two");
     // the hash table; once its entries are compacted the same memory holds the per-ordinal directory of the unit
-    __shared__ __align__(8) unsigned char sTab[AG_H * 16];
+    __shared__ __align__(8) unsigned char sTab[H * 16];
     unsigned long long *tKey = reinterpret_cast<unsigned long long *>(sTab);
-    unsigned int *tCnt = reinterpret_cast<unsigned int *>(sTab + AG_H * 8), *tLast = reinterpret_cast<unsigned int *>(sTab + AG_H * 12);
-    unsigned int *oFirst = reinterpret_cast<unsigned int *>(sTab), *oEnt = oFirst + (U_T + 2), *oHit = oEnt + (U_T + 2);
-    static_assert(3 * (U_T + 2) * 4 <= AG_H * 16, "the directory fits the table's memory");
-    __shared__ unsigned long long dKey[AG_D];
-    __shared__ unsigned int dCnt[AG_D], dLast[AG_D];
-    __shared__ uint16_t sPerm[AG_D];
-    __shared__ uint64_t sGStart[NT];
-    __shared__ uint32_t sGOff[NT], sGSeg[NT];
-    __shared__ unsigned int sDistinct, sOver, sMaxOrd;
-    __shared__ unsigned long long sBase, sChunkAt, sChunkEnd;
+    unsigned int *tCnt = reinterpret_cast<unsigned int *>(sTab + H * 8), *tLast = reinterpret_cast<unsigned int *>(sTab + H * 12);
+    unsigned int *oFirst = reinterpret_cast<unsigned int *>(sTab), *oEnt = oFirst + (NO + 2), *oHit = oEnt + (NO + 2);
+    static_assert(3 * (NO + 2) * 4 <= H * 16, "the directory fits the table's memory");
+    // the staged records of a round and, once every tuple is in the table, the compacted entries share their memory
+    constexpr int SHARE = (R * 16 > DL * 18) ? R * 16 : DL * 18;
+    __shared__ __align__(8) unsigned char sShare[SHARE];
+    uint64_t *sGStart = reinterpret_cast<uint64_t *>(sShare);
+    uint32_t *sGOff = reinterpret_cast<uint32_t *>(sShare + R * 8), *sGSeg = reinterpret_cast<uint32_t *>(sShare + R * 12);
+    unsigned long long *dKey = reinterpret_cast<unsigned long long *>(sShare);
+    unsigned int *dCnt = reinterpret_cast<unsigned int *>(sShare + DL * 8), *dLast = reinterpret_cast<unsigned int *>(sShare + DL * 12);
+    uint16_t *sPerm = reinterpret_cast<uint16_t *>(sShare + DL * 16);
+    __shared__ uint32_t sRep[NO + 1];                           // representative of the unit's segments by ordinal
+    __shared__ unsigned int sDistinct, sOver, sMaxOrd, sNr[2];
+    __shared__ unsigned long long sBase, sChunkAt, sChunkEnd, sNext;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned int nUnits = *a.count;
     if (tid == 0) { sChunkAt = 0; sChunkEnd = 0; }             // (the loop's first barrier publishes them)
     const int lowBits = a.repShift - 1;                         // id and diagonal
     const uint64_t lowMask = (1ull << lowBits) - 1ull;
-    for (unsigned int item = blockIdx.x; item < nUnits; item += gridDim.x) {
-        const uint64_t base = a.list[3 * (size_t) item];
-        const int m = (int) (a.list[3 * (size_t) item + 1] - base);          // the unit: whole segments, m tuples
-        const uint64_t rec0 = a.list[3 * (size_t) item + 2];
-        const uint32_t g0 = a.segOfRec[rec0];
-        for (int i = tid; i < AG_H; i += NT) { tKey[i] = ~0ull; tCnt[i] = 0u; tLast[i] = 0u; }
-        if (tid == 0) { sDistinct = 0; sOver = 0; sMaxOrd = 0; }
+    const uint32_t maxD = min(a.maxD, (uint32_t) DL);
+    // the unit after this one: its list entry and the segment of its first record are on their way while this one is worked on
+    unsigned int item = blockIdx.x;
+    uint64_t nBase = 0, nEnd = 0, nRec0 = 0; uint32_t nG0 = 0;
+    if (item < nUnits) { nBase = a.list[3 * (size_t) item]; nEnd = a.list[3 * (size_t) item + 1]; nRec0 = a.list[3 * (size_t) item + 2]; nG0 = a.segOfRec[nRec0]; }
+    for (; item < nUnits; item += gridDim.x) {
+        const uint64_t base = nBase;
+        const int m = (int) (nEnd - base);                                    // the unit: whole segments, m tuples
+        const uint64_t rec0 = nRec0;
+        const uint32_t g0 = nG0;
+        const bool more = item + gridDim.x < nUnits;
+        if (more) { const size_t nx = (size_t) item + gridDim.x; nBase = a.list[3 * nx]; nEnd = a.list[3 * nx + 1]; nRec0 = a.list[3 * nx + 2]; }
+        for (int i = tid; i < H; i += NT) { tKey[i] = ~0ull; tCnt[i] = 0u; tLast[i] = 0u; }
+        if (tid == 0) { sDistinct = 0; sOver = 0; sMaxOrd = 0; sNr[0] = 0; sNr[1] = 0; }
         __syncthreads();
-        // ---- the unit's records NT at a time (as k_unit_sort stages them); every tuple goes into the table
+        // ---- the unit's records R at a time (as k_unit_sort stages them); every tuple goes into the table
         const unsigned long long endG = base + (uint64_t) m;
-        for (uint64_t c0 = rec0; c0 < a.nRec; c0 += NT) {
-            const uint64_t j = c0 + tid;
-            const unsigned long long d = j < a.nRec ? a.dst[j] : ~0ull;
-            const bool valid = d < endG;
-            sGOff[tid] = valid ? (uint32_t) (d - base) : (uint32_t) m;
-            sGStart[tid] = valid ? (a.recVal[j] >> RUN_CNT_BITS) : 0ull;
-            sGSeg[tid] = valid ? a.segOfRec[j] - g0 : 0u;
-            const int nr = __syncthreads_count(valid);
+        int par = 0;
+        for (uint64_t c0 = rec0; c0 < a.nRec; c0 += R, par ^= 1) {
+            // (a thread's RPT records are consecutive ones; every load of the batch is in bounds whatever the others return)
+            unsigned int nv = 0;
+#pragma unroll
+            for (int k = 0; k < RPT; k++) {
+                const int i = tid * RPT + k;
+                const uint64_t j = c0 + i;
+                const bool in = j < a.nRec;
+                const unsigned long long d = in ? a.dst[j] : ~0ull;
+                const uint64_t rv = in ? a.recVal[j] : 0ull;
+                const uint32_t sg = in ? a.segOfRec[j] : 0u, rp = in ? a.recRep[j] : 0u;
+                const bool valid = d < endG;
+                sGOff[i] = valid ? (uint32_t) (d - base) : (uint32_t) m;
+                sGStart[i] = valid ? (rv >> RUN_CNT_BITS) : 0ull;
+                sGSeg[i] = valid ? sg - g0 : 0u;
+                if (valid && sg - g0 < (uint32_t) NO) sRep[sg - g0] = rp;          // (every record of a segment writes the same word)
+                nv += (unsigned int) __popcll(__ballot(valid));
+            }
+            if (tid == NT - 1) sNext = j0Next(a.dst, a.nRec, c0 + R);
+            if (lane == 0 && nv) atomicAdd(&sNr[par], nv);
+            __syncthreads();
+            const int nr = (int) sNr[par];                              // the records of this round (they are the first nr of it)
             if (nr == 0) break;
-            const int e0 = (int) sGOff[0], e1 = (nr == NT) ? (int) min((unsigned long long) m, (j0Next(a.dst, a.nRec, c0 + NT) - base)) : m;
-            if (tid == 0) sMaxOrd = max(sMaxOrd, sGSeg[nr - 1]);                    // (segments ascend with the records)
+            if (tid == 0) sNr[par ^ 1] = 0u;                            // (the next round's; this round's last barrier is between)
+            const uint32_t lastOrd = sGSeg[nr - 1];                     // (segments ascend with the records)
+            if (lastOrd >= (uint32_t) NO) { if (tid == 0) sOver = 1u; break; }      // (block-uniform; the barrier behind the loop publishes it)
+            const int e0 = (int) sGOff[0], e1 = (nr == R) ? (int) min((unsigned long long) m, sNext - base) : m;
+            if (tid == 0) sMaxOrd = max(sMaxOrd, lastOrd);
             for (int eb = e0; eb < e1; eb += NT * ITEMS) {
                 uint64_t key[ITEMS]; uint32_t ordv[ITEMS];
 #pragma unroll
@@ -125,7 +189,7 @@ __global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
                     if (e < e1) {
                         int r = 0;
 #pragma unroll
-                        for (int st = NT / 2; st > 0; st >>= 1) if (r + st < nr && (int) sGOff[r + st] <= e) r += st;
+                        for (int st = R / 2; st > 0; st >>= 1) if (r + st < nr && (int) sGOff[r + st] <= e) r += st;
                         key[k] = a.keys[sGStart[r] + (uint64_t) (e - (int) sGOff[r])];
                         ordv[k] = sGSeg[r];
                     }
@@ -136,9 +200,9 @@ __global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
                     if (e < e1) {
                         const uint64_t hk = ((uint64_t) ordv[k] << lowBits) | ((key[k] >> 1) & lowMask);
                         const unsigned int last = ((unsigned int) e << 1) | (unsigned int) (key[k] & 1ull);
-                        uint32_t h = aggHash(hk) & (AG_H - 1);
+                        uint32_t h = aggHash(hk) & (H - 1);
                         int probe = 0;
-                        for (; probe < AG_H; probe++) {
+                        for (; probe < H; probe++) {
                             // (a triple is carried by ~6 tuples on average: five of six find their slot taken by their own key - a plain read
                             // tells, the compare-and-swap is for the slot that looks empty)
                             unsigned long long old = __hip_atomic_load(&tKey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -147,36 +211,47 @@ __global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
                                 if (old == ~0ull) { atomicAdd(&sDistinct, 1u); old = hk; }
                             }
                             if (old == hk) { atomicAdd(&tCnt[h], 1u); atomicMax(&tLast[h], last); break; }
-                            h = (h + 1) & (AG_H - 1);
+                            h = (h + 1) & (H - 1);
                         }
-                        if (probe == AG_H) sOver = 1u;
+                        if (probe == H) sOver = 1u;
                     }
                 }
             }
-            const bool stop = __syncthreads_or(sDistinct > a.maxD || sOver != 0u);
-            if (stop || nr < NT) break;
+            const bool stop = __syncthreads_or(sDistinct > maxD || sOver != 0u);
+            if (stop || nr < R) break;
         }
         __syncthreads();
-        if (sDistinct > a.maxD || sOver) {         // too many distinct triples for the table: the tuple path sorts this unit, k_rle_segment reads it
-            if (tid == 0) a.hard.add(base, base + (uint64_t) m);
+        if (more) nG0 = a.segOfRec[nRec0];
+        if (sDistinct > maxD || sOver) {
+            // too much for this instance: the wave-sized one hands the unit on to the block instance of its size; from there the tuple
+            // path sorts it and k_rle_segment reads it
+            if (tid == 0) {
+                if (a.next.cnt) {
+                    int c = 0;
+                    while (c < U_CLASSES - 1 && (uint32_t) m > a.next.cap[c]) c++;
+                    const unsigned int q = atomicAdd(a.next.cnt + c, 1u);
+                    a.next.list[c][3 * (size_t) q] = base; a.next.list[c][3 * (size_t) q + 1] = base + (uint64_t) m; a.next.list[c][3 * (size_t) q + 2] = rec0;
+                    atomicAdd(a.next.handed, 1u);
+                } else a.hard.add(base, base + (uint64_t) m);
+            }
             __syncthreads();
             continue;
         }
         // ---- compact the table
         unsigned int c = 0;
-        for (int i = tid; i < AG_H; i += NT) c += tKey[i] != ~0ull;
+        for (int i = tid; i < H; i += NT) c += tKey[i] != ~0ull;
         unsigned int D;
         unsigned int pos = cdm_block_excl_sum<unsigned int>(c, D);
-        for (int i = tid; i < AG_H; i += NT) if (tKey[i] != ~0ull) { dKey[pos] = tKey[i]; dCnt[pos] = tCnt[i]; dLast[pos] = tLast[i]; pos++; }
+        for (int i = tid; i < H; i += NT) if (tKey[i] != ~0ull) { dKey[pos] = tKey[i]; dCnt[pos] = tCnt[i]; dLast[pos] = tLast[i]; pos++; }
         __syncthreads();
         // ---- sort the D entries by (ordinal, id, diagonal): one wave, the register network of bucket.h
         if (wave == 0) {
-            bucket::sortGroup<W>((int) D, lane,
+            bucket::sortGroup<W, MAXR>((int) D, lane,
                 [&](int i) { return ((W) dKey[i] << AG_IDX) | (W) i; },
                 [&](auto &v) {
-                    constexpr int R = sizeof(v) / sizeof(v[0]);
+                    constexpr int RR = sizeof(v) / sizeof(v[0]);
 #pragma unroll
-                    for (int r = 0; r < R; r++) { const int p = lane * R + r; if (p < (int) D) sPerm[p] = (uint16_t) ((uint32_t) v[r] & ((1u << AG_IDX) - 1u)); }
+                    for (int r = 0; r < RR; r++) { const int p = lane * RR + r; if (p < (int) D) sPerm[p] = (uint16_t) ((uint32_t) v[r] & ((1u << AG_IDX) - 1u)); }
                 });
         }
         const unsigned int nOrd = sMaxOrd + 1u;
@@ -197,7 +272,7 @@ __global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
             atomicAdd(&oEnt[o], 1u);
             if (p == 0 || (hk >> a.diagBits) != (prev >> a.diagBits)) {                 // first entry of an (ordinal, id)
                 const uint32_t id = (uint32_t) ((hk >> a.diagBits) & idMask);
-                if (id != a.segRep[g0 + o]) atomicAdd(&oHit[o], 1u);                    // self tuples give no hit (:898-903)
+                if (id != sRep[o]) atomicAdd(&oHit[o], 1u);                             // self tuples give no hit (:898-903)
             }
         }
         __syncthreads();
@@ -210,7 +285,7 @@ __global__ __launch_bounds__(NT, CDM_AGG_MINW) void k_unit_agg(AggArgs a) {
             }
             for (unsigned int o = tid; o < nOrd; o += NT) {
                 a.entOff[g0 + o] = b + oFirst[o]; a.entCnt[g0 + o] = oEnt[o];
-                a.perRep[a.segRep[g0 + o]] = oHit[o];
+                a.perRep[sRep[o]] = oHit[o];
             }
         }
         __syncthreads();

@@ -655,7 +655,7 @@ int sort2(const uint64_t *keysIn, unsigned long long nIn, unsigned long long ski
             if ((wide || fromStage) && ownBuffers && nGroup != nKept) { cdm_set_error("cdm_kmermatch: internal error: %llu group tuples counted, %llu in the run records", nKept, nGroup); return CDM_ERR_HIP; }
             if (aggregated) {
                 // (the wide form has no tuple path to fall back to: an entry buffer that proves too small is tried again, larger)
-                const unsigned long long slack = aggv::aggChunkSlack(nGroup / runsort::U_T, nRec, ctx->cuCount);     // (the units' and segments' chunks of the entry array: aggvote.h AG_CHUNK)
+                const unsigned long long slack = aggv::aggChunkSlack(nGroup / runsort::U_T, nRec, ctx->cuCount, aggWaveGeom() >= 0);     // (the units' and segments' chunks of the entry array: aggvote.h AG_CHUNK)
                 unsigned long long capEnt = nGroup / 6 + (4ull << 20) + slack;
                 if (const char *e = cdmGetenv("CDM_AGG_CAP")) capEnt = strtoull(e, nullptr, 10);      // tests: force the overflow fallback
                 int rc = aggregate(sortedOut, nGroup, rk.current(), (const uint64_t *) rv.current(), dst.p, nRec, gk, top2, capEnt, !wordFits);
@@ -808,23 +808,59 @@ int placeHits(const unsigned long long *perRepScan, bool sort1R2, cdm_hits **out
     *out = res;
     return CDM_OK;
 }
+// The wave-sized instances of k_unit_agg (aggvote.h): unit range, threads, table slots, distinct limit, segments, waves per SIMD the
+// registers leave room for, tuples a thread fetches per batch, and the most tuples of a unit of the class.  CDM_AGG_GEOM picks one (the sweep of
+// profiles/wave_agg_geometry.txt), CDM_AGG_WAVE_CAP lowers the tuple capacity, CDM_AGG=block runs the block instances alone.
+struct AggWaveGeom { int range, nt, h, dl, no, minw, items; uint32_t cap; };
+static constexpr AggWaveGeom AGG_WAVE[] = {{256, 64, 256, 128, 32, 6, 2, 2304}, {256, 64, 256, 128, 32, 5, 4, 2304}, {256, 64, 512, 256, 32, 3, 4, 2304},
+                                           {512, 128, 512, 256, 64, 6, 2, 2560}, {512, 64, 512, 256, 64, 3, 4, 2560}, {256, 128, 256, 128, 32, 6, 2, 2304}};
+static constexpr int AGG_WAVE_GEOMS = (int) (sizeof(AGG_WAVE) / sizeof(AGG_WAVE[0])), AGG_WAVE_DEFAULT = 1;
+template <int G, typename W> static void launchWaveAgg(hipStream_t st, unsigned int grid, unsigned int pad, const aggv::AggArgs &a) {
+    constexpr AggWaveGeom g = AGG_WAVE[G];
+    hipLaunchKernelGGL((aggv::k_unit_agg<g.nt, g.items, g.h, g.dl, 2, g.no, g.minw, W>), dim3(grid), dim3(g.nt), pad, st, a);
+}
+template <typename W> static void launchWaveAggGeom(int geom, hipStream_t st, unsigned int grid, unsigned int pad, const aggv::AggArgs &a) {
+    switch (geom) {
+        case 0: launchWaveAgg<0, W>(st, grid, pad, a); break;
+        case 1: launchWaveAgg<1, W>(st, grid, pad, a); break;
+        case 2: launchWaveAgg<2, W>(st, grid, pad, a); break;
+        case 3: launchWaveAgg<3, W>(st, grid, pad, a); break;
+        case 4: launchWaveAgg<4, W>(st, grid, pad, a); break;
+        default: launchWaveAgg<5, W>(st, grid, pad, a); break;
+    }
+}
+template <int CLS, typename W> static void launchBlockAgg(hipStream_t st, unsigned int grid, unsigned int pad, const aggv::AggArgs &a) {
+    // (tuples a thread fetches per batch: the class's capacity in one batch, the largest class's in two - twelve keys in registers next to
+    // the look-ahead of the next unit spill)
+    constexpr int ITEMS = runsort::U_CLASS_CAP[CLS] / 256 > 8 ? runsort::U_CLASS_CAP[CLS] / 512 : runsort::U_CLASS_CAP[CLS] / 256;
+    hipLaunchKernelGGL((aggv::k_unit_agg<256, ITEMS, aggv::AG_H, aggv::AG_D, 2, runsort::U_T, CDM_AGG_MINW, W>), dim3(grid), dim3(256), pad, st, a);
+}
 // sort 2 on aggregated tuples (aggvote.h): segments, k_unit_agg in k_unit_sort's place, the tuple sorters for what no table holds,
 // k_rle_segment for those.  CDM_ERR_UNSUPPORTED: the entry buffer was too small (the caller takes the tuple path).
-static void aggUnitHook(hipStream_t st, unsigned int grid, const unsigned long long *list, const unsigned int *count, bucket::BigList hard, void *user) {
-    aggv::AggArgs *u = reinterpret_cast<aggv::AggArgs *>(user);
+static void aggUnitHook(hipStream_t st, unsigned int grid, int cls, const unsigned long long *list, const unsigned int *count, const runsort::UnitClassLists &next, bucket::BigList hard, void *user) {
+    const aggv::AggArgs *u = reinterpret_cast<const aggv::AggArgs *>(user);
     aggv::AggArgs a = *u;
     a.list = list; a.count = count; a.hard = hard;
-    const int cls = (int) (u->nextClass++ % runsort::U_CLASSES);       // (called once per size class, smallest first)
     const unsigned int pad = cdm_lds_pad("CDM_LDS_PAD_AGG");
-    if (u->wideWord) {
-        if (cls == 0) hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[0] / 256, bucket::u128>), dim3(grid), dim3(256), pad, st, a);
-        else if (cls == 1) hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[1] / 256, bucket::u128>), dim3(grid), dim3(256), pad, st, a);
-        else hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[2] / 256, bucket::u128>), dim3(grid), dim3(256), pad, st, a);
+    grid = std::min(grid, (unsigned int) u->cuCount * aggv::aggGridPerCu(u->waveGeom >= 0));
+    if (cls < 0) {      // the wave-sized instance, in front of the size classes
+        a.next = next;
+        if (u->wideWord) launchWaveAggGeom<bucket::u128>(u->waveGeom, st, grid, pad, a); else launchWaveAggGeom<uint64_t>(u->waveGeom, st, grid, pad, a);
         return;
     }
-    if (cls == 0) hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[0] / 256>), dim3(grid), dim3(256), pad, st, a);
-    else if (cls == 1) hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[1] / 256>), dim3(grid), dim3(256), pad, st, a);
-    else hipLaunchKernelGGL((aggv::k_unit_agg<256, runsort::U_CLASS_CAP[2] / 256>), dim3(grid), dim3(256), pad, st, a);
+    if (u->wideWord) {
+        if (cls == 0) launchBlockAgg<0, bucket::u128>(st, grid, pad, a); else if (cls == 1) launchBlockAgg<1, bucket::u128>(st, grid, pad, a); else launchBlockAgg<2, bucket::u128>(st, grid, pad, a);
+        return;
+    }
+    if (cls == 0) launchBlockAgg<0, uint64_t>(st, grid, pad, a); else if (cls == 1) launchBlockAgg<1, uint64_t>(st, grid, pad, a); else launchBlockAgg<2, uint64_t>(st, grid, pad, a);
+}
+// the wave-sized instance in use: -1 under CDM_AGG=block
+static int aggWaveGeom() {
+    const char *m = cdmGetenv("CDM_AGG");
+    if (m && !strcmp(m, "block")) return -1;
+    int g = AGG_WAVE_DEFAULT;
+    if (const char *e = cdmGetenv("CDM_AGG_GEOM")) { const int v = atoi(e); if (v >= 0 && v < AGG_WAVE_GEOMS) g = v; }
+    return g;
 }
 int aggregate(uint64_t *sortedOut, unsigned long long nGroup, const uint32_t *recRep, const uint64_t *recVal, const unsigned long long *dst, unsigned long long nRec,
               const uint64_t *gk, int top2, unsigned long long capEnt, bool wideWord) {
@@ -847,11 +883,16 @@ int aggregate(uint64_t *sortedOut, unsigned long long nGroup, const uint32_t *re
     AggArgs a;
     a.keys = gk; a.recVal = recVal; a.dst = dst; a.nRec = nRec; a.segOfRec = agSegOfRec.p; a.segRep = agSegRep.p; a.segFirstRec = agSegFirstRec.p; a.nSeg = nSeg;
     a.entOff = agEntOff.p; a.entCnt = agEntCnt.p; a.perRep = agPerRep.p; a.ent = agEnt.p; a.cursor = agCursor.p; a.cap = capEnt; a.overflow = agFlags.p;
-    a.maxD = AG_D;
+    a.maxD = AG_D; a.recRep = recRep; a.cuCount = ctx->cuCount; a.waveGeom = aggWaveGeom();
+    int unitRange = runsort::U_T; uint32_t frontCap = 0;
+    if (a.waveGeom >= 0) {
+        unitRange = AGG_WAVE[a.waveGeom].range; frontCap = AGG_WAVE[a.waveGeom].cap;
+        if (const char *e = cdmGetenv("CDM_AGG_WAVE_CAP")) { const long v = atol(e); if (v >= 1 && v < (long) frontCap) frontCap = (uint32_t) v; }
+    }
     if (const char *e = cdmGetenv("CDM_AGG_D")) { const long v = atol(e); if (v >= 1 && v <= AG_D) a.maxD = (uint32_t) v; }
     a.repShift = (int) (idBits + diagBits + 1); a.diagBits = (int) diagBits; a.idBits = idBits; a.sorted = sortedOut; a.list = nullptr; a.count = nullptr; a.hard.list = nullptr; a.hard.cnt = nullptr;
     a.wideWord = wideWord ? 1 : 0;
-    if (runsort::segmentedSortKeys(s, ctx->cuCount, sortedOut, sortedOut, nGroup, (int) (idBits + diagBits + 1), (int) (diagBits + 1), top2, recRep, dst, nRec, gk, recVal, aggUnitHook, &a, wide, agSegOfRec.p, (int) bitsFor((uint64_t) nSeg + 1), agSegFirstRec.p, (uint64_t) nSeg) != CDM_OK) {
+    if (runsort::segmentedSortKeys(s, ctx->cuCount, sortedOut, sortedOut, nGroup, (int) (idBits + diagBits + 1), (int) (diagBits + 1), top2, recRep, dst, nRec, gk, recVal, aggUnitHook, &a, wide, agSegOfRec.p, (int) bitsFor((uint64_t) nSeg + 1), agSegFirstRec.p, (uint64_t) nSeg, unitRange, frontCap) != CDM_OK) {
         cdm_set_error("cdm_kmermatch: segmented sort 2 failed: %s", hipGetErrorString(hipGetLastError())); return CDM_ERR_HIP;
     }
     // the segments the tuple sorters finished (deep pile-ups, units with too many distinct triples)
@@ -874,6 +915,17 @@ int aggregate(uint64_t *sortedOut, unsigned long long nGroup, const uint32_t *re
     }
     unsigned long long used = 0;
     hipMemcpy(&used, agCursor.p, 8, hipMemcpyDeviceToHost);
+    if (cdmGetenv("CDM_BUCKET_STATS") && !fl[0]) {     // every segment's entries, whoever wrote them: a unit finished twice would show here
+        std::vector<uint32_t> ec(nSeg);
+        hipMemcpy(ec.data(), agEntCnt.p, (size_t) nSeg * 4, hipMemcpyDeviceToHost);
+        unsigned long long written = 0;
+        for (uint32_t c : ec) written += c;
+        fprintf(stderr, "aggregate: %llu entries written (%s)\n", written, a.waveGeom >= 0 ? "wave-sized units in front" : "block form");
+        if (a.waveGeom >= 0) {
+            const AggWaveGeom &g = AGG_WAVE[a.waveGeom];
+            fprintf(stderr, "aggregate: wave-sized instance %d: unit range %d, %d threads, table of %d slots, distinct limit %d, %d records a round, %u tuples\n", a.waveGeom, g.range, g.nt, g.h, g.dl, 2 * g.nt, frontCap);
+        }
+    }
     if (cdmGetenv("CDM_BUCKET_STATS")) fprintf(stderr, "aggregate: %llu group tuples, %u segments, %llu entries (room for %llu), %u segments through the tuple sorters%s\n", nGroup, nSeg, used, capEnt, fl[1],
                                             fl[0] ? "; entry buffer overflow" : "");
     if (fl[0]) { agEnt.free(); return CDM_ERR_UNSUPPORTED; }

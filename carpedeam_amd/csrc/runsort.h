@@ -311,11 +311,13 @@ __global__ __launch_bounds__(256) void k_gather_ranges(const unsigned long long 
 
 // ---------------------------------------------------------------------------------------------- segments by size class
 constexpr int U_T = 1024;             // slots per unit range of the segmented sort (k_unit_sort below)
+static_assert(U_T == 1 << 10, "SegListArgs::uShift");
 constexpr int SEG_CLASSES = 4;          // 0..2: k_block_sort with 2, 4, 8 waves; 3: longer (the global radix sort of radix.h)
 struct SegListArgs {
     const uint32_t *recRep; const unsigned long long *dst; uint64_t nRec;
     uint32_t maxWave;                   // segments up to this length are finished by k_bucket_sort
     const unsigned long long *uEnd; uint64_t units;       // the units' ends (NULL: there are no units): a segment that lies inside its unit is the unit's
+    int uShift = 10;                    // log2 of the unit range (U_T, or the smaller range the aggregating hook asks for)
     uint32_t cap[SEG_CLASSES - 1];      // capacities of the block classes
     unsigned long long *list[SEG_CLASSES]; unsigned int *cnt;      // cnt[c]
     const unsigned long long *segFirstRec = nullptr; uint64_t nSeg = 0;      // (k_seg_list_segments) first record of every segment, [nSeg] = nRec
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(1024) void k_seg_list(SegListArgs a) {
             const unsigned long long n = e - s;
             // (with the capacities lowered below a unit's range - tests - a segment beyond maxWave can lie in the middle of a unit: it is
             // sorted / aggregated with its unit, and listing it as well would hand the fallback two overlapping ranges)
-            const bool inUnit = a.uEnd && s / U_T < a.units && e <= a.uEnd[s / U_T];
+            const bool inUnit = a.uEnd && (s >> a.uShift) < a.units && e <= a.uEnd[s >> a.uShift];
             if (n > a.maxWave && !inUnit) cls = n <= a.cap[0] ? 0 : n <= a.cap[1] ? 1 : n <= a.cap[2] ? 2 : 3;
         }
     }
@@ -357,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_seg_list_segments(SegListArgs a) {
     if (g < a.nSeg) {
         s = a.dst[a.segFirstRec[g]]; e = a.dst[a.segFirstRec[g + 1]];
         const unsigned long long n = e - s;
-        const bool inUnit = a.uEnd && s / U_T < a.units && e <= a.uEnd[s / U_T];
+        const bool inUnit = a.uEnd && (s >> a.uShift) < a.units && e <= a.uEnd[s >> a.uShift];
         if (n > a.maxWave && !inUnit) cls = n <= a.cap[0] ? 0 : n <= a.cap[1] ? 1 : n <= a.cap[2] ? 2 : 3;
     }
     if (!__syncthreads_or(cls >= 0)) return;
@@ -404,11 +406,12 @@ struct UnitBoundArgs {
 };
 // one thread per record; a record with a unit boundary B in (dst[r], dst[r + 1]] finds the end (and, if need be, the start) of its
 // segment: the unit that begins at B starts where the segment ends
+template <int UT>
 __global__ __launch_bounds__(1024) void k_unit_bounds(UnitBoundArgs a) {
     const uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.nRec) return;
     const unsigned long long d0 = a.dst[r], d1 = a.dst[r + 1];
-    const uint64_t uLo = d0 / U_T + 1, uHi = (r == a.nRec - 1) ? a.units : d1 / U_T;       // (the end of the array closes the last unit)
+    const uint64_t uLo = d0 / UT + 1, uHi = (r == a.nRec - 1) ? a.units : d1 / UT;       // (the end of the array closes the last unit)
     if (r == 0) { a.uStart[0] = 0; a.uRec[0] = 0; }
     if (uLo > uHi) return;
     uint64_t hi, first;
@@ -428,14 +431,15 @@ __global__ __launch_bounds__(1024) void k_unit_bounds(UnitBoundArgs a) {
     for (uint64_t u = uLo; u <= uHi; u++) {
         if (u <= a.units) { a.uStart[u] = e; a.uRec[u] = hi; }
         // the unit in front of boundary u: this segment is its last one if it starts in that unit's range
-        const bool mine = sSeg >= (u - 1) * (unsigned long long) U_T;
+        const bool mine = sSeg >= (u - 1) * (unsigned long long) UT;
         if (u >= 1 && u - 1 < a.units) a.uEnd[u - 1] = (mine && e - sSeg > a.maxSeg) ? sSeg : e;
     }
 }
 struct UnitClassArgs {
     const unsigned long long *uStart, *uEnd, *uRec; uint64_t units, n;
-    uint32_t cap[U_CLASSES];
-    unsigned long long *list[U_CLASSES]; unsigned int *cnt;        // (start, end, first record) per unit of the class
+    uint32_t cap[U_CLASSES + 1];
+    unsigned long long *list[U_CLASSES + 1]; unsigned int *cnt;    // (start, end, first record) per unit of the class
+    int nCls = U_CLASSES;       // U_CLASSES + 1: a class of small units in front (the aggregating hook's wave-sized instance)
 };
 __global__ __launch_bounds__(1024) void k_unit_classes(UnitClassArgs a) {
     const uint64_t u = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -443,10 +447,11 @@ __global__ __launch_bounds__(1024) void k_unit_classes(UnitClassArgs a) {
     if (u < a.units) {
         s = a.uStart[u]; e = a.uEnd[u]; r0 = a.uRec[u];
         const unsigned long long m = e > s ? e - s : 0;
-        if (m) cls = m <= a.cap[0] ? 0 : m <= a.cap[1] ? 1 : 2;
+        if (m) { cls = 0; while (cls < a.nCls - 1 && m > a.cap[cls]) cls++; }
     }
 #pragma unroll
-    for (int c = 0; c < U_CLASSES; c++) {
+    for (int c = 0; c < U_CLASSES + 1; c++) {
+        if (c >= a.nCls) break;
         const uint32_t q = cdm_block_append(a.cnt + c, cls == c);
         if (cls == c) { a.list[c][3 * (size_t) q] = s; a.list[c][3 * (size_t) q + 1] = e; a.list[c][3 * (size_t) q + 2] = r0; }
     }
@@ -639,12 +644,19 @@ __global__ __launch_bounds__(256) void k_gather_ranges_dense(const unsigned long
         }
     }
 }
-typedef void (*UnitHook)(hipStream_t s, unsigned int grid, const unsigned long long *list, const unsigned int *count, bucket::BigList hard, void *user);
+// The lists of the U_CLASSES size classes, for a hook whose small-unit instance hands a unit on to them (the same triple, appended)
+struct UnitClassLists { unsigned long long *list[U_CLASSES]; unsigned int *cnt; uint32_t cap[U_CLASSES]; unsigned int *handed; };
+// cls: 0 .. U_CLASSES - 1, or -1 for the class of small units in front of them (frontCap below)
+typedef void (*UnitHook)(hipStream_t s, unsigned int grid, int cls, const unsigned long long *list, const unsigned int *count, const UnitClassLists &next, bucket::BigList hard, void *user);
 inline int segmentedSortKeys(hipStream_t s, int cuCount, uint64_t *in, uint64_t *out, uint64_t n, int shiftHi, int hiShift, int top,
                              const uint32_t *recRep, const unsigned long long *dst, uint64_t nRec, const uint64_t *srcKeys, const uint64_t *recVal,
                              UnitHook unitHook = nullptr, void *hookUser = nullptr, bool wide = false, const uint32_t *segOfRec = nullptr, int segBits = 0,
-                             const unsigned long long *segFirstRec = nullptr, uint64_t nSeg = 0) {
+                             const unsigned long long *segFirstRec = nullptr, uint64_t nSeg = 0, int unitRange = U_T, uint32_t frontCap = 0) {
+    // unitRange (256, 512 or U_T) / frontCap (hook only): units are the segments that start in a range of that many slots, and those of
+    // at most frontCap tuples are listed as a class of their own, handed to the hook first with cls = -1
     using namespace bucket;
+    if ((unitRange != 256 && unitRange != 512 && unitRange != U_T) || ((unitRange != U_T || frontCap) && !unitHook)) { cdm_set_error("segmented sort: a unit range of its own needs the aggregating unit kernel"); return CDM_ERR_UNSUPPORTED; }
+    const int nFront = frontCap ? 1 : 0;
     if (n == 0) return CDM_OK;
     if (wide && (!unitHook || !segOfRec)) { cdm_set_error("segmented sort: keys without the representative need the aggregating unit kernel and its segment table"); return CDM_ERR_UNSUPPORTED; }
     uint32_t maxSeg = U_MAXSEG, blockCap = wide ? 0 : 4096;
@@ -654,12 +666,12 @@ inline int segmentedSortKeys(hipStream_t s, int cuCount, uint64_t *in, uint64_t 
     if (const char *e = cdmGetenv("CDM_UNIT_SUB")) { const long m = atol(e); if (m >= 1 && m <= BK_MAXB) maxSub = (uint32_t) m; }
     if (shiftHi - 1 + BLK_IDX > 64) blockCap = 0;       // the block sorter's word does not hold such keys: the global radix sort takes them
     if (!unitHook && U_ORDB + shiftHi - 1 + U_IDXB > 64) maxSeg = 0; // nor does the unit sorter's (ordinal, id, diagonal, index): everything goes to the radix sort
-    const uint64_t units = (n + U_T - 1) / U_T;
+    const uint64_t units = (n + unitRange - 1) / unitRange;
     const size_t listCap = (size_t) (n / ((uint64_t) maxSeg + 1) + 2);
-    DevBuf<unsigned long long> lists[SEG_CLASSES], hardList, uStart, uEnd, uRec, uList[U_CLASSES]; DevBuf<unsigned int> cnt;
-    constexpr int NCNT = SEG_CLASSES + 1 + U_CLASSES;
+    DevBuf<unsigned long long> lists[SEG_CLASSES], hardList, uStart, uEnd, uRec, uList[U_CLASSES + 1]; DevBuf<unsigned int> cnt;
+    constexpr int NCNT = SEG_CLASSES + 1 + U_CLASSES + 2 + U_CLASSES + 1;      // (.. the front class, the units it handed on; k_unit_classes' counters in its own order)
     if (!cnt.alloc(NCNT) || !hardList.alloc(2 * (size_t) (units + 1)) || !uStart.alloc(units + 2) || !uEnd.alloc(units + 1) || !uRec.alloc(units + 2)) return CDM_ERR_HIP;
-    for (int c = 0; c < U_CLASSES; c++) if (!uList[c].alloc(3 * (size_t) (units + 1))) return CDM_ERR_HIP;
+    for (int c = 0; c < U_CLASSES + nFront; c++) if (!uList[c].alloc(3 * (size_t) (units + 1))) return CDM_ERR_HIP;
     for (int c = 2; c < SEG_CLASSES; c++) if (!lists[c].alloc(2 * (listCap + (c == 3 ? (size_t) units + 1 : 0)))) return CDM_ERR_HIP;
     hipMemsetAsync(cnt.p, 0, NCNT * 4, s);
     if (maxSeg) {
@@ -667,16 +679,28 @@ inline int segmentedSortKeys(hipStream_t s, int cuCount, uint64_t *in, uint64_t 
         hipMemsetAsync(uStart.p, 0, (units + 2) * 8, s); hipMemsetAsync(uEnd.p, 0, (units + 1) * 8, s); hipMemsetAsync(uRec.p, 0, (units + 2) * 8, s);
         UnitBoundArgs ub; ub.recRep = recRep; ub.dst = dst; ub.nRec = nRec; ub.maxSeg = maxSeg; ub.units = units; ub.uStart = uStart.p; ub.uEnd = uEnd.p; ub.uRec = uRec.p;
         if (segOfRec && segFirstRec) { ub.segOfRec = segOfRec; ub.segFirstRec = segFirstRec; }
-        hipLaunchKernelGGL(k_unit_bounds, CDM_GRID((nRec + 1023) / 1024, 1024), dim3(1024), 0, s, ub);
+        if (unitRange == 256) hipLaunchKernelGGL(k_unit_bounds<256>, CDM_GRID((nRec + 1023) / 1024, 1024), dim3(1024), 0, s, ub);
+        else if (unitRange == 512) hipLaunchKernelGGL(k_unit_bounds<512>, CDM_GRID((nRec + 1023) / 1024, 1024), dim3(1024), 0, s, ub);
+        else hipLaunchKernelGGL(k_unit_bounds<U_T>, CDM_GRID((nRec + 1023) / 1024, 1024), dim3(1024), 0, s, ub);
         UnitClassArgs uc; uc.uStart = uStart.p; uc.uEnd = uEnd.p; uc.uRec = uRec.p; uc.units = units; uc.n = n;
-        for (int c = 0; c < U_CLASSES; c++) { uc.cap[c] = (uint32_t) U_CLASS_CAP[c]; uc.list[c] = uList[c].p; }
-        uc.cnt = cnt.p + SEG_CLASSES + 1;
+        // (the front class, if there is one, is list U_CLASSES and counter U_CLASSES of the block below, but class 0 of k_unit_classes)
+        unsigned int *const uCnt = cnt.p + SEG_CLASSES + 1;
+        unsigned int *const clsCnt = uCnt + U_CLASSES + 2;
+        uc.nCls = U_CLASSES + nFront;
+        if (nFront) { uc.cap[0] = frontCap; uc.list[0] = uList[U_CLASSES].p; }
+        for (int c = 0; c < U_CLASSES; c++) { uc.cap[c + nFront] = (uint32_t) U_CLASS_CAP[c]; uc.list[c + nFront] = uList[c].p; }
+        uc.cnt = clsCnt;
         hipLaunchKernelGGL(k_unit_classes, dim3((unsigned) ((units + 1023) / 1024)), dim3(1024), 0, s, uc);
+        hipMemcpyAsync(uCnt, clsCnt + nFront, U_CLASSES * 4, hipMemcpyDeviceToDevice, s);
+        if (nFront) hipMemcpyAsync(uCnt + U_CLASSES, clsCnt, 4, hipMemcpyDeviceToDevice, s);
         UnitArgs ua; ua.keys = srcKeys; ua.recVal = recVal; ua.dst = dst; ua.nRec = nRec; ua.out = out; ua.n = n; ua.repShift = shiftHi; ua.hiShift = hiShift; ua.maxSub = maxSub; ua.hard.list = hardList.p; ua.hard.cnt = cnt.p + SEG_CLASSES;
         const unsigned int pad = cdm_lds_pad("CDM_LDS_PAD_UNIT");
         const unsigned int grid = (unsigned int) std::min<uint64_t>(units, (uint64_t) cuCount * 64);
         if (unitHook) {
-            for (int c = 0; c < U_CLASSES; c++) unitHook(s, grid, uList[c].p, cnt.p + SEG_CLASSES + 1 + c, ua.hard, hookUser);
+            UnitClassLists next; next.cnt = uCnt; next.handed = uCnt + U_CLASSES + 1;
+            for (int c = 0; c < U_CLASSES; c++) { next.list[c] = uList[c].p; next.cap[c] = (uint32_t) U_CLASS_CAP[c]; }
+            if (nFront) unitHook(s, grid, -1, uList[U_CLASSES].p, uCnt + U_CLASSES, next, ua.hard, hookUser);
+            for (int c = 0; c < U_CLASSES; c++) unitHook(s, grid, c, uList[c].p, uCnt + c, next, ua.hard, hookUser);
         } else {
         ua.list = uList[0].p; ua.count = cnt.p + SEG_CLASSES + 1; hipLaunchKernelGGL((k_unit_sort<U_CLASS_CAP[0], U_CLASS_NT[0]>), dim3(grid), dim3(U_CLASS_NT[0]), pad, s, ua);
         ua.list = uList[1].p; ua.count = cnt.p + SEG_CLASSES + 2; hipLaunchKernelGGL((k_unit_sort<U_CLASS_CAP[1], U_CLASS_NT[1]>), dim3(grid), dim3(U_CLASS_NT[1]), pad, s, ua);
@@ -684,7 +708,7 @@ inline int segmentedSortKeys(hipStream_t s, int cuCount, uint64_t *in, uint64_t 
         }
     }
     // the segments no unit can hold, listed by size class: one block of 8 waves (bitonic network, bucket.h) up to 4096, the global radix sort beyond
-    SegListArgs la; la.recRep = recRep; la.dst = dst; la.nRec = nRec; la.maxWave = maxSeg; la.uEnd = maxSeg ? uEnd.p : nullptr; la.units = units;
+    SegListArgs la; la.recRep = recRep; la.dst = dst; la.nRec = nRec; la.maxWave = maxSeg; la.uEnd = maxSeg ? uEnd.p : nullptr; la.units = units; la.uShift = unitRange == 256 ? 8 : unitRange == 512 ? 9 : 10;
     la.cap[0] = 0; la.cap[1] = 0; la.cap[2] = blockCap;
     for (int c = 0; c < SEG_CLASSES; c++) la.list[c] = lists[c].p;      // (classes 0 and 1 stay empty: their capacities are 0)
     la.cnt = cnt.p;
@@ -699,6 +723,8 @@ inline int segmentedSortKeys(hipStream_t s, int cuCount, uint64_t *in, uint64_t 
     if (hipMemcpyAsync(hc, cnt.p, NCNT * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return CDM_ERR_HIP;
     if (cdmGetenv("CDM_BUCKET_STATS")) fprintf(stderr, "segmentedSortKeys%s: n %llu, %llu records, %llu units (%u / %u / %u by size class): segments > %u: %u (<= %u, block sort), %u longer (global radix sort); %u hard units (global radix sort)\n",
                                             unitHook ? " (units aggregated)" : "", (unsigned long long) n, (unsigned long long) nRec, (unsigned long long) units, hc[SEG_CLASSES + 1], hc[SEG_CLASSES + 2], hc[SEG_CLASSES + 3], maxSeg, hc[2], blockCap, hc[3], hc[SEG_CLASSES]);
+    if (nFront && cdmGetenv("CDM_BUCKET_STATS")) fprintf(stderr, "segmentedSortKeys: unit range %d: %u units of at most %u tuples in the wave class, %u of them handed on to the size classes (counted there as well)\n",
+                                                          unitRange, hc[SEG_CLASSES + 1 + U_CLASSES], frontCap, hc[SEG_CLASSES + 2 + U_CLASSES]);
     const unsigned int nBig = hc[3] + hc[SEG_CLASSES];
     if (nBig == 0) return CDM_OK;
     // deep pile-ups and hard units: gather, sort on the whole key with the radix sort of radix.h (stable), scatter.  (The ranges are disjoint and
