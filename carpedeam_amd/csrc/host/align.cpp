@@ -241,8 +241,6 @@ bool canBeCovered(float covThr, int covMode, float ql, float tl) {      // Util.
     }
 }
 bool hasCoverage(float covThr, int covMode, float qc, float tc) { switch (covMode) { case 0: return qc >= covThr && tc >= covThr; case 2: return qc >= covThr; case 1: return tc >= covThr; default: return true; } }
-char *utoa(unsigned long long v, char *p) { char b[24]; int n = 0; do { b[n++] = (char) ('0' + v % 10); v /= 10; } while (v); while (n) *p++ = b[--n]; return p; }
-char *itoa(long long v, char *p) { if (v < 0) { *p++ = '-'; return utoa((unsigned long long) -v, p); } return utoa((unsigned long long) v, p); }
 char *seqIdText(float s, char *p) {     // Util::fastSeqIdToBuffer (Util.cpp:278-307)
     if (s == 1.0) { memcpy(p, "1.00", 4); return p + 4; }
     *p++ = '0'; *p++ = '.';

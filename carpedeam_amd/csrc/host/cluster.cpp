@@ -28,7 +28,6 @@ bool exists(const std::string &p) { struct stat st; return lstat(p.c_str(), &st)
 // Util::parseKey: the first white-space delimited token of a line as an unsigned (fast_atoi: digits only)
 inline uint32_t lineKey(const char *d) { uint32_t v = 0; while (*d >= '0' && *d <= '9') v = v * 10 + (uint32_t) (*d++ - '0'); return v; }
 inline const char *skipLine(const char *d) { while (*d != '\n' && *d != '\0') d++; return *d == '\n' ? d + 1 : d; }
-char *utoa(unsigned long long v, char *p) { char b[24]; int n = 0; do { b[n++] = (char) ('0' + v % 10); v /= 10; } while (v); while (n) *p++ = b[--n]; return p; }
 // FileUtil::findDatafiles: X, or X.0 .. X.n
 std::vector<std::string> dataFiles(const std::string &db) {
     std::vector<std::string> f;

@@ -38,6 +38,8 @@
 #include <cerrno>
 #include "mmdb.h"
 #include "sidecar.h"
+#include "cli.h"
+#include "contig_reports.h"
 
 // host/ingest.cpp
 int createdbModule(const std::vector<std::string> &files, const std::string &outPath, bool shuffle, int dbType, std::string *err);
@@ -59,15 +61,6 @@ int alignModule(const std::string &qPath, const std::string &tPath, const std::s
 int mvdbModule(const std::string &src, const std::string &dst, std::string *err);
 
 namespace {
-std::thread *g_deviceThread = NULL;          // a module's device start-up running beside the main thread (DeviceStart): joined before any exit
-void quiesce() { if (g_deviceThread && g_deviceThread->joinable() && g_deviceThread->get_id() != std::this_thread::get_id()) g_deviceThread->join(); }
-[[noreturn]] void die(const std::string &msg) { quiesce(); fprintf(stderr, "%s\n", msg.c_str()); exit(EXIT_FAILURE); }
-// a call the device path does not implement, found before any work was done: status 77 tells the front end (host/front.c) that the
-// reference binary - if the deployment has one - may take this call instead
-[[noreturn]] void unsupported(const std::string &msg) { quiesce(); fprintf(stderr, "%s\n", msg.c_str()); exit(77); }
-void check(int rc, const char *what) { if (rc != CDM_OK) die(std::string(what) + ": " + cdm_last_error()); }
-
-struct Args { std::vector<std::string> pos; std::map<std::string, std::string> flag; };
 Args parse(int argc, char **argv) {
     Args a;
     for (int i = 0; i < argc; i++) {
@@ -77,13 +70,6 @@ Args parse(int argc, char **argv) {
     }
     return a;
 }
-// Per-module flag tables (the reference's own lists: lib/mmseqs/src/commons/Parameters.cpp:871-892 kmermatcher, :422-439
-// rescorediagonal, src/commons/LocalParameters.h:155-171 assembleresults = ancient_correction / ancient_read_assemble).
-//   'U' used by the MI355X path;  'N' accepted, no effect on this path in the reference either (or only on resources);
-//   'V' accepted only with one of the listed values (anything else would be computed differently: refused);
-//   'R' a flag the reference's list for the command knows and this path does not handle: refused whatever its value.
-// A flag that is not in the module's list is an error, as in Parameters::parseParameters (:1703 "Unrecognized parameter").
-struct FlagSpec { const char *name; char kind; const char *allowed; const char *why; };
 const FlagSpec KMERMATCHER_FLAGS[] = {
     {"--kmer-per-seq", 'U', 0, 0}, {"--kmer-per-seq-scale", 'U', 0, 0}, {"--cov-mode", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"-c", 'U', 0, 0}, {"--hash-shift", 'U', 0, 0},
     {"--include-only-extendable", 'U', 0, 0}, {"--ignore-multi-kmer", 'U', 0, 0},
@@ -112,38 +98,6 @@ const FlagSpec ANCIENT_FLAGS[] = {
     {"--keep-target", 'N', 0, "not read by these modules"}, {"--min-seqid-corr-reads", 'N', 0, "not read by these modules"}, {"--min-merge-seq-id", 'U', 0, 0},
     {"--min-seqid-corr-contigs", 'N', 0, "a workflow flag: it becomes the contig phase's --min-seq-id (Nuclassembler.cpp:124-126); ancient_reads_loop reads it"}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0},
     {"--rescore-mode", 'V', "3", "re-alignment of parked candidates is end-to-end ungapped (ancientReadsResults.cpp:502)"}, {0, 0, 0, 0}};
-void checkFlags(const char *module, const Args &a, const FlagSpec *spec, const char *const *extra = NULL) {
-    for (const auto &kv : a.flag) {
-        const FlagSpec *f = spec;
-        while (f->name && kv.first != f->name) f++;
-        bool known = f->name != NULL;
-        for (const char *const *e = extra; !known && e && *e; e++) known = kv.first == *e;
-        if (!known) die("Unrecognized parameter \"" + kv.first + "\"");
-        if (f->name && f->kind == 'R') unsupported(std::string(module) + ": " + kv.first + " is not supported by the MI355X path (" + f->why + ")");
-        if (f->name && f->kind == 'V') {
-            const std::string al = f->allowed;
-            const bool ok = (al.size() >= 2 && al[0] == '*') ? kv.second.find(al.substr(1, al.size() - 2)) != std::string::npos : kv.second == al;
-            if (!ok) unsupported(std::string(module) + ": " + kv.first + " " + kv.second + " is not supported by the MI355X path (" + f->why + "; accepted: " + (al.empty() ? "\"\"" : al) + ")");
-        }
-    }
-}
-float fflag(Args &a, const char *n, float d) { return a.flag.count(n) ? strtof(a.flag[n].c_str(), NULL) : d; }
-long iflag(Args &a, const char *n, long d) { return a.flag.count(n) ? strtol(a.flag[n].c_str(), NULL, 10) : d; }
-
-// CDM_TIMING=1: where a module's wall time goes (stderr)
-std::chrono::steady_clock::time_point g_t0, g_lastLap;
-struct Laps {
-    bool on; std::chrono::steady_clock::time_point t;
-    Laps() : on(getenv("CDM_TIMING") != NULL), t(std::chrono::steady_clock::now()) {
-        if (on && g_t0.time_since_epoch().count()) fprintf(stderr, "  %-32s %.3f s\n", "(arguments, flags)", std::chrono::duration<double>(t - g_t0).count());
-        g_lastLap = t;
-    }
-    void lap(const char *what) {
-        if (!on) return;
-        const auto n = std::chrono::steady_clock::now();
-        fprintf(stderr, "  %-32s %.3f s\n", what, std::chrono::duration<double>(n - t).count()); t = n; g_lastLap = n;
-    }
-};
 // The end of a module whose outputs are written and closed: the process leaves HERE - no release of device buffers (giving tens of GB
 // back to the driver costs seconds, profiles/r05_time_modules_50M_*), no unmapping of the input files, no destructors of the
 // multi-GB host buffers; the operating system and the driver take everything back at once.  (Not under a profiler or sanitizer that
@@ -176,12 +130,6 @@ void finishModule(int rc) {
     fflush(stdout); fflush(stderr);
     reportDone(rc);
     _exit(rc);
-}
-cdm_ctx *openCtx(int offset = 0) {
-    cdm_ctx *ctx = NULL;
-    const char *dev = getenv("CARPEDEAM_DEVICE");
-    check(cdm_ctx_create((dev ? atoi(dev) : 0) + offset, &ctx), "Can not initialise the MI355X device");
-    return ctx;
 }
 // ---- ancient_reads_loop --gpus N: the ranks are host threads of this process, one device each, and the library splits the read
 // iterations over them (cdm_reads_iteration_dist, csrc/dist.hip) - over RCCL.  CDM_LOOP_TRANSPORT=threads (tests on a one-GPU box,
@@ -331,14 +279,6 @@ struct DeviceStart {
         if (code) { fprintf(stderr, "%s\n", err.c_str()); exit(code); }
     }
 };
-cdm_seqdb *uploadSeqDb(cdm_ctx *ctx, const MmDb &db) {
-    if ((db.dbtype & 0x7FFFFFFF) != 1) unsupported("The MI355X path works on nucleotide sequence DBs only (dbtype " + std::to_string(db.dbtype & 0x7FFFFFFF) + " given)");
-    std::vector<uint32_t> lens(db.size());
-    for (size_t i = 0; i < db.size(); i++) lens[i] = db.len[i] >= 2 ? (uint32_t) (db.len[i] - 2) : 0;   // DBReader::getSeqLen
-    cdm_seqdb *h = NULL;
-    check(cdm_seqdb_upload(ctx, db.data(), db.off.data(), lens.data(), db.key.data(), db.ext.data(), db.size(), &h), "Can not load the sequence DB");
-    return h;
-}
 // the entries of a device DB as DB payloads ("SEQ\n"), appended to c
 void appendEntries(cdm_ctx *ctx, cdm_seqdb *h, OutChunk &c) {
     const uint64_t n = cdm_seqdb_size(h);
@@ -405,19 +345,6 @@ bool streamSeqDb(cdm_ctx *ctx, cdm_seqdb *h, const std::string &path, int dbtype
 }
 void writeSeqDb(cdm_ctx *ctx, cdm_seqdb *h, const std::string &path, int dbtype) { if (streamSeqDb(ctx, h, path, dbtype)) return; SeqDbOut o; o.down(ctx, h); o.write(path, dbtype); }
 // ---- text codecs
-// decimal text, two digits per division
-char *utoa(unsigned long long v, char *p) {
-    static const char D2[] = "0001020304050607080910111213141516171819202122232425262728293031323334353637383940414243444546474849"
-                             "5051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
-    if (v < 10) { *p++ = (char) ('0' + v); return p; }
-    if (v < 100) { memcpy(p, D2 + 2 * v, 2); return p + 2; }
-    char b[24]; int n = 24;
-    while (v >= 100) { const unsigned r = (unsigned) (v % 100); v /= 100; n -= 2; memcpy(b + n, D2 + 2 * r, 2); }
-    if (v >= 10) { n -= 2; memcpy(b + n, D2 + 2 * v, 2); } else b[--n] = (char) ('0' + v);
-    memcpy(p, b + n, (size_t) (24 - n));
-    return p + (24 - n);
-}
-char *itoa(long long v, char *p) { if (v < 0) { *p++ = '-'; return utoa((unsigned long long) -v, p); } return utoa(v, p); }
 // ---- parsers for the tab-separated records (strtol / strtod walk the locale machinery: 10x the time of these)
 // unsigned / signed decimal at d; d moves behind the digits (no digits: 0, as strtol gives)
 inline unsigned long parseU(const char *&d) { unsigned long v = 0; while (*d >= '0' && *d <= '9') v = v * 10 + (unsigned long) (*d++ - '0'); return v; }
@@ -1245,750 +1172,6 @@ void concatByKey(const OutChunk &all, const OutChunk &cyclic, OutChunk &merged) 
         merged.add(o.first, c.data.data() + (&c == &all ? offA[i] : offC[i]), c.len[i] - 1, c.ext[i]);
     }
 }
-// ---- contig_damage: per-contig coverage and damage tables from the read pile-up (not a module of the reference).  The contigs and
-// the reads become one DB (contigs first, wasExtended 1; reads behind them, 0), kmermatcher and rescorediagonal run on it with the reads
-// loop's flags, and cdm_pileup_profile counts, per contig, the overlaps of the reads that seed on it: coverage by seeded UNGAPPED
-// overlaps at the identity threshold, not a gapped mapping; a read counts on the longest sequence of each k-mer group it falls into
-// (kmermatcher's representative rule), possibly on several contigs.  One TSV line per contig, integers only.
-bool writeText(const std::string &path, const std::string &text);
-const FlagSpec DAMAGE_FLAGS[] = {{"--damage-ends", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-// an integer flag with the values the device path takes: lo to hi, or the module refuses it with `what`
-long rangedFlag(Args &a, const char *module, const char *flag, long dflt, long lo, long hi, const char *what) {
-    const long v = iflag(a, flag, dflt);
-    if (v < lo || v > hi) unsupported(std::string(module) + ": " + flag + " " + a.flag[flag] + " is not supported by the MI355X path (" + what + ")");
-    return v;
-}
-long damageEnds(Args &a, const char *module) { return rangedFlag(a, module, "--damage-ends", 16, 1, 64, "the tables hold 1 to 64 positions from either end of a read"); }
-// a tab and an integer behind a TSV line
-void put(std::string &to, unsigned long long v) { char num[32]; to.push_back('\t'); to.append(num, (size_t) (utoa(v, num) - num)); }
-// a set of sequences on the device with the names and keys its TSV lines carry
-struct DamageInput { cdm_seqdb *db = NULL; std::vector<std::string> names; std::vector<uint32_t> keys; };
-// path: a sequence DB (names from its header DB where it has one) or FASTA/FASTQ[.gz] (shuffle: createdb's order, as the loop lays its
-// reads out).  false: the input holds no sequence.
-bool loadDamageInput(cdm_ctx *ctx, const std::string &path, bool shuffle, bool wantNames, DamageInput &in) {
-    struct stat st; std::string err;
-    if (stat((path + ".index").c_str(), &st) == 0) {
-        MmDb seq; if (!seq.load(path, &err)) die(err);
-        if (seq.size() == 0) return false;
-        in.db = uploadSeqDb(ctx, seq);
-        in.keys.assign(seq.key.begin(), seq.key.end());
-        if (wantNames) {
-            MmDb hdr;
-            const bool haveHdr = stat((path + "_h.index").c_str(), &st) == 0 && hdr.load(path + "_h", &err);
-            in.names.resize(seq.size());
-            for (size_t i = 0; i < seq.size(); i++) {
-                const int64_t h = haveHdr ? hdr.idOf(seq.key[i]) : -1;
-                if (h >= 0) { const char *p = hdr.entry((size_t) h); size_t l = 0; while (l + 1 < hdr.len[(size_t) h] && p[l] && !isspace((unsigned char) p[l])) l++; in.names[i].assign(p, l); }
-                if (in.names[i].empty()) in.names[i] = std::to_string(seq.key[i]);
-            }
-        }
-        return true;
-    }
-    if (stat(path.c_str(), &st) != 0) die("Cannot open " + path);
-    if (st.st_size == 0) return false;
-    FastxDb fx;
-    if (!readFastxNamed(std::vector<std::string>(1, path), shuffle, fx, wantNames ? &in.names : NULL, &err)) die(err);
-    for (auto &l : fx.len) l -= 2;
-    check(cdm_seqdb_upload(ctx, fx.blob.data(), fx.off.data(), fx.len.data(), fx.key.data(), NULL, fx.key.size(), &in.db), "Can not load the sequences");
-    in.keys.assign(fx.key.begin(), fx.key.end());
-    for (size_t i = 0; i < in.names.size(); i++) if (in.names[i].empty()) in.names[i] = std::to_string(in.keys[i]);
-    return true;
-}
-// The three library calls the pile-up reports share: the contigs (wasExtended 1) and the reads (0) as one DB, kmermatcher and
-// rescorediagonal on it with the reads loop's flags.  The caller frees both results.
-// keepHits: the prefilter hits stay in the set (the gapped map looks at the ones rescorediagonal refused).
-struct PileSet { cdm_seqdb *both = NULL; cdm_alns *alns = NULL; cdm_hits *hits = NULL; };
-PileSet pileupAlignments(cdm_ctx *ctx, cdm_seqdb *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, bool keepHits = false) {
-    PileSet p; cdm_hits *hits = NULL;
-    check(cdm_seqdb_concat(ctx, contigs, reads, 1, 0, &p.both), "contigs and reads as one DB");
-    cdm_kmer_params kp;         // the reads loop's kmermatcher flags (stageflags.K_FLAGS)
-    kp.kmer_size = kmerSize; kp.kmers_per_seq = 200; kp.kmers_per_seq_scale = 0.2f; kp.hash_shift = 67; kp.ignore_multi_kmer = 1; kp.include_only_extendable = 0; kp.cov_mode = 1; kp.cov_thr = 0.0f;
-    cdm_rescore_params rp;      // its rescorediagonal flags (R_FLAGS)
-    rp.seq_id_thr = minSeqId; rp.eval_thr = 0.001; rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
-    check(cdm_kmermatch(ctx, p.both, &kp, &hits), "kmermatcher");
-    check(cdm_rescore(ctx, p.both, hits, &rp, &p.alns), "rescorediagonal");
-    if (keepHits) p.hits = hits; else cdm_hits_free(hits);
-    return p;
-}
-void freePileSet(PileSet &p) { if (p.hits) cdm_hits_free(p.hits); if (p.alns) cdm_alns_free(p.alns); if (p.both) cdm_seqdb_free(p.both); p = PileSet(); }
-// --gapped 0|1 with --gap-band and --gap-min-columns, as contig_map, contig_depth, contig_variants and contig_breaks take them: the
-// reads rescued across insertions and deletions (cdm_pileup_gapped) beside the ungapped overlaps.  whatGapped: what 0 and 1 mean to
-// the module.  Either --gap-* flag without --gapped 1 is refused: it sets an alignment that is off.
-struct GapOpts { bool on = false; long band = 8, minColumns = 32; float minSeqId = 0.9f; };
-GapOpts gapOpts(Args &a, const char *module, const char *whatGapped) {
-    GapOpts g;
-    g.on = rangedFlag(a, module, "--gapped", 0, 0, 1, whatGapped) != 0;
-    for (const char *flag : {"--gap-band", "--gap-min-columns"})
-        if (!g.on && a.flag.count(flag)) unsupported(std::string(module) + ": " + flag + " without --gapped 1 is not supported by the MI355X path (the flag sets the gapped alignment, which is off)");
-    g.band = rangedFlag(a, module, "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
-    g.minColumns = rangedFlag(a, module, "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
-    g.minSeqId = fflag(a, "--min-seq-id", 0.9f);
-    return g;
-}
-const char *const TABLE_GAPPED = "0 counts the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions";
-// The rescued reads of a PileSet that kept its hits, for the *_gapped reductions: cdm_pileup_gapped over the listed contigs with
-// contig_map's scores and gap costs (nucleotide.out's scores, the gap costs of `align`).  The arrays are released with cdm_gap_free.
-struct Rescued { cdm_gap_rec *recs = NULL; uint32_t *ops = NULL, *words = NULL; uint64_t n = 0, nOps = 0, nWords = 0, candidates = 0; float ms = 0.f; };
-void rescueReads(cdm_ctx *ctx, const PileSet &ps, const std::vector<uint32_t> &q, const GapOpts &g, Rescued &r) {
-    cdm_gap_params gp;
-    gp.min_seq_id = 0.0f; gp.skip_extended_targets = 1; gp.band = (uint32_t) g.band; gp.min_columns = (uint32_t) g.minColumns;
-    gp.min_id_permille = (uint32_t) (g.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
-    std::vector<uint64_t> gstats(q.size() * 4);
-    check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), q.size(), &gp, gstats.data(), &r.recs, &r.n, &r.ops, &r.nOps, &r.words, &r.nWords, &r.ms), "gapped pile-up");
-    for (size_t i = 0; i < q.size(); i++) r.candidates += gstats[i * 4];
-}
-bool haveContigs(const DamageInput *contigs) { return contigs && contigs->db && cdm_seqdb_size(contigs->db); }
-const std::string &contigName(const DamageInput &c, uint64_t i, std::string &tmp) { if (i < c.names.size()) return c.names[i]; tmp = std::to_string(c.keys[i]); return tmp; }
-// bedGraph lines of one contig's runs of equal value, zero runs included: name, start, end (0-based, half-open), value
-void bedGraphRuns(std::string &to, const std::string &name, const uint32_t *d, uint32_t len) {
-    for (uint32_t start = 0, p = 1; p <= len; p++)
-        if (p == len || d[p] != d[start]) { to += name; put(to, start); put(to, p); put(to, d[start]); to.push_back('\n'); start = p; }
-}
-// the contigs' own bytes (raw plane included): contig i from at[i], lens[i] + 1 bytes
-std::string contigLetters(cdm_ctx *ctx, const DamageInput &contigs, const std::vector<uint32_t> &lens, std::vector<uint64_t> &at) {
-    at.assign(lens.size() + 1, 0);
-    for (size_t i = 0; i < lens.size(); i++) at[i + 1] = at[i] + lens[i] + 1ull;
-    std::string letters(at.back(), '\0');
-    check(cdm_seqdb_download(ctx, contigs.db, &letters[0], at.data()), "download of the contigs");
-    return letters;
-}
-// the damage TSV from the alignments of a PileSet; no contigs: the header line alone
-void damageTable(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, long ends, const std::string &outPath, Laps &laps) {
-    std::string text = "name\tkey\tlength\treads\tcolumns";
-    for (long d = 1; d <= ends; d++) { const std::string n = std::to_string(d); text += "\t5p_C_" + n + "\t5p_CT_" + n + "\t3p_G_" + n + "\t3p_GA_" + n; }
-    text += "\n";
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> q(nc), lens(nc);
-        std::iota(q.begin(), q.end(), 0u);
-        const size_t cells = (size_t) 2 * (size_t) ends * 16;
-        std::vector<uint64_t> counts(nc * cells), nReads(nc), nCols(nc);
-        cdm_pileup_params pp; pp.ends = (int32_t) ends; pp.min_seq_id = 0.0f; pp.skip_extended_targets = 1;
-        check(cdm_pileup_profile(ctx, ps.both, ps.alns, q.data(), nc, &pp, counts.data(), nReads.data(), nCols.data()), "pile-up profile");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  damage report: %llu records, pile-up kernel %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 16));
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        std::string tmp;
-        for (uint64_t i = 0; i < nc; i++) {
-            text += contigName(*contigs, i, tmp);
-            put(text, contigs->keys[i]); put(text, lens[i]); put(text, nReads[i]); put(text, nCols[i]);
-            const uint64_t *c5 = counts.data() + i * cells, *c3 = c5 + (size_t) ends * 16;
-            for (long d = 0; d < ends; d++) {       // [d][x][y], A,C,G,T = 0..3: C under any read base / under T; G under any / under A
-                const uint64_t *c = c5 + d * 16 + 1 * 4, *g = c3 + d * 16 + 2 * 4;
-                put(text, c[0] + c[1] + c[2] + c[3]); put(text, c[3]); put(text, g[0] + g[1] + g[2] + g[3]); put(text, g[0]);
-            }
-            text.push_back('\n');
-        }
-        laps.lap("damage report: pile-up, table");
-    }
-    if (!writeText(outPath, text)) die("Could not write " + outPath);
-}
-// ---- contig_depth: per-contig depth, breadth and depth variance from the same pile-up (not a module of the reference).  Per read set
-// the three calls above, then cdm_pileup_depth over the contigs: as with the damage tables, coverage by seeded UNGAPPED overlaps at the
-// identity threshold, not a gapped mapping.  One TSV line per contig, integers only: the caller divides (mean = sum / window,
-// variance = (sumsq - sum^2 / window) / (window - 1)).  --gapped 1 (here, in contig_variants and in contig_breaks): the set keeps its
-// hits, cdm_pileup_gapped rescues the reads across insertions and deletions, and the *_gapped reduction counts them as well.
-const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-long depthEdge(Args &a, const char *module) { return rangedFlag(a, module, "--depth-edge", 0, 0, 1048576, "0 to 1048576 positions are left out at either end of a contig"); }
-// one read set's statistics (nc x 8) and, when asked for, the depth of every contig position back to back
-// gap (--gapped 1; the set kept its hits): the rescued reads count as well
-void depthSample(cdm_ctx *ctx, const DamageInput &contigs, const PileSet &ps, long edge, std::vector<uint64_t> &stats, std::vector<uint32_t> *track, const GapOpts *gap = NULL) {
-    const uint64_t nc = cdm_seqdb_size(contigs.db);
-    std::vector<uint32_t> q(nc);
-    std::iota(q.begin(), q.end(), 0u);
-    stats.assign(nc * 8, 0);
-    if (track) track->assign(cdm_seqdb_residues(contigs.db) + 1, 0);
-    cdm_depth_params dp; dp.edge = (int32_t) edge; dp.min_seq_id = 0.0f; dp.skip_extended_targets = 1;
-    if (gap && gap->on) {
-        Rescued r; float ms = 0.f;
-        rescueReads(ctx, ps, q, *gap, r);
-        check(cdm_pileup_depth_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &dp, stats.data(), track ? track->data() : NULL, &ms), "pile-up depth");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  depth report: %llu records, %llu candidates, %llu rescued, gapped kernels %.3f ms, depth kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
-                                          (unsigned long long) r.candidates, (unsigned long long) r.n, r.ms, ms);
-        cdm_gap_free(r.recs, r.ops, r.words);
-        return;
-    }
-    check(cdm_pileup_depth(ctx, ps.both, ps.alns, q.data(), nc, &dp, stats.data(), track ? track->data() : NULL), "pile-up depth");
-    if (getenv("CDM_TIMING")) fprintf(stderr, "  depth report: %llu records, depth kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), cdm_ctx_last_kernel_ms(ctx, 17));
-}
-// the depth TSV of `samples` read sets; no contigs: the header line alone
-void depthTable(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<std::vector<uint64_t>> &stats, size_t samples, const std::string &outPath) {
-    std::string text = "name\tkey\tlength\twindow";
-    static const char *const COLS[7] = {"reads", "columns", "breadth", "covered", "sum", "sumsq", "max"};
-    static const int AT[7] = {0, 1, 2, 4, 5, 6, 7};
-    for (size_t s = 1; s <= samples; s++) for (const char *c : COLS) text += std::string("\t") + c + "_" + std::to_string(s);
-    text += "\n";
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> lens(nc);
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        std::string tmp;
-        for (uint64_t i = 0; i < nc; i++) {
-            text += contigName(*contigs, i, tmp);
-            put(text, contigs->keys[i]); put(text, lens[i]); put(text, stats[0][i * 8 + 3]);
-            for (size_t s = 0; s < samples; s++) for (int c : AT) put(text, stats[s][i * 8 + c]);
-            text.push_back('\n');
-        }
-    }
-    if (!writeText(outPath, text)) die("Could not write " + outPath);
-}
-// bedGraph of the runs of equal depth
-void depthTrackFile(cdm_ctx *ctx, const DamageInput *contigs, const std::vector<uint32_t> &track, const std::string &outPath) {
-    std::string text;
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> lens(nc);
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        std::string tmp;
-        uint64_t at = 0;
-        for (uint64_t i = 0; i < nc; at += lens[i], i++) bedGraphRuns(text, contigName(*contigs, i, tmp), track.data() + at, lens[i]);
-    }
-    if (!writeText(outPath, text)) die("Could not write " + outPath);
-}
-// ---- contig_variants: per-position base counts and variant sites from the same pile-up (not a module of the reference).  The three
-// calls above, then cdm_pileup_bases over the contigs: one summary line per contig, with --sites one line per position where the reads
-// disagree with the contig (D) or among themselves (V), with --consensus the contigs with the reads' majority letter at the D
-// positions.  As with the other two reports the pile-up is seeded UNGAPPED overlaps at the identity threshold: no indels, and no call
-// where no read seeds.  Integers only.
-const FlagSpec VARIANT_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0}, {"--sites", 'U', 0, 0},
-                                  {"--consensus", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0},
-                                  {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-struct VariantOpts { long maskEnds, minDepth, minAltCount, minAltPercent; };
-VariantOpts variantOpts(Args &a, const char *module) {
-    VariantOpts o;
-    o.maskEnds = rangedFlag(a, module, "--mask-ends", 0, 0, 64, "0 to 64 read positions are left out at either end of a read");
-    o.minDepth = rangedFlag(a, module, "--min-depth", 3, 1, 1000000, "a called position has 1 to 1000000 bases");
-    o.minAltCount = rangedFlag(a, module, "--min-alt-count", 2, 1, 1000000, "a second allele has 1 to 1000000 bases");
-    o.minAltPercent = rangedFlag(a, module, "--min-alt-percent", 20, 0, 100, "a percentage of the depth is 0 to 100");
-    return o;
-}
-// what a variant report writes: the summary always, the other two files when named
-struct VariantOut { VariantOpts opt; const std::string *summary, *sites, *consensus; GapOpts gap; };       // gap.on: the rescued reads count as well (the set kept its hits)
-// no contigs: the summary's header line alone, an empty sites file, an empty FASTA
-void variantReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const VariantOut &v, Laps &laps) {
-    std::string text = "name\tkey\tlength\treads\tcolumns\tbases\tmismatches\tcalled\tdiffers\tvariable\n", sitesText, fasta;
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> q(nc), lens(nc);
-        std::iota(q.begin(), q.end(), 0u);
-        std::vector<uint64_t> stats(nc * 8);
-        cdm_bases_params bp; bp.mask_ends = (int32_t) v.opt.maskEnds; bp.min_depth = (int32_t) v.opt.minDepth; bp.min_alt_count = (int32_t) v.opt.minAltCount;
-        bp.min_alt_percent = (int32_t) v.opt.minAltPercent; bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
-        const bool wantSites = v.sites || v.consensus;
-        cdm_site *sites = NULL; uint64_t nSites = 0; float ms = 0.f;
-        if (v.gap.on) {
-            Rescued r;
-            rescueReads(ctx, ps, q, v.gap, r);
-            check(cdm_pileup_bases_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
-            if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu candidates, %llu rescued, %llu sites, gapped kernels %.3f ms, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
-                                              (unsigned long long) r.candidates, (unsigned long long) r.n, (unsigned long long) nSites, r.ms, ms);
-            cdm_gap_free(r.recs, r.ops, r.words);
-        } else {
-            check(cdm_pileup_bases(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), NULL, wantSites ? &sites : NULL, wantSites ? &nSites : NULL, &ms), "pile-up base counts");
-            if (getenv("CDM_TIMING")) fprintf(stderr, "  variant report: %llu records, %llu sites, base count kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nSites, ms);
-        }
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        std::string tmp;
-        for (uint64_t i = 0; i < nc; i++) {
-            text += contigName(*contigs, i, tmp);
-            put(text, contigs->keys[i]); put(text, lens[i]);
-            for (int c = 0; c < 7; c++) put(text, stats[i * 8 + c]);
-            text.push_back('\n');
-        }
-        static const char LETTER[] = "ACGTN";
-        if (v.sites)
-            for (uint64_t k = 0; k < nSites; k++) {     // name, pos (1-based), ref, major, flags, depth, forward A C G T, reverse a c g t
-                const cdm_site &st = sites[k];
-                const uint32_t fl = st.info >> 8;
-                sitesText += contigName(*contigs, st.query, tmp);
-                put(sitesText, (unsigned long long) st.pos + 1);
-                sitesText.push_back('\t'); sitesText.push_back(LETTER[st.info & 15u]);
-                sitesText.push_back('\t'); sitesText.push_back(LETTER[(st.info >> 4) & 15u]);
-                sitesText.push_back('\t'); if (fl & CDM_SITE_DIFFERS) sitesText.push_back('D'); if (fl & CDM_SITE_VARIABLE) sitesText.push_back('V');
-                unsigned long long d = 0; for (uint32_t c : st.counts) d += c;
-                put(sitesText, d);
-                for (uint32_t c : st.counts) put(sitesText, c);
-                sitesText.push_back('\n');
-            }
-        if (v.consensus) {      // the contigs' own bytes, the reads' majority letter at the D positions
-            std::vector<uint64_t> at;
-            std::string letters = contigLetters(ctx, *contigs, lens, at);
-            for (uint64_t k = 0; k < nSites; k++)
-                if ((sites[k].info >> 8) & CDM_SITE_DIFFERS) letters[at[sites[k].query] + sites[k].pos] = LETTER[(sites[k].info >> 4) & 15u];
-            for (uint64_t i = 0; i < nc; i++) { fasta.push_back('>'); fasta += contigName(*contigs, i, tmp); fasta.push_back('\n'); fasta.append(letters, at[i], lens[i] + 1ull); }
-        }
-        cdm_sites_free(sites);
-        laps.lap("variant report: base counts, tables");
-    }
-    if (!writeText(*v.summary, text)) die("Could not write " + *v.summary);
-    if (v.sites && !writeText(*v.sites, sitesText)) die("Could not write " + *v.sites);
-    if (v.consensus && !writeText(*v.consensus, fasta)) die("Could not write " + *v.consensus);
-}
-// ---- contig_breaks: contig break points from spanning reads of the same pile-up (not a module of the reference).  The three calls
-// above, then cdm_pileup_breaks over the contigs: one summary line per contig and, behind it, one `#break` line per run of boundaries
-// that too few reads span with --break-anchor columns on either side (J: the reads cover the stretch and none spans it - the
-// signature of a chimeric join; G: a stretch without reads); with --split the contigs cut at their breaks, with --span-track the
-// spanning coverage of every boundary.  As with the other three reports the pile-up is seeded UNGAPPED overlaps at the identity
-// threshold: reads shorter than twice the anchor span nothing, and there is no break call where no read seeds.  Integers only.
-const FlagSpec BREAK_FLAGS[] = {{"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0}, {"--split", 'U', 0, 0},
-                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-struct BreakOpts { long anchor, edge, minSpan, minSpanPercent; };
-// The default anchor is reasoned, not measured: a read with w columns beyond a false join expects 0.75 w mismatches there, and at the
-// identity threshold t a read of L columns is dropped when 0.75 w > (1 - t) L; w = 16 covers L <= 120 at t = 0.9.
-BreakOpts breakOpts(Args &a, const char *module) {
-    BreakOpts o;
-    o.anchor = rangedFlag(a, module, "--break-anchor", 16, 1, 1024, "a spanning read has 1 to 1024 columns on either side of a boundary");
-    o.edge = rangedFlag(a, module, "--break-edge", 50, 1, 1048576, "1 to 1048576 boundaries are left out at either end of a contig");
-    if (o.edge < o.anchor) unsupported(std::string(module) + ": --break-edge " + std::to_string(o.edge) + " is not supported by the MI355X path (it is --break-anchor, here " + std::to_string(o.anchor) +
-                                       ", at the least: nearer to a contig's end no read has its anchor on both sides)");
-    o.minSpan = rangedFlag(a, module, "--min-span", 1, 1, 1000000, "a boundary is held by 1 to 1000000 spanning reads");
-    o.minSpanPercent = rangedFlag(a, module, "--min-span-percent", 0, 0, 100, "a percentage of the depth is 0 to 100");
-    return o;
-}
-// what a break report writes: the summary always, the other two files when named
-struct BreakOut { BreakOpts opt; long minPiece; const std::string *summary, *split, *track; GapOpts gap; };      // gap.on: the rescued reads count as well (the set kept its hits)
-// no contigs: the summary's header line alone, an empty FASTA, an empty track
-void breakReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const BreakOut &o, Laps &laps) {
-    std::string text = "name\tkey\tlength\treads\tcolumns\twindow\tweak\tbreaks\tjoins\tmin_span\tsum_span\n", fasta, bed;
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> q(nc), lens(nc), track;
-        std::iota(q.begin(), q.end(), 0u);
-        std::vector<uint64_t> stats(nc * 8);
-        if (o.track) track.assign(cdm_seqdb_residues(contigs->db) + 1, 0);
-        cdm_breaks_params bp; bp.anchor = (int32_t) o.opt.anchor; bp.edge = (int32_t) o.opt.edge; bp.min_span = (int32_t) o.opt.minSpan; bp.min_span_percent = (int32_t) o.opt.minSpanPercent;
-        bp.min_seq_id = 0.0f; bp.skip_extended_targets = 1;
-        cdm_break *br = NULL; uint64_t nBr = 0; float ms = 0.f;
-        if (o.gap.on) {
-            Rescued r;
-            rescueReads(ctx, ps, q, o.gap, r);
-            check(cdm_pileup_breaks_gapped(ctx, ps.both, ps.alns, q.data(), nc, r.recs, r.n, r.ops, r.nOps, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
-            if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu candidates, %llu rescued, %llu breaks, gapped kernels %.3f ms, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
-                                              (unsigned long long) r.candidates, (unsigned long long) r.n, (unsigned long long) nBr, r.ms, ms);
-            cdm_gap_free(r.recs, r.ops, r.words);
-        } else {
-            check(cdm_pileup_breaks(ctx, ps.both, ps.alns, q.data(), nc, &bp, stats.data(), o.track ? track.data() : NULL, &br, &nBr, &ms), "pile-up break points");
-            if (getenv("CDM_TIMING")) fprintf(stderr, "  break report: %llu records, %llu breaks, break point kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nBr, ms);
-        }
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        std::string tmp, letters;
-        std::vector<uint64_t> at;
-        if (o.split) letters = contigLetters(ctx, *contigs, lens, at);
-        uint64_t k = 0, trackAt = 0;
-        for (uint64_t i = 0; i < nc; trackAt += lens[i], i++) {
-            const std::string &name = contigName(*contigs, i, tmp);
-            text += name;
-            put(text, contigs->keys[i]); put(text, lens[i]);
-            for (int c = 0; c < 8; c++) put(text, stats[i * 8 + c]);
-            text.push_back('\n');
-            const uint64_t k0 = k;
-            for (; k < nBr && br[k].query == i; k++) {      // 1-based boundaries
-                const cdm_break &b = br[k];
-                text += "#break\t"; text += name;
-                put(text, (unsigned long long) b.first + 1); put(text, (unsigned long long) b.last + 1); put(text, b.min_span); put(text, b.uncovered); put(text, b.depth_left); put(text, b.depth_right);
-                text.push_back('\t'); text.push_back(b.flags & CDM_BREAK_GAP ? 'G' : 'J'); text.push_back('\n');
-            }
-            if (o.split) {      // a piece ends at position first - 1, the next begins at position last: the letters between, which no read spans, are dropped
-                uint64_t from = 0, piece = 0;
-                for (uint64_t j = k0; j <= k; j++) {
-                    const uint64_t to = j < k ? br[j].first : lens[i];
-                    piece++;
-                    if (to - from >= (uint64_t) o.minPiece) {
-                        fasta.push_back('>'); fasta += name;
-                        if (k > k0) { fasta.push_back('_'); fasta += std::to_string(piece); }
-                        fasta.push_back('\n'); fasta.append(letters, at[i] + from, to - from); fasta.push_back('\n');
-                    }
-                    if (j < k) from = br[j].last;
-                }
-            }
-            if (o.track) bedGraphRuns(bed, name, track.data() + trackAt, lens[i]);      // the runs of equal span
-        }
-        cdm_breaks_free(br);
-        laps.lap("break report: break points, tables");
-    }
-    if (!writeText(*o.summary, text)) die("Could not write " + *o.summary);
-    if (o.split && !writeText(*o.split, fasta)) die("Could not write " + *o.split);
-    if (o.track && !writeText(*o.track, bed)) die("Could not write " + *o.track);
-}
-// ---- contig_map: the reads on the contigs as a SAM file (not a module of the reference).  The three calls above, then cdm_pileup_map
-// over the contigs: one line per counted record in coordinate order, soft clips around the overlap, NM and MD from the mismatch
-// words, one primary line per read.  SEQ is the read as the device compared it - the letters its codes and N bits stand for - so SEQ,
-// CIGAR and MD agree by construction.  As with the four reports the records are seeded UNGAPPED overlaps at the identity threshold:
-// no insertions or deletions, no line for a read that seeds nowhere.  --gapped 1 adds the seeded pairs that test refused: cdm_pileup_gapped
-// aligns them across insertions and deletions within a band, and the rescued reads come as lines of their own (CIGAR with I and D, MD
-// with ^, a trailing XG:i:<gap letters>), merged into the others by (contig, position), the ungapped line first on equal keys.
-const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-// what a map report writes: the SAM file, with the read group when one is named, without the secondary lines when asked
-struct MapOut { const std::string *sam; const std::string *readGroup; bool primaryOnly; bool gapped = false; long gapBand = 8, gapMinColumns = 32; float minSeqId = 0.9f; };
-// SAM names a reference sequence once: two contigs of one name end the command
-void mapCheckNames(const DamageInput &contigs) {
-    std::vector<std::string> names; std::string tmp;
-    for (uint64_t i = 0; i < contigs.keys.size(); i++) names.push_back(contigName(contigs, i, tmp));
-    std::sort(names.begin(), names.end());
-    for (size_t i = 1; i < names.size(); i++)
-        if (names[i] == names[i - 1]) die("contig_map: two contigs are named " + names[i] + "; a SAM file can not tell them apart");
-}
-void putNumber(std::string &to, unsigned long long v) { char num[32]; to.append(num, (size_t) (utoa(v, num) - num)); }
-// no contigs: the header lines without @SQ
-void mapReport(cdm_ctx *ctx, const DamageInput *contigs, const DamageInput *reads, const PileSet &ps, const MapOut &o, Laps &laps) {
-    std::string text = "@HD\tVN:1.6\tSO:coordinate\n", tmp;
-    std::vector<uint32_t> lens;
-    std::vector<std::string> part;        // the record lines, a chunk a host thread
-    const uint64_t nc = haveContigs(contigs) ? cdm_seqdb_size(contigs->db) : 0;
-    if (nc) {
-        lens.resize(nc);
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        for (uint64_t i = 0; i < nc; i++) { text += "@SQ\tSN:"; text += contigName(*contigs, i, tmp); text += "\tLN:"; putNumber(text, lens[i]); text.push_back('\n'); }
-    }
-    if (o.readGroup) text += "@RG\tID:" + *o.readGroup + "\n";
-    text += "@PG\tID:carpedeam\tPN:carpedeam\n";
-    if (nc) {
-        std::vector<uint32_t> q(nc);
-        std::iota(q.begin(), q.end(), 0u);
-        std::vector<uint64_t> stats(nc * 4);
-        cdm_map_params mp; mp.min_seq_id = 0.0f; mp.skip_extended_targets = 1;
-        cdm_map_rec *recs = NULL; uint32_t *mism = NULL; uint64_t nRecs = 0, nMism = 0; float ms = 0.f;
-        check(cdm_pileup_map(ctx, ps.both, ps.alns, q.data(), nc, &mp, stats.data(), &recs, &nRecs, &mism, &nMism, &ms), "pile-up map");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  map report: %llu records, %llu lines, %llu mismatches, map kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nRecs, (unsigned long long) nMism, ms);
-        // --gapped 1: the rescued reads, and the order of the two streams merged by (contig, pos), an ungapped record first on equal keys
-        // (entry: index << 1 | rescued)
-        cdm_gap_rec *grecs = NULL; uint32_t *gops = NULL, *gwords = NULL; uint64_t nGap = 0, nGops = 0, nGwords = 0;
-        std::vector<uint64_t> merged;
-        if (o.gapped) {
-            cdm_gap_params gp;        // nucleotide.out's scores and the gap costs of `align`
-            gp.min_seq_id = mp.min_seq_id; gp.skip_extended_targets = mp.skip_extended_targets; gp.band = (uint32_t) o.gapBand; gp.min_columns = (uint32_t) o.gapMinColumns;
-            gp.min_id_permille = (uint32_t) (o.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
-            std::vector<uint64_t> gstats(nc * 4);
-            float gms = 0.f;
-            check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), nc, &gp, gstats.data(), &grecs, &nGap, &gops, &nGops, &gwords, &nGwords, &gms), "gapped pile-up");
-            if (getenv("CDM_TIMING")) {
-                uint64_t cand = 0, gaps = 0;
-                for (uint64_t i = 0; i < nc; i++) { cand += gstats[i * 4]; gaps += gstats[i * 4 + 2]; }
-                fprintf(stderr, "  map report: %llu refused hits aligned, %llu rescued with %llu gap letters, gapped kernels %.3f ms\n", (unsigned long long) cand, (unsigned long long) nGap, (unsigned long long) gaps, gms);
-            }
-            merged.reserve(nRecs + nGap);
-            for (uint64_t i = 0, j = 0; i < nRecs || j < nGap;) {
-                const bool plain = j == nGap || (i < nRecs && (recs[i].query < grecs[j].query || (recs[i].query == grecs[j].query && recs[i].pos <= grecs[j].pos)));
-                merged.push_back(plain ? i++ << 1 : j++ << 1 | 1u);
-            }
-        }
-        const uint64_t nLines = nRecs + nGap;
-        // the reads as the device compared them: their packed codes and N bits come down, no byte of the input is looked at
-        const uint64_t nr = cdm_seqdb_size(reads->db), words = cdm_seqdb_words(reads->db);
-        std::vector<uint32_t> rlens(nr), codes(words + 1); std::vector<uint16_t> nbits(words + 1);
-        check(cdm_seqdb_export_packed(ctx, reads->db, codes.data(), nbits.data(), rlens.data(), NULL, NULL, NULL, NULL), "download of the reads");
-        std::vector<uint64_t> woff(nr + 1, 0);        // (every sequence starts on a word boundary: 16 letters a code word, 16 N bits beside it)
-        for (uint64_t i = 0; i < nr; i++) woff[i + 1] = woff[i] + (rlens[i] + 15u) / 16u;
-        // the lines on the host threads, in contiguous chunks of records
-        const int T = std::max(1, omp_get_max_threads());
-        part.resize((size_t) T);
-        static const char LETTER[] = "ACGTN";
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the chunks: a smaller team still visits them all
-        for (int t = 0; t < T; t++) {
-            std::string &to = part[(size_t) t]; std::string name;
-            // what the two kinds of line share: QNAME to MAPQ in front of CIGAR, and RNEXT to QUAL behind it
-            auto lineHead = [&](uint32_t target, uint32_t flags, uint32_t query, uint32_t pos) {
-                to += contigName(*reads, (uint64_t) target - nc, name);       // (reads only as targets: behind the contigs in the joint DB)
-                to.push_back('\t'); putNumber(to, (flags & CDM_MAP_REVERSE ? 16u : 0u) | (flags & CDM_MAP_SECONDARY ? 256u : 0u));
-                to.push_back('\t'); to += contigName(*contigs, query, name);
-                to.push_back('\t'); putNumber(to, (unsigned long long) pos + 1);
-                to += "\t255\t";
-            };
-            auto lineSeq = [&](uint32_t target, uint32_t tlen, bool rev) {
-                const uint64_t read = (uint64_t) target - nc;
-                to += "\t*\t0\t0\t";
-                const uint32_t *cw = codes.data() + woff[read]; const uint16_t *nw = nbits.data() + woff[read];
-                for (uint32_t i = 0; i < tlen; i++) {       // the read in the contig's orientation: complemented from its end when reverse
-                    const uint32_t p = rev ? tlen - 1u - i : i, b = (cw[p >> 4] >> ((p & 15u) * 2u)) & 3u;
-                    to.push_back((nw[p >> 4] >> (p & 15u)) & 1u ? 'N' : LETTER[rev ? 3u - b : b]);
-                }
-            };
-            for (uint64_t k = nLines * (uint64_t) t / (uint64_t) T, end = nLines * (uint64_t) (t + 1) / (uint64_t) T; k < end; k++) {
-                const uint64_t entry = o.gapped ? merged[k] : k << 1;
-                if (entry & 1u) {       // a rescued read: CIGAR from its operations, MD with ^ from its words, XG the gap letters
-                    const cdm_gap_rec &r = grecs[entry >> 1];
-                    if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
-                    lineHead(r.target, r.flags, r.query, r.pos);
-                    if (r.tstart) { putNumber(to, r.tstart); to.push_back('S'); }
-                    uint32_t gaps = 0;
-                    for (uint32_t j = 0; j < r.n_ops; j++) {
-                        const uint32_t w = gops[r.ops + j];
-                        putNumber(to, w >> 2); to.push_back("MID"[w & 3u]);
-                        if (w & 3u) gaps += w >> 2;
-                    }
-                    if (const uint32_t right = r.tlen - r.tstart - r.columns) { putNumber(to, right); to.push_back('S'); }
-                    lineSeq(r.target, r.tlen, (r.flags & CDM_MAP_REVERSE) != 0);
-                    to += "\t*\tNM:i:"; putNumber(to, r.nm);
-                    to += "\tMD:Z:";
-                    uint32_t from = 0; bool inDeletion = false;
-                    for (uint32_t j = 0; j < r.n_words; j++) {      // a deleted letter joins the ^ in front of it when it follows a deleted letter on the contig
-                        const uint32_t w = gwords[r.words + j], c = w & 0xFFFFFFu; const bool deleted = (w >> 28) == 15u;
-                        if (!(deleted && inDeletion && c == from)) { putNumber(to, c - from); if (deleted) to.push_back('^'); }
-                        to.push_back(LETTER[std::min(4u, (w >> 24) & 15u)]);
-                        from = c + 1u; inDeletion = deleted;
-                    }
-                    putNumber(to, r.span - from);
-                    if (o.readGroup) { to += "\tRG:Z:"; to += *o.readGroup; }
-                    to += "\tXG:i:"; putNumber(to, gaps);
-                    to.push_back('\n');
-                    continue;
-                }
-                const cdm_map_rec &r = recs[entry >> 1];
-                if (o.primaryOnly && (r.flags & CDM_MAP_SECONDARY)) continue;
-                lineHead(r.target, r.flags, r.query, r.pos);
-                const uint32_t right = r.tlen - r.tstart - r.columns;
-                if (r.tstart) { putNumber(to, r.tstart); to.push_back('S'); }
-                putNumber(to, r.columns); to.push_back('M');
-                if (right) { putNumber(to, right); to.push_back('S'); }
-                lineSeq(r.target, r.tlen, (r.flags & CDM_MAP_REVERSE) != 0);
-                to += "\t*\tNM:i:"; putNumber(to, r.nm);
-                to += "\tMD:Z:";
-                uint32_t from = 0;
-                for (uint32_t j = 0; j < r.nm; j++) {       // the matches in front of a mismatch, then the contig's letter there
-                    const uint32_t w = mism[r.mm + j], c = w & 0xFFFFFFu;
-                    putNumber(to, c - from); to.push_back(LETTER[std::min(4u, (w >> 24) & 15u)]);
-                    from = c + 1u;
-                }
-                putNumber(to, r.columns - from);
-                if (o.readGroup) { to += "\tRG:Z:"; to += *o.readGroup; }
-                to.push_back('\n');
-            }
-        }
-        cdm_gap_free(grecs, gops, gwords);
-        cdm_map_free(recs, mism);
-        laps.lap("map report: records, lines");
-    }
-    // the header, then the chunks in order: the text is never joined in memory
-    FILE *f = fopen(o.sam->c_str(), "w");
-    bool ok = f != NULL && fwrite(text.data(), 1, text.size(), f) == text.size();
-    for (size_t t = 0; ok && t < part.size(); t++) { ok = fwrite(part[t].data(), 1, part[t].size(), f) == part[t].size(); std::string().swap(part[t]); }
-    if (f && fclose(f) != 0) ok = false;
-    if (!ok) die("Could not write " + *o.sam);
-}
-// ---- contig_indels: insertion and deletion sites of the contigs and the contigs polished at them (not a module of the reference).
-// The chain of contig_map --gapped 1 - the three calls above, cdm_pileup_gapped with the command's scores and gap costs - then
-// cdm_pileup_indels over the contigs: one summary line per contig, with --sites one line per supported insertion or deletion (S) and
-// whether more than half of the crossing reads carry it (M), with --consensus the contigs with their M sites applied.  Substitutions
-// are not touched: contig_variants --consensus does those.  A read seeded twice on one contig counts twice, as it has two SAM lines.
-// The defaults are those of contig_variants' second allele, reasoned, not measured.  Integers only.
-const FlagSpec INDEL_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-indel-count", 'U', 0, 0}, {"--min-indel-percent", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0},
-                                {"--sites", 'U', 0, 0}, {"--consensus", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-// what an indel report writes: the summary always, the other two files when named
-struct IndelOut { long minDepth, minCount, minPercent, gapBand, gapMinColumns; float minSeqId; const std::string *summary, *sites, *consensus; };
-// no contigs: the summary's header line alone, an empty sites file, an empty FASTA
-void indelReport(cdm_ctx *ctx, const DamageInput *contigs, const PileSet &ps, const IndelOut &o, Laps &laps) {
-    std::string text = "name\tkey\tlength\treads\tcolumns\trescued\tinsertions\tdeletions\tinserted_letters\tdeleted_letters\tplaces\tsupported\tmajor\tapplied\tnew_length\n", sitesText, fasta;
-    if (haveContigs(contigs)) {
-        const uint64_t nc = cdm_seqdb_size(contigs->db);
-        std::vector<uint32_t> q(nc), lens(nc);
-        std::iota(q.begin(), q.end(), 0u);
-        cdm_gap_params gp;        // nucleotide.out's scores and the gap costs of `align`, as contig_map --gapped 1
-        gp.min_seq_id = 0.0f; gp.skip_extended_targets = 1; gp.band = (uint32_t) o.gapBand; gp.min_columns = (uint32_t) o.gapMinColumns;
-        gp.min_id_permille = (uint32_t) (o.minSeqId * 1000 + 0.5); gp.match = 2; gp.mismatch = -3; gp.gap_open = 5; gp.gap_extend = 2;
-        std::vector<uint64_t> gstats(nc * 4), stats(nc * 10);
-        cdm_gap_rec *grecs = NULL; uint32_t *gops = NULL, *gwords = NULL; uint64_t nGap = 0, nGops = 0, nGwords = 0; float gms = 0.f, ms = 0.f;
-        check(cdm_pileup_gapped(ctx, ps.both, ps.hits, ps.alns, q.data(), nc, &gp, gstats.data(), &grecs, &nGap, &gops, &nGops, &gwords, &nGwords, &gms), "gapped pile-up");
-        cdm_indel_params ip; ip.min_depth = (int32_t) o.minDepth; ip.min_count = (int32_t) o.minCount; ip.min_percent = (int32_t) o.minPercent; ip.min_seq_id = 0.0f; ip.skip_extended_targets = 1;
-        cdm_indel_site *sites = NULL; uint8_t *codes = NULL; uint64_t nSites = 0, nCodes = 0;
-        check(cdm_pileup_indels(ctx, ps.both, ps.alns, q.data(), nc, grecs, nGap, gops, nGops, &ip, stats.data(), NULL, &sites, &nSites, &codes, &nCodes, &ms), "pile-up indel sites");
-        if (getenv("CDM_TIMING")) fprintf(stderr, "  indel report: %llu records, %llu rescued, %llu sites, gapped kernels %.3f ms, indel kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns), (unsigned long long) nGap, (unsigned long long) nSites, gms, ms);
-        cdm_gap_free(grecs, gops, gwords);
-        check(cdm_seqdb_meta(ctx, contigs->db, lens.data(), NULL, NULL), "meta");
-        static const char LETTER[] = "ACGTN";
-        std::string tmp;
-        if (o.sites) {      // name, pos (1-based), kind, length, letters, count, cross, others, flags; a deletion shows the contig's letters as the device compared them
-            const uint64_t words = cdm_seqdb_words(contigs->db);
-            std::vector<uint32_t> cw(words + 1), clens(nc); std::vector<uint16_t> nw(words + 1); std::vector<uint64_t> woff(nc + 1, 0);
-            check(cdm_seqdb_export_packed(ctx, contigs->db, cw.data(), nw.data(), clens.data(), NULL, NULL, NULL, NULL), "download of the contigs' codes");
-            for (uint64_t i = 0; i < nc; i++) woff[i + 1] = woff[i] + (lens[i] + 15u) / 16u;
-            for (uint64_t k = 0; k < nSites; k++) {
-                const cdm_indel_site &st = sites[k];
-                const uint32_t kind = st.info & 15u, g = (st.info >> 4) & 0xFFFu, fl = st.info >> 16;
-                sitesText += contigName(*contigs, st.query, tmp);
-                put(sitesText, (unsigned long long) st.pos + 1);
-                sitesText.push_back('\t'); sitesText.push_back(kind == CDM_INDEL_INS ? 'I' : 'D');
-                put(sitesText, g);
-                sitesText.push_back('\t');
-                if (kind == CDM_INDEL_INS) for (uint32_t j = 0; j < st.n_letters; j++) sitesText.push_back(LETTER[std::min<uint32_t>(4u, codes[st.letters + j])]);
-                else for (uint32_t j = 0; j < g; j++) {
-                    const uint64_t p = (uint64_t) st.pos + j, w = woff[st.query] + (p >> 4);
-                    sitesText.push_back((nw[w] >> (p & 15u)) & 1u ? 'N' : LETTER[(cw[w] >> ((p & 15u) * 2u)) & 3u]);
-                }
-                put(sitesText, st.count); put(sitesText, st.cross); put(sitesText, st.others);
-                sitesText.push_back('\t'); sitesText.push_back('S'); if (fl & CDM_INDEL_MAJOR) sitesText.push_back('M');
-                sitesText.push_back('\n');
-            }
-        }
-        // the polished contigs: the M sites in site order behind a cursor; a site inside a stretch an earlier deletion removed is skipped
-        std::vector<uint64_t> at;
-        std::string letters;
-        if (o.consensus) letters = contigLetters(ctx, *contigs, lens, at);
-        uint64_t k = 0;
-        for (uint64_t i = 0; i < nc; i++) {
-            uint64_t next = 0, applied = 0, newLen = 0;
-            if (o.consensus) { fasta.push_back('>'); fasta += contigName(*contigs, i, tmp); fasta.push_back('\n'); }
-            for (; k < nSites && sites[k].query == i; k++) {
-                const cdm_indel_site &st = sites[k];
-                if (!((st.info >> 16) & CDM_INDEL_MAJOR) || st.pos < next) continue;
-                if (o.consensus) fasta.append(letters, at[i] + next, st.pos - next);
-                newLen += st.pos - next; applied++;
-                if ((st.info & 15u) == CDM_INDEL_INS) {
-                    if (o.consensus) for (uint32_t j = 0; j < st.n_letters; j++) fasta.push_back(LETTER[std::min<uint32_t>(4u, codes[st.letters + j])]);
-                    newLen += st.n_letters; next = st.pos;
-                } else next = (uint64_t) st.pos + ((st.info >> 4) & 0xFFFu);
-            }
-            if (o.consensus) fasta.append(letters, at[i] + next, lens[i] + 1ull - next);        // (with the byte that ends the contig)
-            newLen += lens[i] - next;
-            text += contigName(*contigs, i, tmp);
-            put(text, contigs->keys[i]); put(text, lens[i]);
-            for (int c = 0; c < 10; c++) put(text, stats[i * 10 + c]);
-            put(text, applied); put(text, newLen);
-            text.push_back('\n');
-        }
-        cdm_indel_free(sites, codes);
-        laps.lap("indel report: gapped records, sites, tables");
-    }
-    if (!writeText(*o.summary, text)) die("Could not write " + *o.summary);
-    if (o.sites && !writeText(*o.sites, sitesText)) die("Could not write " + *o.sites);
-    if (o.consensus && !writeText(*o.consensus, fasta)) die("Could not write " + *o.consensus);
-}
-// What a pileReports call is asked for (NULL: not asked for): the damage table with its ends, the depth table with its edge and
-// track, the variant, the break and the indel reports, the map report with the read set whose names and letters its lines carry.
-struct PileAsk {
-    const std::string *damageOut = NULL; long ends = 0;
-    const std::string *depthOut = NULL; long edge = 0; const std::string *trackOut = NULL;
-    const VariantOut *variants = NULL; const BreakOut *breaks = NULL;
-    const MapOut *map = NULL; const DamageInput *mapReads = NULL;
-    const IndelOut *indels = NULL;
-};
-// The reports of one read set against one set of contigs: the three calls once, then each reduction that was asked for on the same
-// alignment set.  contigs == NULL: the header lines alone.  Neither DB is freed here.
-void pileReports(cdm_ctx *ctx, const DamageInput *contigs, cdm_seqdb *reads, int kmerSize, float minSeqId, const PileAsk &ask, Laps &laps) {
-    PileSet ps;
-    if (haveContigs(contigs)) {
-        if (ask.map) mapCheckNames(*contigs);
-        const bool keepHits = (ask.map && ask.map->gapped) || ask.indels || (ask.variants && ask.variants->gap.on) || (ask.breaks && ask.breaks->gap.on);
-        ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, keepHits);
-        laps.lap(ask.damageOut ? "damage report: kmermatcher, rescorediagonal" : ask.depthOut ? "depth report: kmermatcher, rescorediagonal" : ask.variants ? "variant report: kmermatcher, rescorediagonal" :
-                 ask.breaks ? "break report: kmermatcher, rescorediagonal" : ask.indels ? "indel report: kmermatcher, rescorediagonal" : "map report: kmermatcher, rescorediagonal");
-    }
-    if (ask.damageOut) damageTable(ctx, contigs, ps, ask.ends, *ask.damageOut, laps);
-    if (ask.depthOut) {
-        std::vector<std::vector<uint64_t>> stats(1); std::vector<uint32_t> track;
-        if (haveContigs(contigs)) depthSample(ctx, *contigs, ps, ask.edge, stats[0], ask.trackOut ? &track : NULL);
-        depthTable(ctx, contigs, stats, 1, *ask.depthOut);
-        if (ask.trackOut) depthTrackFile(ctx, contigs, track, *ask.trackOut);
-        laps.lap("depth report: depth, table");
-    }
-    if (ask.variants) variantReport(ctx, contigs, ps, *ask.variants, laps);
-    if (ask.breaks) breakReport(ctx, contigs, ps, *ask.breaks, laps);
-    if (ask.map) mapReport(ctx, contigs, ask.mapReads, ps, *ask.map, laps);
-    if (ask.indels) indelReport(ctx, contigs, ps, *ask.indels, laps);
-    freePileSet(ps);
-}
-// The commands with one read set: exactly (or at least) three positional arguments or the usage line, the flag check, what the
-// command asks for from its flags (fill), both inputs, the reports.
-template <class Fill> int contigReport(Args &a, const char *module, bool exactly, const char *usage, const FlagSpec *flags, Fill fill) {
-    if (exactly ? a.pos.size() != 3 : a.pos.size() < 3) die(usage);
-    checkFlags(module, a, flags);
-    PileAsk ask;
-    fill(ask);
-    Laps laps;
-    cdm_ctx *ctx = openCtx();
-    DamageInput contigs, reads;
-    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    if (have && !loadDamageInput(ctx, a.pos[1], true, ask.map != NULL, reads)) die(std::string(module) + ": " + a.pos[1] + " holds no reads");      // (the map's lines carry the reads' names)
-    ask.mapReads = &reads;
-    laps.lap("inputs read, sequences up");
-    pileReports(ctx, have ? &contigs : NULL, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), ask, laps);
-    if (contigs.db) cdm_seqdb_free(contigs.db);
-    if (reads.db) cdm_seqdb_free(reads.db);
-    cdm_ctx_destroy(ctx);
-    return EXIT_SUCCESS;
-}
-int contigDamage(Args &a) {
-    return contigReport(a, "contig_damage", false, "Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]", DAMAGE_FLAGS,
-                        [&](PileAsk &ask) { ask.ends = damageEnds(a, "contig_damage"); ask.damageOut = &a.pos[2]; });
-}
-int contigDepth(Args &a) {
-    if (a.pos.size() < 3) die("Usage: carpedeam contig_depth <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> [<i:reads> ...] <o:tsvFile> [--depth-edge 0] [--min-seq-id 0.9] [-k 20] [--depth-track <bedGraph>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32]");
-    checkFlags("contig_depth", a, DEPTH_FLAGS);
-    const long edge = depthEdge(a, "contig_depth");
-    const GapOpts gap = gapOpts(a, "contig_depth", TABLE_GAPPED);
-    const size_t samples = a.pos.size() - 2;
-    const bool wantTrack = a.flag.count("--depth-track") != 0;
-    if (wantTrack && samples > 1) unsupported("contig_depth: --depth-track with " + std::to_string(samples) + " read sets is not supported by the MI355X path (the track is written for one read set)");
-    const int k = (int) iflag(a, "-k", 20); const float minSeqId = fflag(a, "--min-seq-id", 0.9f);
-    Laps laps;
-    cdm_ctx *ctx = openCtx();
-    DamageInput contigs;
-    const bool have = loadDamageInput(ctx, a.pos[0], false, true, contigs);
-    laps.lap("contigs read, sequences up");
-    std::vector<std::vector<uint64_t>> stats(samples); std::vector<uint32_t> track;
-    for (size_t s = 0; have && s < samples; s++) {      // each read set is freed before the next
-        DamageInput reads;
-        if (!loadDamageInput(ctx, a.pos[1 + s], true, false, reads)) die("contig_depth: " + a.pos[1 + s] + " holds no reads");
-        PileSet ps = pileupAlignments(ctx, contigs.db, reads.db, k, minSeqId, gap.on);
-        laps.lap("depth report: reads up, kmermatcher, rescorediagonal");
-        depthSample(ctx, contigs, ps, edge, stats[s], wantTrack ? &track : NULL, &gap);
-        freePileSet(ps); cdm_seqdb_free(reads.db);
-        laps.lap("depth report: depth");
-    }
-    depthTable(ctx, have ? &contigs : NULL, stats, samples, a.pos.back());
-    if (wantTrack) depthTrackFile(ctx, have ? &contigs : NULL, track, a.flag["--depth-track"]);
-    laps.lap("depth report: table");
-    if (contigs.db) cdm_seqdb_free(contigs.db);
-    cdm_ctx_destroy(ctx);
-    return EXIT_SUCCESS;
-}
-int contigVariants(Args &a) {
-    VariantOut v;
-    return contigReport(a, "contig_variants", true, "Usage: carpedeam contig_variants <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-alt-count 2] [--min-alt-percent 20] [--mask-ends 0] "
-                        "[--sites <tsvFile>] [--consensus <fastaFile>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", VARIANT_FLAGS, [&](PileAsk &ask) {
-        v.opt = variantOpts(a, "contig_variants");
-        v.gap = gapOpts(a, "contig_variants", TABLE_GAPPED);
-        v.summary = &a.pos[2]; v.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; v.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
-        ask.variants = &v;
-    });
-}
-int contigBreaks(Args &a) {
-    BreakOut o;
-    return contigReport(a, "contig_breaks", true, "Usage: carpedeam contig_breaks <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--break-anchor 16] [--break-edge 50] [--min-span 1] [--min-span-percent 0] "
-                        "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", BREAK_FLAGS, [&](PileAsk &ask) {
-        o.opt = breakOpts(a, "contig_breaks");
-        o.gap = gapOpts(a, "contig_breaks", TABLE_GAPPED);
-        o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
-        o.summary = &a.pos[2]; o.split = a.flag.count("--split") ? &a.flag["--split"] : NULL; o.track = a.flag.count("--span-track") ? &a.flag["--span-track"] : NULL;
-        ask.breaks = &o;
-    });
-}
-int contigMap(Args &a) {
-    MapOut o;
-    return contigReport(a, "contig_map", true, "Usage: carpedeam contig_map <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:samFile> [--read-group <id>] [--primary-only 0] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20] [--threads N]",
-                        MAP_FLAGS, [&](PileAsk &ask) {
-        o.primaryOnly = rangedFlag(a, "contig_map", "--primary-only", 0, 0, 1, "0 writes every line, 1 leaves the secondary lines out") != 0;
-        o.readGroup = a.flag.count("--read-group") ? &a.flag["--read-group"] : NULL;
-        if (o.readGroup && (o.readGroup->empty() || o.readGroup->find('\t') != std::string::npos))
-            unsupported("contig_map: --read-group \"" + *o.readGroup + "\" is not supported by the MI355X path (a read group's ID is at least one character and holds no tab)");
-        const GapOpts g = gapOpts(a, "contig_map", "0 writes the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions");
-        o.gapped = g.on; o.gapBand = g.band; o.gapMinColumns = g.minColumns; o.minSeqId = g.minSeqId;
-        o.sam = &a.pos[2];
-        ask.map = &o;
-    });
-}
-int contigIndels(Args &a) {
-    IndelOut o;
-    return contigReport(a, "contig_indels", true, "Usage: carpedeam contig_indels <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-depth 3] [--min-indel-count 2] [--min-indel-percent 20] "
-                        "[--gap-band 8] [--gap-min-columns 32] [--sites <tsvFile>] [--consensus <fastaFile>] [--min-seq-id 0.9] [-k 20] [--threads N]", INDEL_FLAGS, [&](PileAsk &ask) {
-        o.minDepth = rangedFlag(a, "contig_indels", "--min-depth", 3, 1, 1000000, "a called place is crossed by 1 to 1000000 reads");
-        o.minCount = rangedFlag(a, "contig_indels", "--min-indel-count", 2, 1, 1000000, "a supported insertion or deletion has 1 to 1000000 reads");
-        o.minPercent = rangedFlag(a, "contig_indels", "--min-indel-percent", 20, 0, 100, "a percentage of the crossing reads is 0 to 100");
-        o.gapBand = rangedFlag(a, "contig_indels", "--gap-band", 8, 1, 31, "the gapped alignment looks at 1 to 31 diagonals on either side of the seed's");
-        o.gapMinColumns = rangedFlag(a, "contig_indels", "--gap-min-columns", 32, 1, 4096, "a rescued read has 1 to 4096 letters aligned at the least");
-        o.minSeqId = fflag(a, "--min-seq-id", 0.9f);
-        o.summary = &a.pos[2]; o.sites = a.flag.count("--sites") ? &a.flag["--sites"] : NULL; o.consensus = a.flag.count("--consensus") ? &a.flag["--consensus"] : NULL;
-        ask.indels = &o;
-    });
-}
 int readsLoop(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam ancient_reads_loop <i:sequenceDB|reads[.gz]|R1 R2 [R1 R2 ...]> <o:sequenceDB> --ancient-damage <prefix> [--num-iter-reads-only N]");
     checkFlags("ancient_reads_loop", a, ANCIENT_FLAGS, LOOP_FLAGS);
@@ -2262,12 +1445,6 @@ bool indexKeys(const std::string &path, std::vector<std::string> &lines, std::ve
     free(line); fclose(f);
     return true;
 }
-bool writeText(const std::string &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "w");
-    if (!f) return false;
-    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-    return fclose(f) == 0 && ok;
-}
 // the command's own directory and what it holds (--remove-tmp-files 1): plain files and links, one level of sub-directories
 void removeOwnDir(const std::string &dir, int depth = 0) {
     if (DIR *d = opendir(dir.c_str())) {
@@ -2458,8 +1635,8 @@ int assembleFused(Args &a) {
         unlink((REP + ".fasta").c_str());
     }
     if (anyReport) {       // rank 0's context (the loop's helpers of a --gpus N run are gone): the FASTA as contig_damage would read it, the reads as they stand
-        DamageInput contigs;
-        const bool have = loadDamageInput(reportCtx, outFile, false, true, contigs);
+        SeqSet contigs;
+        const bool have = loadSeqSet(reportCtx, outFile, false, true, contigs);
         pileReports(reportCtx, have ? &contigs : NULL, E.reads, 20, 0.9f, ask, laps);
         if (contigs.db) cdm_seqdb_free(contigs.db);
         cdm_seqdb_free(E.reads); cdm_ctx_destroy(reportCtx);

@@ -169,7 +169,6 @@ int64_t MmDb::idOfSearch(uint32_t k) const {
     return (it == key.end() || *it != k) ? -1 : (int64_t) (it - key.begin());
 }
 
-static char *utoaFast(unsigned long long v, char *p) { char b[24]; int n = 0; do { b[n++] = (char) ('0' + v % 10); v /= 10; } while (v); while (n) *p++ = b[--n]; return p; }
 static bool writeDbtype(const std::string &path, int dbtype) {
     FILE *t = fopen((path + ".dbtype").c_str(), "wb");
     if (!t) return false;
@@ -181,7 +180,7 @@ static void indexText(std::string &out, const uint32_t *key, const uint32_t *len
     out.reserve(n * 28);
     char b[96];
     for (size_t i = 0; i < n; i++) {
-        char *p = utoaFast(key[i], b); *p++ = '\t'; p = utoaFast(base, p); *p++ = '\t'; p = utoaFast(len[i], p); *p++ = '\t'; p = utoaFast(ext[i], p); *p++ = '\n';
+        char *p = utoa(key[i], b); *p++ = '\t'; p = utoa(base, p); *p++ = '\t'; p = utoa(len[i], p); *p++ = '\t'; p = utoa(ext[i], p); *p++ = '\n';
         out.append(b, p - b);
         base += len[i];
     }

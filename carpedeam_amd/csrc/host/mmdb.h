@@ -32,6 +32,20 @@ template <typename T> struct HugeAlloc {
 };
 template <typename T> using HVec = std::vector<T, HugeAlloc<T>>;
 
+// decimal text behind p, two digits per division; the end of what was written
+inline char *utoa(unsigned long long v, char *p) {
+    static const char D2[] = "0001020304050607080910111213141516171819202122232425262728293031323334353637383940414243444546474849"
+                             "5051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
+    if (v < 10) { *p++ = (char) ('0' + v); return p; }
+    if (v < 100) { memcpy(p, D2 + 2 * v, 2); return p + 2; }
+    char b[24]; int n = 24;
+    while (v >= 100) { const unsigned r = (unsigned) (v % 100); v /= 100; n -= 2; memcpy(b + n, D2 + 2 * r, 2); }
+    if (v >= 10) { n -= 2; memcpy(b + n, D2 + 2 * v, 2); } else b[--n] = (char) ('0' + v);
+    memcpy(p, b + n, (size_t) (24 - n));
+    return p + (24 - n);
+}
+inline char *itoa(long long v, char *p) { if (v < 0) { *p++ = '-'; return utoa((unsigned long long) -v, p); } return utoa((unsigned long long) v, p); }
+
 struct MmDb {
     HVec<uint32_t> key;       // ordered by key (DBReader::sortIndex, DBReader.cpp:238-)
     HVec<uint64_t> off, len;  // len includes the trailing NUL
