@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -149,13 +150,80 @@ __device__ __forceinline__ void bitonicRegs(W (&v)[R], int lane) {
         }
     }
 }
+// ---- 32-bit words: the same sort by another network of the same depth, made for the vector unit's issue rate.
+// Every comparator points the same way (the smaller word to the smaller index): a merge of two sorted halves of k elements starts
+// with i against i ^ (k - 1), the mirror image, and goes on with i against i ^ j, j = k / 4 .. 1.  Then
+//  - an exchange inside a lane is v_min_u32 + v_max_u32 and no select at all;
+//  - an exchange between lanes is v_min_u32 + v_max_u32 with the partner's word as their DPP operand (no move of its own) and one
+//    select by "the lane's bit D is clear", D = 1 .. 32: six lane masks in the whole network, where up / down directions need one
+//    per (k, j) and ran the kernel out of scalar registers;
+//  - the R words of a stage are independent: their instructions interleave and fill each other's DPP wait states.
+// lane ^ M for the merge's first stage, M = 2^t - 1 (a mirror image inside 2^t lanes)
+template <int CTRL> __device__ __forceinline__ uint32_t dppMove(uint32_t a) {      // bound_ctrl and full masks: foldable into the consumer
+    return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) a, CTRL, 0xF, 0xF, true);
+}
+template <int M> __device__ __forceinline__ uint32_t mirrorLane32(uint32_t a) {
+    static_assert(M == 1 || M == 3 || M == 7 || M == 15 || M == 31 || M == 63, "mirror image inside 2, 4 .. 64 lanes");
+    if (M == 1) return dppMove<0xB1>(a);                                        // quad_perm [1,0,3,2]
+    if (M == 3) return dppMove<0x1B>(a);                                        // quad_perm [3,2,1,0]
+    if (M == 7) return dppMove<0x141>(a);                                       // row_half_mirror
+    if (M == 15) return dppMove<0x140>(a);                                      // row_mirror
+    if (M == 31) return (uint32_t) __builtin_amdgcn_ds_swizzle((int) a, 0x7C1F);       // xor 0x1F within 32 lanes
+    return (uint32_t) __shfl_xor((int) a, 63, 64);
+}
+template <int M> __device__ __forceinline__ uint32_t xorLaneFold32(uint32_t a) {
+    static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16, "lane distance");
+    if (M == 1) return dppMove<0xB1>(a);                                        // quad_perm [1,0,3,2]
+    if (M == 2) return dppMove<0x4E>(a);                                        // quad_perm [2,3,0,1]
+    if (M == 4) return dppMove<0x1B>(dppMove<0x141>(a));                        // row_half_mirror, then quad_perm [3,2,1,0]: 7 - (i ^ 3) = i ^ 4; the second folds
+    if (M == 8) return dppMove<0x128>(a);                                       // row_ror:8
+    return (uint32_t) __builtin_amdgcn_ds_swizzle((int) a, 0x401F);             // xor 0x10 within 32 lanes
+}
+// v[r] against b[r], the word of its partner in another lane; lanes with bit D clear are the lower side
+template <int R> __device__ __forceinline__ void keepLowerOrUpper(uint32_t (&v)[R], const uint32_t (&b)[R], bool lower) {
+    uint32_t lo[R], hi[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) { lo[r] = min(v[r], b[r]); hi[r] = max(v[r], b[r]); }
+#pragma unroll
+    for (int r = 0; r < R; r++) v[r] = lower ? lo[r] : hi[r];
+}
+template <int R, int J> __device__ __forceinline__ void bitonicStage32(uint32_t (&v)[R], int lane) {     // i against i ^ J
+    if constexpr (J < R) {
+#pragma unroll
+        for (int r = 0; r < R; r++) if ((r ^ J) > r) { const uint32_t a = v[r], b = v[r ^ J]; v[r] = min(a, b); v[r ^ J] = max(a, b); }
+    } else {
+        uint32_t b[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) b[r] = xorLaneFold32<J / R>(v[r]);
+        keepLowerOrUpper<R>(v, b, (lane & (J / R)) == 0);
+    }
+}
+template <int R, int K> __device__ __forceinline__ void bitonicMirror32(uint32_t (&v)[R], int lane) {    // i against i ^ (K - 1)
+    if constexpr (K <= R) {
+#pragma unroll
+        for (int r = 0; r < R; r++) if ((r ^ (K - 1)) > r) { const uint32_t a = v[r], b = v[r ^ (K - 1)]; v[r] = min(a, b); v[r ^ (K - 1)] = max(a, b); }
+    } else {
+        uint32_t b[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) b[r] = mirrorLane32<K / R - 1>(v[R - 1 - r]);
+        keepLowerOrUpper<R>(v, b, (lane & (K / (2 * R))) == 0);
+    }
+}
+template <int R, int K, int J> __device__ __forceinline__ void bitonicMerge32(uint32_t (&v)[R], int lane) {
+    if constexpr (J > 0) { bitonicStage32<R, J>(v, lane); bitonicMerge32<R, K, (J >> 1)>(v, lane); }
+}
+template <int R, int K> __device__ __forceinline__ void bitonicLevels32(uint32_t (&v)[R], int lane) {
+    if constexpr (K <= 64 * R) { bitonicMirror32<R, K>(v, lane); bitonicMerge32<R, K, (K >> 2)>(v, lane); bitonicLevels32<R, 2 * K>(v, lane); }
+}
+template <int R>
+__device__ __forceinline__ void bitonicRegs32(uint32_t (&v)[R], int lane) { bitonicLevels32<R, 2>(v, lane); }
 // sorts the gm <= 64 R elements i = 0.. of a group by mk(i) and hands the sorted register array to done(v)
 template <int R, typename W, typename MakeComp, typename Done>
 __device__ __forceinline__ void sortGroupRegs(int gm, int lane, const MakeComp &mk, const Done &done) {
     W v[R];
 #pragma unroll
     for (int r = 0; r < R; r++) { const int i = lane * R + r; v[r] = (i < gm) ? mk(i) : (W) ~(W) 0; }
-    bitonicRegs<R, W>(v, lane);
+    if constexpr (std::is_same<W, uint32_t>::value) bitonicRegs32<R>(v, lane); else bitonicRegs<R, W>(v, lane);
     done(v);
 }
 // MAXR: the largest network the caller can reach (gm <= 64 MAXR); the ones beyond it are not instantiated - a kernel's register

@@ -73,14 +73,14 @@ template <typename LY> struct StartFrom {      // the scan's index starts at 0, 
 // (rep, id, diagonal, strand) key of one member of a k-mer run, ~0 if the member is dropped (assignGroup :453-562)
 __device__ __forceinline__ uint64_t groupKeyCore(const GroupParams &a, uint32_t repId, int queryLen, int repPos, bool repIsReverse,
                                                  uint32_t id, int tLen, int tPos0, bool targetIsReverse) {
-    int qPos, tPos; bool qRev;
-    if (repIsReverse && !targetIsReverse) { qPos = repPos; tPos = tPos0; qRev = true; }
-    else if (repIsReverse && targetIsReverse) { qPos = (queryLen - 1) - repPos; tPos = (tLen - 1) - tPos0; qRev = false; }
-    else if (!repIsReverse && targetIsReverse) { qPos = (queryLen - 1) - repPos; tPos = (tLen - 1) - tPos0; qRev = true; }
-    else { qPos = repPos; tPos = tPos0; qRev = false; }
+    // the reference's four strand cases of assignGroup: a target on the reverse strand counts both positions from the other end -
+    // qPos = (queryLen - 1) - repPos, tPos = (tLen - 1) - tPos0 -, and the query is reversed when the two strands differ.  As selects:
+    // the four branches were an exec save / restore nest per member
+    const bool qRev = repIsReverse != targetIsReverse;
     // (the reference holds positions and the diagonal in `short` below 32 765 letters and in `int` above, kmermatcher.cpp:803-808;
     // below that limit the casts never change a value, so one expression serves both paths)
-    const int diagonal = qPos - tPos;
+    const int plain = repPos - tPos0;
+    const int diagonal = targetIsReverse ? (queryLen - tLen) - plain : plain;
     const bool canBeExtended = diagonal < 0 || (diagonal > (queryLen - tLen));
     // coverage modes 0-2 with a threshold <= 0 hold for any two positive lengths: skip the divisions
     const bool cbc = (a.covThr <= 0.0f && a.covMode <= 2 && queryLen > 0 && tLen > 0) ? true : canBeCoveredK(a.covThr, a.covMode, (float) queryLen, (float) tLen);
@@ -285,7 +285,8 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
     __shared__ uint32_t sSAll[BK_WAVES][GK_CAP];
     static_assert(GK_CAP >= 64 * GkGeom<LY>::MAXR || !LY::bySlot, "the largest network of the instance writes 64 R words of sSAll");
     __shared__ WaveLdsT<GK_WIN> wAll[BK_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (slot instance: the wave's number as a scalar - r0 and every address made of it, a.keys + r0, a.out + r0, stay out of the vector unit)
+    const int lane = threadIdx.x & 63, wave = LY::bySlot ? __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) : (int) (threadIdx.x >> 6);
     const uint64_t r0 = ((uint64_t) blockIdx.x * BK_WAVES + wave) * (uint64_t) a.own;
     if (r0 >= a.n) return;      // (whole wave)
     uint64_t *sKey = sKeyAll[wave]; V *sVal = sValAll[wave]; uint32_t *ss = sSAll[wave];
@@ -303,6 +304,9 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
     __shared__ uint32_t sRecRep[BK_WAVES][REC ? REC_CAP : 1];
     __shared__ uint64_t sRecVal[BK_WAVES][REC ? REC_CAP : 1];
     const uint32_t recLimit = a.recLimit;
+    // the array's first run as a slot of this wave's window (no slot of it: the run starts elsewhere) - one 32-bit compare per member
+    const uint32_t firstRel = a.firstRunIdx - r0 < (uint64_t) GK_WIN ? (uint32_t) (a.firstRunIdx - r0) : ~0u;
+    unsigned long long *const outW = a.out + r0;
     const uint64_t waveIdx = (uint64_t) blockIdx.x * BK_WAVES + wave;
     // slot tuples (LayoutSlot): a tuple becomes its (key, id) pair as it is loaded; the head digit is the segment the index lies in -
     // the wave's own one for nearly every tuple of its window (segments are millions of tuples long)
@@ -372,16 +376,24 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
                     // slot tuples: sequence, position and strand come straight out of the slot index (the k-mer itself is of no interest
                     // behind the sort; every sequence has the one length)
                     const int er = (int) (ss[s0] & IDXM);
-                    uint32_t repId, bestPos, id, tPos; bool repFwd, fwd;
-                    slotFields(a.geom, sKey[er], repId, bestPos, repFwd);
-                    for (int t = s0 + 1; t < gm && !(ss[t] >> 31); t++) {     // same sequence twice in the run (rare)
-                        uint32_t ie, pe; bool fe;
-                        slotFields(a.geom, sKey[(int) (ss[t] & IDXM)], ie, pe, fe);
-                        if (ie != repId) break;
-                        if (pe < bestPos) { bestPos = pe; repFwd = fe; }
+                    uint32_t repId, bestPos, id, tPos, repR; bool repFwd, fwd;
+                    const uint64_t repT = sKey[er];
+                    slotFields(a.geom, repT, repId, bestPos, repFwd, repR);
+                    // Same sequence twice in the run: inside a k-mer run the sorted order is the slot order (stable passes, the index is
+                    // part of the word), and a sequence's slots are consecutive - the representative's sequence has another tuple in the
+                    // run exactly when the NEXT tuple's slot (there is one: the run has two tuples or more here) lies in front of that
+                    // sequence's last slot.  A subtract and a compare per lane; the scan behind it decodes tuples and is rare
+                    const uint32_t nextSlot = (uint32_t) sKey[(int) (ss[s0 + 1] & IDXM)];
+                    if (nextSlot - (uint32_t) repT < a.geom.uniS - repR) {
+                        for (int t = s0 + 1; t < gm && !(ss[t] >> 31); t++) {
+                            uint32_t ie, pe; bool fe;
+                            slotFields(a.geom, sKey[(int) (ss[t] & IDXM)], ie, pe, fe);
+                            if (ie != repId) break;
+                            if (pe < bestPos) { bestPos = pe; repFwd = fe; }
+                        }
                     }
                     slotFields(a.geom, sKey[e], id, tPos, fwd);
-                    const bool firstRun = r0 + (uint64_t) (g0 + s0) == a.firstRunIdx;
+                    const bool firstRun = (uint32_t) (g0 + s0) == firstRel;
                     gk = groupKeyCore(a, repId, (int) a.geom.uniL, (int) bestPos, firstRun ? false : !repFwd, id, (int) a.geom.uniL, (int) tPos, !fwd);
                     if (a.wide && s0 == p) gk = markRunStart(a, gk, repId);
                     recRepOfLane = repId;
@@ -408,7 +420,8 @@ __global__ __launch_bounds__(bucket::BK_NT, gkMinWaves<LY>()) void k_bucket_grou
                     if (a.wide && s0 == p) gk = markRunStart(a, gk, repId);
                     recRepOfLane = repId;
                 }
-                a.out[r0 + (uint64_t) (g0 + p)] = gk;
+                if constexpr (LY::bySlot) outW[(uint32_t) (g0 + p)] = gk;       // (scalar base, 32-bit lane part)
+                else a.out[r0 + (uint64_t) (g0 + p)] = gk;
                 const unsigned long long keptMask = __ballot(runsort::gkKept(gk));
                 keptCnt += (uint32_t) __popcll(keptMask);
                 if constexpr (REC) if (a.recRep) {

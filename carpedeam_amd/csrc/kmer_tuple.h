@@ -154,11 +154,18 @@ struct LayoutSlot {
     __device__ static void unpackR1(uint64_t key, V v, const TupleGeom &g, uint32_t &len, uint32_t &pos) { LayoutPacked::unpackR1(key, v, g, len, pos); }
 };
 // sequence, stored position (kmermatcher.cpp:186: counted from the other end on the reverse strand) and strand of a slot tuple
-__device__ __forceinline__ void slotFields(const TupleGeom &g, uint64_t t8, uint32_t &id, uint32_t &pos, bool &fwd) {
+// (r: the slot of the sequence, 0 = its whole-sequence hash tuple.  Both positions are computed and one is selected: as branches the
+// two cases cost the grouping kernel's member loop an exec save / restore nest per decoded tuple)
+__device__ __forceinline__ void slotFields(const TupleGeom &g, uint64_t t8, uint32_t &id, uint32_t &pos, bool &fwd, uint32_t &r) {
     fwd = ((uint32_t) (t8 >> rx::SLOT_STRAND_SHIFT) & 1u) != 0u;
-    uint32_t r;
     slotSplit(g, (uint32_t) t8, id, r);
-    pos = r == 0u ? 0u : (fwd ? r - 1u : g.uniL - (r - 1u) - (uint32_t) g.uniK);
+    const uint32_t pf = r - 1u, pr = (g.uniL + 1u - (uint32_t) g.uniK) - r;
+    const uint32_t p = fwd ? pf : pr;
+    pos = r == 0u ? 0u : p;
+}
+__device__ __forceinline__ void slotFields(const TupleGeom &g, uint64_t t8, uint32_t &id, uint32_t &pos, bool &fwd) {
+    uint32_t r;
+    slotFields(g, t8, id, pos, fwd, r);
 }
 // the slot tuple at k-mer-order index idx (head digit td) as the (key, id) pair LayoutPacked holds
 __device__ __forceinline__ void slotTupleToPair(const TupleGeom &g, uint64_t t8, uint32_t td, uint64_t &key, uint32_t &id) {
