@@ -315,16 +315,29 @@ template <int RECORDS> __device__ __forceinline__ uint32_t waveInclusiveSum(uint
     }
     return (uint32_t) x;
 }
+// SPLIT pile-up: the two mask words of column col (0..63) in the counter rows of the slots 5, 16, 27 and 38 (32 words each, 16 columns to a row)
+__device__ __forceinline__ uint32_t endMaskWord(uint32_t col) { const uint32_t t = col & 0x30u; return 5u * 32u + 2u * col + (t << 4) + (t << 2); }
+constexpr uint64_t INTERIOR_SLOTS = (1ull << 5) | (1ull << 16) | (1ull << 27) | (1ull << 38);
 constexpr uint32_t NOT_STAGED = 0x80000000u;        // no offset - first word comes near it (offsets < POOL, word indices < 2^26)
 
 // MAXREC: most records of a query on this instance (64, or 15 with CT = uint8_t: two 4-bit fields per counter and a quarter of the
 // record slots - less LDS per block, more waves per CU; the kernel is bound by the latency of its dependent gathers, so the
 // occupancy is what it runs on).  MINW: waves per SIMD (= blocks per CU) the register allocation has to leave room for.
-template <int MAXREC, typename CT, int MINW>
+//
+// SPLIT: the pile-up by damage class.  All columns of a record but the five at each end of its target are class 5, so their counts
+// are kept per lane (= column) in two registers, forward and reverse records, with one 8-bit field per target base (at most 64
+// records: no carries).  The loop over the staged records of one strand is then a range test, the letter and one shifted add; the
+// strand is a constant of the loop (a reverse record adds to field 3 - stored letter and walks its words downwards).  The at most ten
+// end columns of a record go to the LDS counters with one lane per record and end, one step per class.  The four counter rows of the slots
+// tb * 11 + 5 hold no counts then: they are the 64 x 2 words of a per-column mask of the end slots that the record lanes mark and the
+// column's lane reads at the call (which is why SPLIT needs 16-bit counters: four rows of 32 words).  Records outside the stage keep
+// a loop with lane = column and letters from global memory that feeds the same registers and counters.
+template <int MAXREC, typename CT, int MINW, bool SPLIT>
 __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectArgs a, const uint32_t *__restrict__ list, const unsigned int *__restrict__ nList) {
     constexpr int HB = sizeof(CT) * 4;                  // bits per field: total | reverse << HB
     constexpr int PER = 4 / sizeof(CT);                 // counters per LDS dword
     constexpr int POOL = fastPoolWords<MAXREC, CT, MINW>();
+    static_assert(!SPLIT || (PER == 2 && MAXREC <= 64), "the end mask takes 64 x 2 words: the four interior rows of 16-bit counters");
     static_assert(POOL >= STAGE_WORDS && (size_t) MINW * ldsAllocBytes(fastLdsBytes<CT>(POOL)) <= CU_LDS_BYTES,
                   "the launch bound asks for more blocks per CU than the kernel's LDS lets run: the compiler would drop the request");
     __shared__ double sLogT[16], sLogQ[12 * 16], sLogD[2 * 11 * 16];
@@ -432,6 +445,8 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
             iDelta = off - w0;
         }
         const uint64_t okMask = __ballot(ok);
+        // SPLIT: the staged records by strand (the strand is a constant of their loops), and the others
+        const uint64_t stMask = SPLIT ? __ballot(ok && staged) : 0, revMask = SPLIT ? __ballot((iLenFlags & 0x80000000u) != 0) : 0;
         if (a.stats) {      // (a stats run: not what is timed)
             const uint64_t mN = __ballot(ok && tN), mLong = __ballot(nW > (uint32_t) STAGE_WORDS), mOver = __ballot(fits && !staged);
             if (lane == 0) { atomicAdd(&a.stats[0], (unsigned long long) __popcll(okMask)); atomicAdd(&a.stats[1], (unsigned long long) __popcll(mN));
@@ -443,13 +458,71 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
         if (hasNext && (uint32_t) lane < nRecCur) { recCur = a.rec[r0N + lane]; if (a.ry) ryCur = a.ry[r0N + lane]; }
 
         // ---- pile-up + call, 64 positions at a time.  The record fields are wave-uniform: they are read out of the owning lane into
-        // scalar registers, the per-lane work is the target letter, its damage class and one LDS add.
+        // scalar registers, the per-lane work is the target letter, its damage class and one LDS add (SPLIT: see above).
         const uint32_t lastWord = (qLen + 15) / 16;
         for (uint32_t base = 0; base < qLen; base += 64) {
             const uint32_t p = base + lane;
             uint64_t touched = 0;       // slots of this lane's column that are non-zero
             uint32_t cov4 = 0;          // records per target base (8 bits each: at most 64 records), counted on the way
-            for (uint64_t m = okMask; m; m &= m - 1) {
+            uint32_t inFwd = 0, inRev = 0;      // SPLIT: class 5 records of this lane's column per target base, 8 bits each, by strand
+            if constexpr (SPLIT) {
+                // the record's interior columns iLo .. iLo + iLen on the query (oriented target positions 5 .. tLen - 6 inside the span;
+                // a span of 30 columns or more always has some) and the letter index iC of column iLo: on the target as stored, once
+                // staged in sStage as a whole, 16 letters to the word.  A forward record's index goes up with the column, a reverse
+                // one's down.  (Made again for every chunk, so that the three are not live through the call.)
+                const uint32_t lead = (uint32_t) max(0, 5 - (int) iDs), iLo = iQs + lead, iLen = min(iSpan, (iLenFlags & 0x3FFFFFFFu) - 6u - iDs) - lead;
+                const uint32_t iC = ((iLenFlags & 0x80000000u) ? (iLenFlags & 0x3FFFFFFFu) - 1u - (iDs + lead) : iDs + lead) + ((uint32_t) (wave * POOL) + iDelta) * 16u;
+                const uint64_t inMask = __ballot(iLo < base + 64u && iLo + iLen >= base) & stMask;
+                // ---- the end columns of the staged records, one lane per (record, end).  Up to 32 records: lane l takes the 5' end
+                // (target positions 0 .. 4, classes 0 .. 4) of record l & 31 when l < 32 and its 3' end (tLen - 5 .. tLen - 1, classes
+                // 6 .. 10) otherwise, five steps in all; more records: lane = record and the two ends one after the other.  The
+                // column of a position is qs + tpos - ds, where that lies in the span and in this chunk; position, column and letter
+                // index go up (the index of a reverse record down) by one per step.
+                uint32_t *const stageAll = &sStage[0][0];
+                {
+                    const bool halves = nRec <= 32u;
+                    const int src = halves ? (lane & 31) : lane;
+                    const uint32_t eQs = (uint32_t) __shfl((int) iQs, src), eSpan = (uint32_t) __shfl((int) iSpan, src), eDs = (uint32_t) __shfl((int) iDs, src);
+                    const uint32_t eLf = (uint32_t) __shfl((int) iLenFlags, src), eDelta = (uint32_t) __shfl((int) iDelta, src);
+                    const uint32_t tLen = eLf & 0x3FFFFFFFu; const bool rev = (eLf & 0x80000000u) != 0;
+                    for (uint32_t pass = 0; pass < (halves ? 1u : 2u); pass++) {
+                        const bool far = halves ? lane >= 32 : pass != 0;
+                        const uint32_t tpos = far ? tLen - 5u : 0u;
+                        uint32_t d = tpos - eDs, col = eQs + d - base;            // (either wraps to a large number when below its range)
+                        uint32_t f = (rev ? tLen - 1u - tpos : tpos) + ((uint32_t) (wave * POOL) + eDelta) * 16u, cls = far ? 6u : 0u;
+                        if (eDelta != NOT_STAGED) {
+#pragma unroll
+                            for (int step = 0; step < 5; step++) {
+                                if (d <= eSpan && col < 64u) {
+                                    const uint32_t slot = (__builtin_amdgcn_ubfe(stageAll[f >> 4], f << 1, 2u) ^ (rev ? 3u : 0u)) * 11u + cls;
+                                    atomicAdd(&cntWords[slot * 32u + (col >> 1)], (rev ? (1u | (1u << HB)) : 1u) << ((col & 1u) * 16u));
+                                    atomicOr(&cntWords[endMaskWord(col) + (slot >> 5)], 1u << (slot & 31u));
+                                }
+                                d++; col++; cls++; f += rev ? ~0u : 1u;
+                            }
+                        }
+                    }
+                }
+                // ---- the interior columns of the staged records, lane = column
+                for (uint64_t m = inMask & ~revMask; m; m &= m - 1) {
+                    const int r = __ffsll((unsigned long long) m) - 1;
+                    const uint32_t d = p - (uint32_t) __builtin_amdgcn_readlane((int) iLo, r);
+                    if (d <= (uint32_t) __builtin_amdgcn_readlane((int) iLen, r)) {
+                        const uint32_t f = (uint32_t) __builtin_amdgcn_readlane((int) iC, r) + d;
+                        inFwd += 1u << (__builtin_amdgcn_ubfe(stageAll[f >> 4], f << 1, 2u) << 3);
+                    }
+                }
+                for (uint64_t m = inMask & revMask; m; m &= m - 1) {
+                    const int r = __ffsll((unsigned long long) m) - 1;
+                    const uint32_t d = p - (uint32_t) __builtin_amdgcn_readlane((int) iLo, r);
+                    if (d <= (uint32_t) __builtin_amdgcn_readlane((int) iLen, r)) {
+                        const uint32_t f = (uint32_t) __builtin_amdgcn_readlane((int) iC, r) - d;
+                        inRev += 0x01000000u >> (__builtin_amdgcn_ubfe(stageAll[f >> 4], f << 1, 2u) << 3);      // field 3 - stored letter
+                    }
+                }
+            }
+            // SPLIT: the records outside the stage (lane = column, letters from global memory); otherwise every record
+            for (uint64_t m = SPLIT ? __ballot(iQs < base + 64u && iQs + iSpan >= base) & okMask & ~stMask : okMask; m; m &= m - 1) {
                 const int r = __ffsll((unsigned long long) m) - 1;
                 const uint32_t qs = (uint32_t) __builtin_amdgcn_readlane((int) iQs, r), span = (uint32_t) __builtin_amdgcn_readlane((int) iSpan, r);
                 if (qs + span < base || qs >= base + 64) continue;   // wave uniform
@@ -471,10 +544,29 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
                     // damage class 0..4 from the 5' end, 6..10 at the 3' end, 5 inside (accepted records are at least 30 columns long)
                     const uint32_t cls = min(tpos, 5u) + (uint32_t) max((int) tpos - (int) (tLen - 6u), 0);
                     const uint32_t slot = tb * 11u + cls;
-                    atomicAdd(&cntWords[slot * (64 / PER) + laneWord], (lf & 0x80000000u) ? incRev : incFwd);
-                    touched |= 1ull << slot;
-                    cov4 += 1u << (8u * tb);
+                    if (SPLIT && cls == 5u) {
+                        if (lf & 0x80000000u) inRev += 1u << (8u * tb); else inFwd += 1u << (8u * tb);
+                    } else {
+                        atomicAdd(&cntWords[slot * (64 / PER) + laneWord], (lf & 0x80000000u) ? incRev : incFwd);
+                        touched |= 1ull << slot;
+                        if (!SPLIT) cov4 += 1u << (8u * tb);
+                    }
                 }
+            }
+            if constexpr (SPLIT) {
+                // the end slots the record lanes marked for this column, their records per target base, and the interior ones
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const uint32_t mw = endMaskWord((uint32_t) lane);
+                const uint64_t marked = (uint64_t) cntWords[mw] | ((uint64_t) cntWords[mw + 1] << 32);
+                if (marked) { cntWords[mw] = 0; cntWords[mw + 1] = 0; }
+                touched |= marked;      // (a slot may have records of both kinds: its counter is read once)
+                for (uint64_t m = touched; m; m &= m - 1) {
+                    const uint32_t slot = (uint32_t) __ffsll((unsigned long long) m) - 1u;
+                    cov4 += ((cntWords[slot * 32u + laneWord] >> laneShift) & 0xFFu) << (8u * (slot / 11u));
+                }
+                const uint32_t in = inFwd + inRev;
+                cov4 += in;
+                touched |= ((in & 0xFFu) ? 1ull << 5 : 0) | ((in & 0xFF00u) ? 1ull << 16 : 0) | ((in & 0xFF0000u) ? 1ull << 27 : 0) | ((in >> 24) ? 1ull << 38 : 0);
             }
             uint32_t newCode = 0; bool keep = true;
             if (p < qLen) {
@@ -482,10 +574,17 @@ __global__ __launch_bounds__(64 * FAST_WAVES, MINW) void k_correct_fast(CorrectA
                 const bool qIsN = qHasN && cdm_isN(a.nmask, qw, p);
                 if (qIsN) qb = 0;
                 newCode = callBase(sLogT, sLogQ, sLogD, qb, p, qLen, qWasExt,
-                                   [&](int slot) { const uint32_t v = cntWords[slot * (64 / PER) + laneWord] >> laneShift; return (uint64_t) (v & ((1u << HB) - 1u)) | ((uint64_t) ((v >> HB) & ((1u << HB) - 1u)) << 32); },
+                                   [=](int slot) {
+                                       if constexpr (SPLIT) {
+                                           const int tb = slot / 11;
+                                           if (slot - tb * 11 == 5) return (uint64_t) (((inFwd + inRev) >> (8 * tb)) & 0xFFu) | ((uint64_t) ((inRev >> (8 * tb)) & 0xFFu) << 32);
+                                       }
+                                       const uint32_t v = cntWords[slot * (64 / PER) + laneWord] >> laneShift; return (uint64_t) (v & ((1u << HB) - 1u)) | ((uint64_t) ((v >> HB) & ((1u << HB) - 1u)) << 32); },
                                    touched, keep, cov4);
             }
-            for (uint64_t m = touched; m; m &= m - 1) atomicAnd(&cntWords[(__ffsll((unsigned long long) m) - 1) * (64 / PER) + laneWord], laneClear);
+            // (SPLIT: the interior slots have no counter - their rows hold the mask words, cleared above)
+            for (uint64_t m = SPLIT ? touched & ~INTERIOR_SLOTS : touched; m; m &= m - 1) atomicAnd(&cntWords[(__ffsll((unsigned long long) m) - 1) * (64 / PER) + laneWord], laneClear);
+            if constexpr (SPLIT) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
             const uint64_t b0 = cdm_ballot((newCode & 1u) != 0), b1 = cdm_ballot((newCode & 2u) != 0);
             uint64_t nb = 0;
             if (qHasN) nb = cdm_ballot(p < qLen && keep && cdm_isN(a.nmask, qw, p));
@@ -621,15 +720,21 @@ int cdm_correct_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, co
         grid = perCu > 0 ? ctx->cuCount * perCu : residentGrid(kernel, 64 * FAST_WAVES, pad, ctx->cuCount, guess);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * FAST_WAVES), pad, s, a, list, nList);
     };
-    if (smallW == 8) launchFast(k_correct_fast<15, uint8_t, 8>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
-    else if (smallW == 5) launchFast(k_correct_fast<15, uint8_t, 5>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
-    else if (smallW) launchFast(k_correct_fast<15, uint8_t, 6>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    if (smallW == 8) launchFast(k_correct_fast<15, uint8_t, 8, false>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    else if (smallW == 5) launchFast(k_correct_fast<15, uint8_t, 5, false>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
+    else if (smallW) launchFast(k_correct_fast<15, uint8_t, 6, false>, blocks * 2, activeSmall.p, counters.p + 3, grids[0]);
     // CDM_CORRECT_BIGW (experiments): blocks per CU of the 16..64-record instance.  5 (the default) with the pool that leaves room for five,
     // 4 with a pool for every record at full length; 6 does not fit the LDS with any pool and selects the default instance.
     const char *bigEnv = cdmGetenv("CDM_CORRECT_BIGW");
     const int bigW = bigEnv ? atoi(bigEnv) : 5;
-    if (bigW == 4) launchFast(k_correct_fast<64, uint16_t, 4>, blocks, activeFast.p, counters.p + 2, grids[1]);
-    else launchFast(k_correct_fast<64, uint16_t, 5>, blocks * 2, activeFast.p, counters.p + 2, grids[1]);
+    // CDM_CORRECT_PILEUP=joint|split (A/B runs and tests): the pile-up loop of that instance, split by damage class (the default) or every
+    // column through the LDS counters.  The instance of up to 15 records has 8-bit counters and the joint loop alone.
+    const char *pileEnv = cdmGetenv("CDM_CORRECT_PILEUP");
+    const bool split = !(pileEnv && std::string(pileEnv) == "joint");
+    if (bigW == 4 && split) launchFast(k_correct_fast<64, uint16_t, 4, true>, blocks, activeFast.p, counters.p + 2, grids[1]);
+    else if (bigW == 4) launchFast(k_correct_fast<64, uint16_t, 4, false>, blocks, activeFast.p, counters.p + 2, grids[1]);
+    else if (split) launchFast(k_correct_fast<64, uint16_t, 5, true>, blocks * 2, activeFast.p, counters.p + 2, grids[1]);
+    else launchFast(k_correct_fast<64, uint16_t, 5, false>, blocks * 2, activeFast.p, counters.p + 2, grids[1]);
     grids[2] = residentGrid(k_correct, 64 * WAVES_PER_BLOCK, 0, ctx->cuCount, blocks / 2);
     hipLaunchKernelGGL(k_correct, dim3(grids[2]), dim3(64 * WAVES_PER_BLOCK), 0, s, a);
     hipEventRecord(ctx->ev1, s);
