@@ -28,6 +28,8 @@
 
 #include "carpedeam_hip.h"
 #include "mmdb.h"
+#include "modules.h"
+#include "records.h"
 
 namespace {
 // ---- NucleotideMatrix: letters -> A,C,T,G,X = 0..4 (NucleotideMatrix.cpp:17-61), scores of nucleotide.out (+2 / -3, X row -3)
@@ -241,21 +243,6 @@ bool canBeCovered(float covThr, int covMode, float ql, float tl) {      // Util.
     }
 }
 bool hasCoverage(float covThr, int covMode, float qc, float tc) { switch (covMode) { case 0: return qc >= covThr && tc >= covThr; case 2: return qc >= covThr; case 1: return tc >= covThr; default: return true; } }
-char *seqIdText(float s, char *p) {     // Util::fastSeqIdToBuffer (Util.cpp:278-307)
-    if (s == 1.0) { memcpy(p, "1.00", 4); return p + 4; }
-    *p++ = '0'; *p++ = '.';
-    if (s < 0.10) *p++ = '0';
-    if (s < 0.01) *p++ = '0';
-    return itoa((int) (s * 1000), p);
-}
-}  // namespace
-
-struct AlignParams {       // (host/main.cpp holds the same declaration)
-    float covThr = 0.f, seqIdThr = 0.f; double evalThr = 0.001; int covMode = 0, seqIdMode = 0, alnLenThr = 0; bool wrapped = false, includeIdentity = false;
-    int gapOpen = 5, gapExtend = 2, zdrop = 40; unsigned maxAccept = INT_MAX, maxReject = INT_MAX; size_t maxSeqLen = 65535;
-};
-
-namespace {
 // a hit between the seed and its record: what the seed (no extension needed), the host's extension or the device's gave
 struct Pending { uint32_t dbKey; int qL, tL, origLen; bool isReverse, isIdentity, onDevice; int score1, qs1, qe1, ds1, de1, aaIds; unsigned btLen; };
 struct ThreadWork {

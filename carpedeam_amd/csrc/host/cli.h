@@ -45,6 +45,7 @@ inline void checkFlags(const char *module, const Args &a, const FlagSpec *spec, 
 }
 inline float fflag(Args &a, const char *n, float d) { return a.flag.count(n) ? strtof(a.flag[n].c_str(), NULL) : d; }
 inline long iflag(Args &a, const char *n, long d) { return a.flag.count(n) ? strtol(a.flag[n].c_str(), NULL, 10) : d; }
+inline double dflag(Args &a, const char *n, double d) { return a.flag.count(n) ? strtod(a.flag[n].c_str(), NULL) : d; }
 // an integer flag with the values the device path takes: lo to hi, or the module refuses it with `what`
 inline long rangedFlag(Args &a, const char *module, const char *flag, long dflt, long lo, long hi, const char *what) {
     const long v = iflag(a, flag, dflt);
@@ -72,12 +73,18 @@ inline cdm_ctx *openCtx(int offset = 0) {
     check(cdm_ctx_create((dev ? atoi(dev) : 0) + offset, &ctx), "Can not initialise the MI355X device");
     return ctx;
 }
-inline cdm_seqdb *uploadSeqDb(cdm_ctx *ctx, const MmDb &db) {
-    if ((db.dbtype & 0x7FFFFFFF) != 1) unsupported("The MI355X path works on nucleotide sequence DBs only (dbtype " + std::to_string(db.dbtype & 0x7FFFFFFF) + " given)");
+// the sequences of a text DB on the device: 0 and *out, or an exit status (77: not a nucleotide DB, refused before the text is touched) and its message
+inline int seqDbToDevice(cdm_ctx *ctx, const MmDb &db, cdm_seqdb **out, std::string *msg) {
+    if ((db.dbtype & 0x7FFFFFFF) != 1) { *msg = "The MI355X path works on nucleotide sequence DBs only (dbtype " + std::to_string(db.dbtype & 0x7FFFFFFF) + " given)"; return 77; }
     std::vector<uint32_t> lens(db.size());
     for (size_t i = 0; i < db.size(); i++) lens[i] = db.len[i] >= 2 ? (uint32_t) (db.len[i] - 2) : 0;   // DBReader::getSeqLen
-    cdm_seqdb *h = NULL;
-    check(cdm_seqdb_upload(ctx, db.data(), db.off.data(), lens.data(), db.key.data(), db.ext.data(), db.size(), &h), "Can not load the sequence DB");
+    if (cdm_seqdb_upload(ctx, db.data(), db.off.data(), lens.data(), db.key.data(), db.ext.data(), db.size(), out) == CDM_OK) return 0;
+    *msg = std::string("Can not load the sequence DB: ") + cdm_last_error();
+    return EXIT_FAILURE;
+}
+inline cdm_seqdb *uploadSeqDb(cdm_ctx *ctx, const MmDb &db) {
+    cdm_seqdb *h = NULL; std::string msg;
+    if (const int rc = seqDbToDevice(ctx, db, &h, &msg)) { if (rc == 77) unsupported(msg); die(msg); }
     return h;
 }
 inline bool writeText(const std::string &path, const std::string &text) {

@@ -22,6 +22,7 @@
 #include <unistd.h>
 
 #include "mmdb.h"
+#include "modules.h"
 
 namespace {
 bool exists(const std::string &p) { struct stat st; return lstat(p.c_str(), &st) == 0; }

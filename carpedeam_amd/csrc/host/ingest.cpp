@@ -25,6 +25,7 @@
 #include <zlib.h>
 
 #include "mmdb.h"
+#include "modules.h"
 
 namespace {
 struct Entries {

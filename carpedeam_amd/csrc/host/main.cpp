@@ -14,11 +14,9 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <numeric>
 #include <omp.h>
 #include <unistd.h>
@@ -40,25 +38,8 @@
 #include "sidecar.h"
 #include "cli.h"
 #include "contig_reports.h"
-
-// host/ingest.cpp
-int createdbModule(const std::vector<std::string> &files, const std::string &outPath, bool shuffle, int dbType, std::string *err);
-int convert2fastaModule(const std::string &dbPath, const std::string &outPath, std::string *err);
-int createhdbModule(const std::string &seqPath, const std::string &cyclePath, const std::string &outPath, std::string *err);
-// host/cluster.cpp: the host-side modules of linclust's tail and the workflow scripts' file modules (status 77: a mode that is not implemented)
-int clustModule(const std::string &seqPath, const std::string &alnPath, const std::string &outPath, int mode, std::string *err);
-int createsubdbModule(const std::string &orderArg, const std::string &inPath, const std::string &outPath, int subDbMode, std::string *err);
-int filterdbModule(const std::string &inPath, const std::string &outPath, const std::string &filterFile, std::string *err);
-int mergeclustersModule(const std::string &seqPath, const std::string &outPath, const std::vector<std::string> &steps, std::string *err);
-int result2repseqModule(const std::string &seqPath, const std::string &cluPath, const std::string &outPath, std::string *err);
-int rmdbModule(const std::string &db);
-// host/align.cpp: linclust's gapped alignment step on the assembled contigs
-struct AlignParams {
-    float covThr = 0.f, seqIdThr = 0.f; double evalThr = 0.001; int covMode = 0, seqIdMode = 0, alnLenThr = 0; bool wrapped = false, includeIdentity = false;
-    int gapOpen = 5, gapExtend = 2, zdrop = 40; unsigned maxAccept = INT_MAX, maxReject = INT_MAX; size_t maxSeqLen = 65535;
-};
-int alignModule(const std::string &qPath, const std::string &tPath, const std::string &prefPath, const std::string &outPath, const AlignParams &P, std::string *err);
-int mvdbModule(const std::string &src, const std::string &dst, std::string *err);
+#include "modules.h"
+#include "records.h"
 
 namespace {
 Args parse(int argc, char **argv) {
@@ -264,12 +245,10 @@ struct DeviceStart {
             if (cdm_ctx_create(dev ? atoi(dev) : 0, &ctx) != CDM_OK) return fail(EXIT_FAILURE, std::string("Can not initialise the MI355X device: ") + cdm_last_error());
             if (damagePrefix && cdm_damage_load(ctx, damagePrefix->c_str()) != CDM_OK) return fail(EXIT_FAILURE, std::string("Profile not 12 fields: ") + cdm_last_error());
             if (!seq) return;
-            if ((seq->dbtype & 0x7FFFFFFF) != 1) return fail(77, "The MI355X path works on nucleotide sequence DBs only (dbtype " + std::to_string(seq->dbtype & 0x7FFFFFFF) + " given)");
-            if (side) { if (!importSeqSide(ctx, *side, &db)) fail(EXIT_FAILURE, std::string("Can not load the sequence DB: ") + cdm_last_error()); return; }
-            std::vector<uint32_t> lens(seq->size());
-            for (size_t i = 0; i < seq->size(); i++) lens[i] = seq->len[i] >= 2 ? (uint32_t) (seq->len[i] - 2) : 0;   // DBReader::getSeqLen
-            if (cdm_seqdb_upload(ctx, seq->data(), seq->off.data(), lens.data(), seq->key.data(), seq->ext.data(), seq->size(), &db) != CDM_OK)
-                return fail(EXIT_FAILURE, std::string("Can not load the sequence DB: ") + cdm_last_error());
+            // (a side-car of another dbtype goes the text's way, which refuses the dbtype before it looks at the text that was never mapped)
+            if (side && (seq->dbtype & 0x7FFFFFFF) == 1) { if (!importSeqSide(ctx, *side, &db)) fail(EXIT_FAILURE, std::string("Can not load the sequence DB: ") + cdm_last_error()); return; }
+            std::string msg;
+            if (const int rc = seqDbToDevice(ctx, *seq, &db, &msg)) fail(rc, msg);
         });
         g_deviceThread = &th;
     }
@@ -279,41 +258,47 @@ struct DeviceStart {
         if (code) { fprintf(stderr, "%s\n", err.c_str()); exit(code); }
     }
 };
+// The index columns of a device DB (n > 0) as a data file lays its entries out - "SEQ\n\0" each, entry i at offs[i] with elen[i] bytes, the
+// NUL among them; fill() returns the bytes of them all
+struct SeqDbLayout {
+    HVec<uint32_t> keys, elen; HVec<uint8_t> ext; HVec<uint64_t> offs;
+    uint64_t fill(cdm_ctx *ctx, cdm_seqdb *h) {
+        const uint64_t n = cdm_seqdb_size(h);
+        keys.resize(n); elen.resize(n); ext.resize(n); offs.resize(n);
+        check(cdm_seqdb_meta(ctx, h, elen.data(), keys.data(), ext.data()), "meta");
+        uint64_t tot = 0;
+        for (uint64_t i = 0; i < n; i++) { offs[i] = tot; elen[i] += 2; tot += elen[i]; }
+        return tot;
+    }
+};
 // the entries of a device DB as DB payloads ("SEQ\n"), appended to c
 void appendEntries(cdm_ctx *ctx, cdm_seqdb *h, OutChunk &c) {
     const uint64_t n = cdm_seqdb_size(h);
     if (n == 0) return;
-    std::vector<uint32_t> lens(n), keys(n); std::vector<uint8_t> ext(n);
-    check(cdm_seqdb_meta(ctx, h, lens.data(), keys.data(), ext.data()), "meta");
-    std::vector<uint64_t> offs(n); uint64_t tot = 0;
-    for (uint64_t i = 0; i < n; i++) { offs[i] = tot; tot += lens[i] + 2; }
+    SeqDbLayout l; const uint64_t tot = l.fill(ctx, h);
     HVec<char> buf(tot);
-    check(cdm_seqdb_download(ctx, h, buf.data(), offs.data()), "download");
+    check(cdm_seqdb_download(ctx, h, buf.data(), l.offs.data()), "download");
     c.reserve(c.key.size() + n, c.data.size() + tot);
-    for (uint64_t i = 0; i < n; i++) c.add(keys[i], buf.data() + offs[i], lens[i] + 1, ext[i]);
+    for (uint64_t i = 0; i < n; i++) c.add(l.keys[i], buf.data() + l.offs[i], l.elen[i] - 1, l.ext[i]);
 }
 // a device DB as a text DB (+ its side-car): down() takes everything off the device, write() needs the device no more
 struct SeqDbOut {
-    uint64_t n = 0; HVec<uint32_t> keys, elen; HVec<uint8_t> ext; HVec<uint64_t> offs; HVec<char> buf; SeqSideHost side;
+    uint64_t n = 0; SeqDbLayout l; HVec<char> buf; SeqSideHost side;
     void down(cdm_ctx *ctx, cdm_seqdb *h) {
         n = cdm_seqdb_size(h);
         if (n == 0) return;
-        std::vector<uint32_t> lens(n);
-        keys.resize(n); ext.resize(n);
-        check(cdm_seqdb_meta(ctx, h, lens.data(), keys.data(), ext.data()), "meta");
         // the download buffer has the data file's layout already: "SEQ\n\0" per entry (the NULs are the buffer's zero fill)
-        offs.resize(n); elen.resize(n); uint64_t tot = 0;
-        for (uint64_t i = 0; i < n; i++) { offs[i] = tot; elen[i] = lens[i] + 2; tot += lens[i] + 2; }
+        const uint64_t tot = l.fill(ctx, h);
         buf.resize(tot);
         buf[tot - 1] = '\0';           // the download writes [0, tot - 1): "SEQ\n" per entry and the NULs between them; the last entry's NUL is ours
-        check(cdm_seqdb_download(ctx, h, buf.data(), offs.data()), "download");
+        check(cdm_seqdb_download(ctx, h, buf.data(), l.offs.data()), "download");
         side.take(ctx, h);
     }
     void write(const std::string &path, int dbtype) {
         std::string err;
         if (n == 0) { if (!mmdbWriteChunks(path, dbtype, std::vector<OutChunk>(1), &err)) die(err); return; }
         side.begin(path, dbtype);       // (beside the text: other files)
-        if (!mmdbWriteBlob(path, dbtype, buf.data(), buf.size(), keys.data(), offs.data(), elen.data(), ext.data(), n, &err)) die(err);
+        if (!mmdbWriteBlob(path, dbtype, buf.data(), buf.size(), l.keys.data(), l.offs.data(), l.elen.data(), l.ext.data(), n, &err)) die(err);
         side.commit();
     }
 };
@@ -325,16 +310,13 @@ static int seqDbPieceSink(void *user, const char *data, uint64_t offset, uint64_
 bool streamSeqDb(cdm_ctx *ctx, cdm_seqdb *h, const std::string &path, int dbtype) {
     const uint64_t n = cdm_seqdb_size(h);
     if (n == 0) return false;
-    HVec<uint32_t> keys(n), elen(n); HVec<uint8_t> ext(n); HVec<uint64_t> offs(n); std::vector<uint32_t> lens(n);
-    check(cdm_seqdb_meta(ctx, h, lens.data(), keys.data(), ext.data()), "meta");
-    uint64_t tot = 0;
-    for (uint64_t i = 0; i < n; i++) { offs[i] = tot; elen[i] = lens[i] + 2; tot += lens[i] + 2; }
+    SeqDbLayout l; const uint64_t tot = l.fill(ctx, h);
     int fd = mmdbOpenStreamedData(path, tot);
     if (fd < 0) return false;
     SeqSideHost side; side.take(ctx, h); side.begin(path, dbtype);
     bool okIx = true; std::string errIx;
-    std::thread ix([&] { okIx = mmdbWriteBlob(path, dbtype, nullptr, 0, keys.data(), offs.data(), elen.data(), ext.data(), n, &errIx, MMDB_DATA_ELSEWHERE); });
-    const int rc = cdm_seqdb_download_stream(ctx, h, offs.data(), 64u << 20, seqDbPieceSink, &fd);
+    std::thread ix([&] { okIx = mmdbWriteBlob(path, dbtype, nullptr, 0, l.keys.data(), l.offs.data(), l.elen.data(), l.ext.data(), n, &errIx, MMDB_DATA_ELSEWHERE); });
+    const int rc = cdm_seqdb_download_stream(ctx, h, l.offs.data(), 64u << 20, seqDbPieceSink, &fd);
     const bool okClose = close(fd) == 0;
     ix.join();
     if (rc != CDM_OK) die(std::string("download: ") + cdm_last_error());
@@ -344,110 +326,6 @@ bool streamSeqDb(cdm_ctx *ctx, cdm_seqdb *h, const std::string &path, int dbtype
     return true;
 }
 void writeSeqDb(cdm_ctx *ctx, cdm_seqdb *h, const std::string &path, int dbtype) { if (streamSeqDb(ctx, h, path, dbtype)) return; SeqDbOut o; o.down(ctx, h); o.write(path, dbtype); }
-// ---- text codecs
-// ---- parsers for the tab-separated records (strtol / strtod walk the locale machinery: 10x the time of these)
-// unsigned / signed decimal at d; d moves behind the digits (no digits: 0, as strtol gives)
-inline unsigned long parseU(const char *&d) { unsigned long v = 0; while (*d >= '0' && *d <= '9') v = v * 10 + (unsigned long) (*d++ - '0'); return v; }
-inline long parseI(const char *&d) { bool neg = false; if (*d == '-') { neg = true; d++; } else if (*d == '+') d++; const long v = (long) parseU(d); return neg ? -v : v; }
-// a plain decimal "digits[.digits]" with at most 15 significant digits is mantissa / 10^k, both exact doubles: the division is
-// correctly rounded, i.e. the very double strtod returns.  Anything else (exponents, inf, nan, long mantissas) goes to strtod.
-inline double parseDecimal(const char *&d) {
-    static const double P10[] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15};
-    const char *p = d; unsigned long m = 0; int digits = 0, frac = 0;
-    while (*p >= '0' && *p <= '9') { m = m * 10 + (unsigned long) (*p++ - '0'); digits++; }
-    if (*p == '.') { p++; while (*p >= '0' && *p <= '9') { m = m * 10 + (unsigned long) (*p++ - '0'); digits++; frac++; } }
-    if (digits == 0 || digits > 15 || *p == 'e' || *p == 'E' || (*p != '\t' && *p != '\n' && *p != '\0')) { char *e; const double v = strtod(d, &e); d = e; return v; }
-    d = p;
-    return (double) m / P10[frac];
-}
-inline void skipField(const char *&d) { while (*d && *d != '\t' && *d != '\n') d++; }
-char *seqIdText(float s, char *p) {   // Util::fastSeqIdToBuffer + the tab overwriting its last char (Util.cpp:278-307, Matcher.cpp:362-363)
-    if (s == 1.0) { memcpy(p, "1.00", 4); return p + 4; }
-    *p++ = '0'; *p++ = '.';
-    if (s < 0.10) *p++ = '0';
-    if (s < 0.01) *p++ = '0';
-    return itoa((int) (s * 1000), p);
-}
-// contiguous slice [lo, hi) of n items for thread t of T
-inline void sliceOf(size_t n, int t, int T, size_t &lo, size_t &hi) { lo = n * (size_t) t / T; hi = n * (size_t) (t + 1) / T; }
-// Slices of the queries that carry about the same number of RECORDS each (off = CSR offsets of the records; a query costs one more
-// unit).  The record lists are anything but even: kmermatcher's representatives - the longest, lowest-id sequences - hold the hits of
-// whole k-mer groups, so at 10 M reads the first sixteenth of the queries owned most of the text and threads beyond the first
-// added nothing.
-inline std::vector<size_t> balancedSlices(const uint64_t *off, size_t n, int T) {
-    std::vector<size_t> b(T + 1, n);
-    b[0] = 0;
-    const uint64_t total = off[n] + n;
-    for (int t = 1; t < T; t++) {
-        const uint64_t want = total / (uint64_t) T * (uint64_t) t;
-        size_t lo = b[t - 1], hi = n;
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (off[mid] + mid < want) lo = mid + 1; else hi = mid; }
-        b[t] = lo;
-    }
-    return b;
-}
-// number of records (= lines) of entry i of a result DB
-inline uint32_t countLines(const MmDb &db, int64_t i) {
-    if (i < 0) return 0;
-    const char *d = db.entry((size_t) i), *e = d + (db.len[(size_t) i] ? db.len[(size_t) i] - 1 : 0);
-    uint32_t n = 0;
-    while (d < e) { const char *nl = (const char *) memchr(d, '\n', (size_t) (e - d)); n++; d = nl ? nl + 1 : e; }
-    return n;
-}
-// CSR offsets of the queries' record lists: the lines are counted first (memchr speed), the records then go straight to their place
-void countRecords(const MmDb &res, const MmDb &seq, HVec<uint64_t> &off) {
-    const size_t n = seq.size();
-    off.resize(n + 1);
-    off[0] = 0;
-#pragma omp parallel for schedule(dynamic, 4096)
-    for (size_t i = 0; i < n; i++) off[i + 1] = countLines(res, res.idOf(seq.key[i]));
-    for (size_t i = 0; i < n; i++) off[i + 1] += off[i];
-}
-void parseAlnDb(const MmDb &aln, const MmDb &seq, HVec<uint64_t> &off, HVec<cdm_aln> &rec) {   // Matcher.cpp:274-353
-    const double lam = 0x1.4478764a1b24ap-1, logk = log(0x1.a1c1e68ea2ab1p-2), LN2 = std::log(2.0);
-    const int T = std::max(1, omp_get_max_threads());
-    countRecords(aln, seq, off);
-    rec.resize(off[seq.size()]);
-    long badKey = -1, badEntry = -1;
-    const std::vector<size_t> cut = balancedSlices(off.data(), seq.size(), T);
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
-    for (int t = 0; t < T; t++) {
-        const size_t lo = cut[t], hi = cut[t + 1];
-        for (size_t i = lo; i < hi; i++) {
-            if (off[i + 1] == off[i]) continue;
-            const char *d = aln.entry((size_t) aln.idOf(seq.key[i]));
-            cdm_aln *out = rec.data() + off[i], *const end = rec.data() + off[i + 1];
-            while (*d && out < end) {
-                cdm_aln r;
-                auto tab = [&] { if (*d == '\t') d++; };
-                const uint32_t tkey = (uint32_t) parseU(d); tab();
-                const int bits = (int) parseI(d); tab();
-                r.seq_id = (float) parseDecimal(d); tab();
-                skipField(d); tab();                                   // the E-value is not read back
-                r.q_start = (int) parseI(d); tab(); r.q_end = (int) parseI(d); tab(); skipField(d); tab();
-                r.db_start = (int) parseI(d); tab(); r.db_end = (int) parseI(d); tab(); skipField(d);
-                const int64_t tt = seq.idOf(tkey);
-                if (tt < 0) {
-#pragma omp critical
-                    badKey = (long) tkey;
-                    break;
-                }
-                r.target = (uint32_t) tt; r.ident = -1;
-                r.raw_score = static_cast<int>((logk + bits * LN2) / lam + 0.5);   // computeRawScoreFromBitScore as the consumers do
-                *out++ = r;
-                while (*d && *d != '\n') d++;
-                if (*d == '\n') d++;
-            }
-            // the index length and the entry's NUL must agree (an embedded NUL or a wrong length would leave records unparsed or unfilled)
-            if (badKey < 0 && (out != end || *d)) {
-#pragma omp critical
-                badEntry = (long) seq.key[i];
-            }
-        }
-    }
-    if (badKey >= 0) die("Invalid database read for key " + std::to_string(badKey));
-    if (badEntry >= 0) die("Invalid database read: the entry of key " + std::to_string(badEntry) + " does not end where its index length says");
-}
 cdm_ancient_params ancientParams(Args &a) {
     cdm_ancient_params p;
     p.seq_id_thr = fflag(a, "--min-seq-id", 0.9f); p.corr_reads_ry_seq_id = fflag(a, "--min-ryseq-id-corr-reads", 0.99f); p.ry_seq_id_thr = 0.99f;
@@ -456,232 +334,6 @@ cdm_ancient_params ancientParams(Args &a) {
     p.min_cov_safe = (int) iflag(a, "--min-cov-safe", 5); p.max_seq_len = (uint64_t) iflag(a, "--max-seq-len", 65535);
     return p;
 }
-
-// QueryMatcher::prefilterHitToBuffer per hit, one DB entry per query (kmermatcher.cpp:815-930)
-void formatPrefDb(const MmDb &seq, const uint64_t *off, const cdm_hit *rec, std::vector<OutChunk> &chunks) {
-    const int T = std::max(1, omp_get_max_threads());
-    chunks.clear(); chunks.resize(T);
-    const size_t MAXREC = 10 + 1 + 11 + 1 + 6 + 1;      // "%u\t%d\t%d\n" with a short diagonal
-    const std::vector<size_t> cut = balancedSlices(off, seq.size(), T);
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
-    for (int t = 0; t < T; t++) {
-        const size_t lo = cut[t], hi = cut[t + 1];
-        OutChunk &c = chunks[t];
-        c.reserve(hi - lo, (off[hi] - off[lo]) * MAXREC + (hi - lo));
-        for (size_t i = lo; i < hi; i++) {
-            char *const w0 = c.open((off[i + 1] - off[i]) * MAXREC), *w = w0;
-            for (uint64_t h = off[i]; h < off[i + 1]; h++) {   // QueryMatcher::prefilterHitToBuffer
-                w = utoa(seq.keyOf(rec[h].target), w); *w++ = '\t'; w = itoa(rec[h].score, w); *w++ = '\t'; w = itoa((short) rec[h].diagonal, w); *w++ = '\n';
-            }
-            // representatives' records carry wasExtended 0, fill-in records the sequence's flag (kmermatcher.cpp:727, DBWriter default)
-            c.close(seq.key[i], w0, w, (off[i + 1] - off[i] > 1) ? 0 : seq.ext[i]);
-        }
-    }
-}
-// QueryMatcher::parsePrefilterHits: the prefilter text as CSR over the query ids
-void parsePrefDb(const MmDb &pref, const MmDb &seq, HVec<uint64_t> &off, HVec<cdm_hit> &rec) {
-    const int T = std::max(1, omp_get_max_threads());
-    countRecords(pref, seq, off);
-    rec.resize(off[seq.size()]);
-    long badKey = -1, badEntry = -1;
-    const std::vector<size_t> cut = balancedSlices(off.data(), seq.size(), T);
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
-    for (int t = 0; t < T; t++) {
-        const size_t lo = cut[t], hi = cut[t + 1];
-        for (size_t i = lo; i < hi; i++) {
-            if (off[i + 1] == off[i]) continue;
-            const char *d = pref.entry((size_t) pref.idOf(seq.key[i]));
-            cdm_hit *out = rec.data() + off[i], *const end = rec.data() + off[i + 1];
-            while (*d && out < end) {
-                cdm_hit h;
-                const uint32_t tkey = (uint32_t) parseU(d); if (*d == '\t') d++; h.score = (int) parseI(d); if (*d == '\t') d++; h.diagonal = (short) parseI(d);
-                const int64_t tt = seq.idOf(tkey);
-                if (tt < 0) {
-#pragma omp critical
-                    badKey = (long) tkey;
-                    break;
-                }
-                h.target = (uint32_t) tt; *out++ = h;
-                while (*d && *d != '\n') d++;
-                if (*d == '\n') d++;
-            }
-            if (badKey < 0 && (out != end || *d)) {
-#pragma omp critical
-                badEntry = (long) seq.key[i];
-            }
-        }
-    }
-    if (badKey >= 0) die("Invalid database read for key " + std::to_string(badKey));
-    if (badEntry >= 0) die("Invalid database read: the entry of key " + std::to_string(badEntry) + " does not end where its index length says");
-}
-// Matcher::resultToBuffer per record, one DB entry per query that has a prefilter entry (rescorediagonal.cpp:145-356)
-// (asParsed, if given: every record as parseAlnDb would read it back from the text written here - raw score recomputed from the bit
-// score, the coordinates, and in `ident` the identity in thousandths as the text truncates it: what writeAlnsSide takes.
-// pref == NULL: every query has a prefilter entry - the hits came from kmermatcher's own side-car.)
-void formatAlnDb(const MmDb &seq, const MmDb *pref, const uint64_t *aoff, const cdm_aln *arec, uint64_t dbRes, std::vector<OutChunk> &chunks, cdm_aln *asParsed = NULL) {
-    const double lam = 0x1.4478764a1b24ap-1, logk = log(0x1.a1c1e68ea2ab1p-2), LN2 = std::log(2.0);
-    const int T = std::max(1, omp_get_max_threads());
-    chunks.clear(); chunks.resize(T);
-    const size_t MAXREC = 10 + 11 + 5 + 14 + 6 * 11 + 10;      // key, bits, seq.id., E-value, six coordinates, separators
-    const std::vector<size_t> cut = balancedSlices(aoff, seq.size(), T);
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
-    for (int t = 0; t < T; t++) {
-        const size_t lo = cut[t], hi = cut[t + 1];
-        OutChunk &c = chunks[t];
-        c.reserve(hi - lo, (aoff[hi] - aoff[lo]) * MAXREC + (hi - lo));
-        // the E-value text and bit score of (raw score, query length) recur all over a read set: formatted once per thread
-        struct EvalText { int qLen = -1, score = -1, bits = 0; unsigned char n = 0; char txt[15]; };
-        std::vector<EvalText> cache(1u << 14);
-        for (size_t i = lo; i < hi; i++) {
-            if (pref && pref->idOf(seq.key[i]) < 0) continue;
-            const int qLen = (int) (seq.len[i] - 2);
-            char *const w0 = c.open((aoff[i + 1] - aoff[i]) * MAXREC), *w = w0;
-            for (uint64_t r = aoff[i]; r < aoff[i + 1]; r++) {   // Matcher::resultToBuffer (Matcher.cpp:356-404)
-                const cdm_aln &x = arec[r];
-                if (r + 16 < aoff[hi]) __builtin_prefetch(&seq.len[arec[r + 16].target]);      // (a random look-up per record: on its way 16 records ahead)
-                const int alnLen = std::max(abs(x.q_end - x.q_start), abs(x.db_end - x.db_start)) + 1;
-                const float sid = static_cast<float>(x.ident) / static_cast<float>(alnLen);
-                w = utoa(seq.keyOf(x.target), w); *w++ = '\t';
-                EvalText &ev = cache[((uint32_t) x.raw_score * 2654435761u ^ (uint32_t) qLen * 40503u) >> 18];
-                if (ev.qLen != qLen || ev.score != x.raw_score) {
-                    ev.qLen = qLen; ev.score = x.raw_score; ev.bits = cdm_bit_score(x.raw_score);
-                    ev.n = (unsigned char) snprintf(ev.txt, sizeof(ev.txt), "%.3E", cdm_evalue(x.raw_score, qLen, dbRes));
-                }
-                w = itoa(ev.bits, w); *w++ = '\t';
-                w = seqIdText(sid, w); *w++ = '\t';
-                memcpy(w, ev.txt, ev.n); w += ev.n; *w++ = '\t';
-                w = itoa(x.q_start, w); *w++ = '\t'; w = itoa(x.q_end, w); *w++ = '\t'; w = itoa(qLen, w); *w++ = '\t';
-                w = itoa(x.db_start, w); *w++ = '\t'; w = itoa(x.db_end, w); *w++ = '\t'; w = itoa((int) (seq.len[x.target] - 2), w); *w++ = '\n';
-                if (asParsed) {
-                    cdm_aln p = x;
-                    p.raw_score = static_cast<int>((logk + ev.bits * LN2) / lam + 0.5); p.ident = (int) seqIdTo1000(sid); p.seq_id = seqIdFrom1000((uint32_t) p.ident);
-                    asParsed[r] = p;
-                }
-            }
-            c.close(seq.key[i], w0, w, 0);
-        }
-    }
-}
-
-// the same records for the result of the Hamming mode: one entry per query that has a prefilter entry (rescorediagonal.cpp:350), flag 0
-void formatRescoredPrefDb(const MmDb &seq, const MmDb &pref, const uint64_t *off, const cdm_hit *rec, std::vector<OutChunk> &chunks) {
-    const int T = std::max(1, omp_get_max_threads());
-    chunks.clear(); chunks.resize(T);
-    const size_t MAXREC = 10 + 1 + 11 + 1 + 6 + 1;
-    const std::vector<size_t> cut = balancedSlices(off, seq.size(), T);
-#pragma omp parallel for schedule(static, 1) num_threads(T)     // a loop over the slices: a smaller team still visits them all
-    for (int t = 0; t < T; t++) {
-        const size_t lo = cut[t], hi = cut[t + 1];
-        OutChunk &c = chunks[t];
-        c.reserve(hi - lo, (off[hi] - off[lo]) * MAXREC + (hi - lo));
-        for (size_t i = lo; i < hi; i++) {
-            if (pref.idOf(seq.keyOf(i)) < 0) continue;
-            char *const w0 = c.open((off[i + 1] - off[i]) * MAXREC), *w = w0;
-            for (uint64_t h = off[i]; h < off[i + 1]; h++) {
-                w = utoa(seq.keyOf(rec[h].target), w); *w++ = '\t'; w = itoa(rec[h].score, w); *w++ = '\t'; w = itoa((short) rec[h].diagonal, w); *w++ = '\n';
-            }
-            c.close(seq.keyOf(i), w0, w, 0);
-        }
-    }
-}
-
-// ---- record side-cars: the CSR a consumer's parser would produce from the text, as cdm_hits_upload / cdm_alns_upload take it
-bool writeHitsSide(const std::string &path, const MmDb &seq, const uint64_t *off, const cdm_hit *rec, int dbtype, SideHeader *hdr) {
-    if (!sideEnabled()) return false;
-    const uint64_t n = seq.size(), count = off[n];
-    bool fits = true;
-#pragma omp parallel for reduction(&& : fits) schedule(static)
-    for (uint64_t i = 0; i < count; i++) { cdm_hit h = rec[i]; h.diagonal = (short) h.diagonal; fits = fits && fitsHit8(h); }
-    const uint64_t hash = sideKeyHash(seq.key.data(), n);
-    if (fits) {
-        HVec<SideHit8> c(count);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < count; i++) { c[i].target = rec[i].target; c[i].score = (int16_t) rec[i].score; c[i].diagonal = (int16_t) (short) rec[i].diagonal; }
-        const SidePiece pc[2] = {{off, (n + 1) * 8}, {c.data(), count * sizeof(SideHit8)}};
-        return sideWriteBody(path, SIDE_HITS, SIDE_F_COMPACT, n, count, n, hash, dbtype, pc, 2, hdr);
-    } else {
-        HVec<cdm_hit> c(count);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < count; i++) { c[i] = rec[i]; c[i].diagonal = (short) rec[i].diagonal; }       // (the text holds the diagonal as a short: QueryMatcher.h:114-126)
-        const SidePiece pc[2] = {{off, (n + 1) * 8}, {c.data(), count * sizeof(cdm_hit)}};
-        return sideWriteBody(path, SIDE_HITS, 0, n, count, n, hash, dbtype, pc, 2, hdr);
-    }
-}
-// hits / alignments of the DB at `path` from its side-car if that belongs to these files and to this sequence DB
-bool readHitsSide(const std::string &path, const MmDb &seq, HVec<uint64_t> &off, HVec<cdm_hit> &rec, int *dbtype) {
-    SideFile f;
-    if (!sideOpen(path, SIDE_HITS, f)) return false;
-    const SideHeader &h = *f.h;
-    if (h.n != seq.size() || h.seqN != seq.size() || h.seqKeyHash != sideKeyHash(seq.key.data(), seq.size())) return false;
-    off.resize(h.n + 1); rec.resize(h.count);
-    memcpy(off.data(), f.section(0), (h.n + 1) * 8);
-    if (off[h.n] != h.count) return false;
-    if (h.flags & SIDE_F_COMPACT) {
-        const SideHit8 *c = (const SideHit8 *) f.section(1);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < h.count; i++) { rec[i].target = c[i].target; rec[i].score = c[i].score; rec[i].diagonal = c[i].diagonal; }
-    } else memcpy(rec.data(), f.section(1), h.count * sizeof(cdm_hit));
-    *dbtype = h.dbtype;
-    return true;
-}
-bool writeAlnsSide(const std::string &path, const MmDb &seq, const uint64_t *off, const cdm_aln *asParsed, SideHeader *hdr) {
-    if (!sideEnabled()) return false;
-    const uint64_t n = seq.size(), count = off[n];
-    bool fits = true;
-#pragma omp parallel for reduction(&& : fits) schedule(static)
-    for (uint64_t i = 0; i < count; i++) {
-        const cdm_aln &r = asParsed[i];
-        auto s16 = [](int v) { return v >= -32768 && v <= 32767; };
-        fits = fits && r.raw_score >= 0 && r.raw_score <= 65535 && s16(r.q_start) && s16(r.q_end) && s16(r.db_start) && s16(r.db_end);
-    }
-    const uint64_t hash = sideKeyHash(seq.key.data(), n);
-    if (fits) {
-        HVec<SideAln16> c(count);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < count; i++) {
-            const cdm_aln &r = asParsed[i];
-            c[i].target = r.target; c[i].rawScore = (uint16_t) r.raw_score; c[i].seqId1000 = (uint16_t) r.ident;       // (ident carries the identity in thousandths here, see formatAlnDb)
-            c[i].qStart = (int16_t) r.q_start; c[i].qEnd = (int16_t) r.q_end; c[i].dbStart = (int16_t) r.db_start; c[i].dbEnd = (int16_t) r.db_end;
-        }
-        const SidePiece pc[2] = {{off, (n + 1) * 8}, {c.data(), count * sizeof(SideAln16)}};
-        return sideWriteBody(path, SIDE_ALNS, SIDE_F_COMPACT, n, count, n, hash, 5, pc, 2, hdr);
-    } else {
-        const SidePiece pc[2] = {{off, (n + 1) * 8}, {asParsed, count * sizeof(cdm_aln)}};
-        return sideWriteBody(path, SIDE_ALNS, 0, n, count, n, hash, 5, pc, 2, hdr);
-    }
-}
-bool readAlnsSide(const std::string &path, const MmDb &seq, HVec<uint64_t> &off, HVec<cdm_aln> &rec) {
-    SideFile f;
-    if (!sideOpen(path, SIDE_ALNS, f)) return false;
-    const SideHeader &h = *f.h;
-    if (h.n != seq.size() || h.seqN != seq.size() || h.seqKeyHash != sideKeyHash(seq.key.data(), seq.size())) return false;
-    off.resize(h.n + 1); rec.resize(h.count);
-    memcpy(off.data(), f.section(0), (h.n + 1) * 8);
-    if (off[h.n] != h.count) return false;
-    if (h.flags & SIDE_F_COMPACT) {
-        const SideAln16 *c = (const SideAln16 *) f.section(1);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < h.count; i++) {
-            cdm_aln r;
-            r.target = c[i].target; r.raw_score = c[i].rawScore; r.ident = -1; r.q_start = c[i].qStart; r.q_end = c[i].qEnd; r.db_start = c[i].dbStart; r.db_end = c[i].dbEnd;
-            r.seq_id = seqIdFrom1000(c[i].seqId1000);
-            rec[i] = r;
-        }
-    } else {
-        const cdm_aln *c = (const cdm_aln *) f.section(1);
-#pragma omp parallel for schedule(static)
-        for (uint64_t i = 0; i < h.count; i++) { cdm_aln r = c[i]; r.seq_id = seqIdFrom1000((uint32_t) r.ident); r.ident = -1; rec[i] = r; }
-    }
-    return true;
-}
-
-// the record side-cars beside the text: their sections are built and written in a thread while the caller formats and writes the text DB
-struct SideThread {
-    std::thread th; SideHeader hdr; bool ok = false; std::string path;
-    template <typename F> void begin(const std::string &p, F body) { if (!sideEnabled()) return; path = p; th = std::thread([this, body] { ok = body(&hdr); }); }
-    void commit() { if (th.joinable()) { th.join(); if (ok) sideCommit(path, &hdr); } }
-};
-
 // the modules' parameters from their flags (kmermatcher; rescorediagonal's Hamming mode): ancient_assemble_fused reads them the same way
 cdm_kmer_params kmerParams(Args &a) {
     cdm_kmer_params p;
@@ -690,12 +342,15 @@ cdm_kmer_params kmerParams(Args &a) {
     p.include_only_extendable = (int) iflag(a, "--include-only-extendable", 0); p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.8f);
     return p;
 }
-cdm_hamming_params hammingParams(Args &a, bool reversePrefilter) {
-    cdm_hamming_params p;
-    p.seq_id_thr = fflag(a, "--min-seq-id", 0.0f); p.eval_thr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
+cdm_rescore_params rescoreParams(Args &a) {
+    cdm_rescore_params p;
+    p.seq_id_thr = fflag(a, "--min-seq-id", 0.0f); p.eval_thr = dflag(a, "-e", 0.001);
     p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.0f); p.seq_id_mode = (int) iflag(a, "--seq-id-mode", 0); p.min_aln_len = (int) iflag(a, "--min-aln-len", 0);
-    p.reverse_prefilter = reversePrefilter;
     return p;
+}
+cdm_hamming_params hammingParams(Args &a, bool reversePrefilter) {      // the same six flags and the prefilter's strand convention
+    const cdm_rescore_params r = rescoreParams(a);
+    return {r.seq_id_thr, r.eval_thr, r.cov_mode, r.cov_thr, r.seq_id_mode, r.min_aln_len, reversePrefilter};
 }
 int kmermatcher(Args &a) {
     if (a.pos.size() < 2) die("Usage: carpedeam kmermatcher <i:sequenceDB> <o:prefilterDB>");
@@ -771,9 +426,7 @@ int rescorediagonal(Args &a) {
     dev.join(); cdm_ctx *ctx = dev.ctx; cdm_seqdb *db = dev.db; laps.lap("(device context, sequences up: waited)");
     cdm_hits *hits = NULL; cdm_alns *alns = NULL;
     check(cdm_hits_upload(ctx, db, off.data(), rec.data(), &hits), "upload"); laps.lap("  (hits up)");
-    cdm_rescore_params p;
-    p.seq_id_thr = fflag(a, "--min-seq-id", 0.0f); p.eval_thr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
-    p.cov_mode = (int) iflag(a, "--cov-mode", 0); p.cov_thr = fflag(a, "-c", 0.0f); p.seq_id_mode = (int) iflag(a, "--seq-id-mode", 0); p.min_aln_len = (int) iflag(a, "--min-aln-len", 0);
+    cdm_rescore_params p = rescoreParams(a);
     check(cdm_rescore(ctx, db, hits, &p, &alns), "rescorediagonal"); laps.lap("  (kernels)");
     HVec<uint64_t> aoff(seq.size() + 1); HVec<cdm_aln> arec(cdm_alns_count(alns));
     check(cdm_alns_download(ctx, alns, aoff.data(), arec.data()), "download");
@@ -888,7 +541,7 @@ int clusterModules(const std::string &cmd, Args &a) {
     if (cmd == "align") {
         need(4, "align <i:queryDB> <i:targetDB> <i:resultDB> <o:alignmentDB>"); checkFlags("align", a, ALIGN_FLAGS);
         AlignParams P;
-        P.covThr = fflag(a, "-c", 0.0f); P.seqIdThr = fflag(a, "--min-seq-id", 0.0f); P.evalThr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
+        P.covThr = fflag(a, "-c", 0.0f); P.seqIdThr = fflag(a, "--min-seq-id", 0.0f); P.evalThr = dflag(a, "-e", 0.001);
         P.covMode = (int) iflag(a, "--cov-mode", 0); P.seqIdMode = (int) iflag(a, "--seq-id-mode", 0); P.alnLenThr = (int) iflag(a, "--min-aln-len", 0);
         P.wrapped = iflag(a, "--wrapped-scoring", 0) != 0;
         P.gapOpen = (int) nuclValue("--gap-open", 5); P.gapExtend = (int) nuclValue("--gap-extend", 2); P.zdrop = (int) iflag(a, "--zdrop", 40);
@@ -1049,7 +702,7 @@ void runLoop(const char *module, Args &a, const std::vector<std::string> &inputs
     kp.kmers_per_seq_scale = fflag(a, "--kmer-per-seq-scale-ancient", 0.2f); kp.hash_shift = (uint64_t) iflag(a, "--hash-shift", 67);
     kp.ignore_multi_kmer = 1; kp.include_only_extendable = (int) iflag(a, "--include-only-extendable-ancient-reads", 0); kp.cov_mode = 1; kp.cov_thr = 0.0f;
     cdm_rescore_params rp;
-    rp.seq_id_thr = fflag(a, "--min-seq-id", 0.9f); rp.eval_thr = a.flag.count("-e") ? strtod(a.flag["-e"].c_str(), NULL) : 0.001;
+    rp.seq_id_thr = fflag(a, "--min-seq-id", 0.9f); rp.eval_thr = dflag(a, "-e", 0.001);
     rp.cov_mode = 1; rp.cov_thr = 0.0f; rp.seq_id_mode = 0; rp.min_aln_len = 0;
     cdm_ancient_params ap = ancientParams(a);
     if (!a.flag.count("--max-seq-len")) ap.max_seq_len = 200000;   // setGuidedNuclAssemblerWorkflowDefaults (GuidedNuclassembler.cpp:29)
