@@ -62,7 +62,9 @@ def build(verbose=False):
         if p.returncode:
             raise RuntimeError("compile failed: " + " ".join(j))
     if jobs or not os.path.exists(LIB):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lgomp"]
+        # the soname lets whatever names the library as a dependency (the module binary, the tests' primitives harness) take the copy
+        # a process has loaded already - CDM_LIB, a tree at another path - instead of mapping a second one with a state of its own
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(LIB), "-o", LIB] + objs + ["-lgomp"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
             sys.stderr.write(r.stdout + r.stderr)

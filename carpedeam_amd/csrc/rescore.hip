@@ -446,6 +446,13 @@ int cdm_rescore_impl(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_hits *hits, co
     std::vector<int32_t> minScore(db->maxLen + 1, INT_MAX);
     for (uint32_t L = 1; L <= db->maxLen; L++) {
         if (!present[L]) continue;
+        // A score of 0 that passes -e: the reference then writes the alignment's constructor values (coordinates -1) for a hit that is no
+        // identity hit, after counting the byte in front of both sequences - undefined there, refused here.
+        if (cdm_evalue_host(0, L, db->residues) <= par->eval_thr) {
+            cdm_set_error("cdm_rescore: -e %g lets a score of 0 pass for sequences of %u letters (E-value %g): the records of such hits are undefined in the reference",
+                          par->eval_thr, L, cdm_evalue_host(0, L, db->residues));
+            return CDM_ERR_UNSUPPORTED;
+        }
         int lo = 0, hi = 2 * (int) L;   // E-value decreases with the score (tests/test_gpu_rescore.py checks it for the lengths used)
         if (!(cdm_evalue_host(hi, L, db->residues) <= par->eval_thr)) continue;
         while (lo < hi) { int mid = (lo + hi) / 2; if (cdm_evalue_host(mid, L, db->residues) <= par->eval_thr) hi = mid; else lo = mid + 1; }

@@ -278,6 +278,8 @@ typedef struct cdm_aln {
     float seq_id;     /* value a reader of the text record gets: (float)strtod(fastSeqIdToBuffer(ident/alnLen)) */
 } cdm_aln;
 
+/* CDM_ERR_UNSUPPORTED (the message names -e) when eval_thr lets a raw score of 0 pass for the length of any sequence in db, whether or not a
+ * hit has it as its query: the reference's record for such a hit that is no identity hit is undefined (coordinates -1, read outside both). */
 int cdm_rescore(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_hits *hits, const cdm_rescore_params *par, cdm_alns **out);
 /* What cdm_rescore keeps beside the records, and the size of its kernel's tile (for tests that place inputs on tile boundaries):
  * hits per block of the scoring kernel; the number of identity records written with the coordinates -1 (a sequence that scores 0

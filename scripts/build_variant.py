@@ -21,5 +21,7 @@ for src in srcs:
     mine.append(obj)
 objs = [os.path.join(B.OBJ, f) for f in sorted(os.listdir(B.OBJ)) if f.endswith(".o") and f[:-2] not in srcs] + mine
 lib = os.path.join(out_dir, "libcarpedeam_hip_%s.so" % tag)
-subprocess.run([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-lgomp"], check=True, capture_output=True)
+# the regular library's soname, whatever the file is called: a process that loaded this variant through CDM_LIB hands it to whatever
+# names libcarpedeam_hip.so as a dependency (the tests' primitives harness) instead of mapping the regular build beside it
+subprocess.run([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(B.LIB), "-o", lib] + objs + ["-lgomp"], check=True, capture_output=True)
 print(lib)

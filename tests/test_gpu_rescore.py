@@ -116,4 +116,6 @@ def test_hamming_mode_matches_golden(ctx):
     exp = mmdb.load_keyed(os.path.join(g, "res.keyed.gz"))
     assert not diff_keys(got, exp)
     assert len(krec) > 1000
-    # other criteria: every --seq-id-mode, a coverage mode that looks at both sequences, a length threshold - against the oracle below
+    # other criteria of the Hamming mode (every --seq-id-mode, a coverage mode that looks at both sequences, a length threshold) against
+    # the oracle: tests/test_gpu_modules.py::test_hamming_mode_of_rescorediagonal_on_db_files; mode 3 under every gate and coverage mode:
+    # tests/test_gpu_rescore_directed.py
