@@ -18,6 +18,7 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -813,6 +814,17 @@ static int doCycleCheck(const std::string &seqPath, const std::string &outPath, 
 // src/assembler/ancientContigsResults.cpp:25-70.  NOT a strict weak ordering (the fall-through `return true`); the queue below is
 // libstdc++'s std::priority_queue with this very comparator, as in the reference.  Overload resolution as there (libgab.h has
 // `using namespace std`): lgamma and log of float arguments are the float functions.
+// ORACLE_CONTIG_LOG=<file> (tests): what the gate, the comparator, the queue and the rounds of a query did, one tab-separated line
+// per event, buffered per query (tlContigLog) and written out whole.  The switch changes nothing else.
+static thread_local std::string *tlContigLog = NULL;
+static thread_local uint32_t tlContigKey = 0;
+static thread_local unsigned tlContigRound = 0;
+static void contigLog(const char *fmt, ...) {
+    if (!tlContigLog) return;
+    char b[256]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
+    *tlContigLog += b;
+}
+static uint32_t floatBits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 struct CmpContigs {
     bool operator()(const Aln &r1, const Aln &r2) const {
         float mm_count1 = r1.alnLengthCons - r1.deamMatch;
@@ -830,6 +842,7 @@ struct CmpContigs {
         }
         if (p < 0.45) return true;
         if (p > 0.55) return false;
+        contigLog("C\t%u\t%u\t%u\t%a\n", tlContigKey, r1.alnLengthCons, r2.alnLengthCons, p);       // the middle zone: the lengths decide
         if (r1.alnLengthCons < r2.alnLengthCons) return true;
         if (r1.alnLengthCons > r2.alnLengthCons) return false;
         return true;
@@ -840,6 +853,7 @@ typedef std::priority_queue<Aln, std::vector<Aln>, CmpContigs> QueueContigs;
 static bool selectFragmentContigs(QueueContigs &qu, uint32_t qKey, Aln &out) {
     while (!qu.empty()) {
         Aln res = qu.top(); qu.pop();
+        contigLog("P\t%u\t%u\t%u\n", qKey, tlContigRound, res.dbKey);
         const bool notBoth = !(res.dbStartPos == 0 && res.qStartPos == 0);
         const bool rightStart = res.dbStartPos == 0 && (res.dbEndPos != static_cast<int>(res.dbLen) - 1);
         const bool leftStart = res.qStartPos == 0 && (res.qEndPos != static_cast<int>(res.qLen) - 1);
@@ -933,10 +947,12 @@ static int doContigMerge(const std::string &seqPath, const std::string &alnPath,
     DbOut out; out.init(seq.size());
     std::vector<uint8_t> wasExtended(seq.size(), 0);
     std::vector<DiNuc> D, Drev; initDeam(par.damage + "5p.prof", par.damage + "3p.prof", D, Drev);
+    FILE *eventLog = getenv("ORACLE_CONTIG_LOG") ? fopen(getenv("ORACLE_CONTIG_LOG"), "w") : NULL;
 #pragma omp parallel num_threads(par.threads)
     {
         std::vector<Aln> alns, contigs, tmpAl;
         std::vector<uint8_t> useReverse(seq.size(), 0);
+        std::string events;
 #pragma omp for schedule(dynamic, 100)
         for (size_t id = 0; id < seq.size(); id++) {
             uint32_t qKey = seq.key[id];
@@ -948,6 +964,7 @@ static int doContigMerge(const std::string &seqPath, const std::string &alnPath,
             if (aid != (size_t) UINT_MAX) parseAlns(aln.getData(aid), alns);
             bool couldExtend = false;
             QueueContigs queue;
+            if (eventLog) { events.clear(); tlContigLog = &events; tlContigKey = qKey; tlContigRound = 0; }
             for (Aln &a : alns) {  // :187-235
                 size_t tid = seq.getId(a.dbKey); unsigned tLen = seq.seqLen(tid);
                 std::string t;
@@ -973,6 +990,7 @@ static int doContigMerge(const std::string &seqPath, const std::string &alnPath,
                 minAlnLen = (c.alnLength < minAlnLen) ? std::min(minAlnLen, static_cast<unsigned>(0.2 * c.dbLen)) : minAlnLen;
                 if (c.seqId >= par.mergeSeqIdThr && c.rySeqId >= par.rySeqIdThr && c.alnLength >= minAlnLen) {
                     c.deamMatch = ancientMatchCount(c, cons, qLen, c.isRev ? Drev : D, seq);
+                    contigLog("G\t%u\t%u\t%u\t%08x\n", qKey, c.dbKey, c.alnLengthCons, floatBits(c.deamMatch));
                     queue.push(c);
                 }
             }
@@ -984,23 +1002,25 @@ static int doContigMerge(const std::string &seqPath, const std::string &alnPath,
                 while (selectFragmentContigs(queue, qKey, best)) {
                     size_t tid = seq.getId(best.dbKey);
                     const char *ts = seq.getData(tid); unsigned tLen = seq.seqLen(tid);
-                    if (best.dbStartPos == 0) { if ((tLen - (best.dbEndPos + 1)) <= rightOff) continue; }
-                    else if (best.qStartPos == 0) { if (best.dbStartPos <= static_cast<int>(leftOff)) continue; }
+                    if (best.dbStartPos == 0) { if ((tLen - (best.dbEndPos + 1)) <= rightOff) { contigLog("S\t%u\t%u\t%u\tR\t%u\t%u\n", qKey, tlContigRound, best.dbKey, tLen - (best.dbEndPos + 1), rightOff); continue; } }
+                    else if (best.qStartPos == 0) { if (best.dbStartPos <= static_cast<int>(leftOff)) { contigLog("S\t%u\t%u\t%u\tL\t%u\t%u\n", qKey, tlContigRound, best.dbKey, (unsigned) best.dbStartPos, leftOff); continue; } }
                     unsigned ds = best.dbStartPos, de = best.dbEndPos, qs = best.qStartPos, qe = best.qEndPos;
+                    if (!(ds == 0 && qe == (qLen - 1)) && !(qs == 0 && de == (tLen - 1))) contigLog("X\t%u\t%u\t%u\n", qKey, tlContigRound, best.dbKey);       // neither branch
                     if (ds == 0 && qe == (qLen - 1)) {
                         if (rightOff > 0) { tmpAl.push_back(best); continue; }
                         unsigned fragLen = tLen - (de + 1);
-                        if (query.size() + fragLen >= par.maxSeqLen) break;
+                        if (query.size() + fragLen >= par.maxSeqLen) { contigLog("B\t%u\t%u\t%u\tR\t%u\n", qKey, tlContigRound, best.dbKey, (unsigned) queue.size()); break; }
                         std::string frag = useReverse[tid] ? nuclRevFragment(ts, fragLen) : std::string(ts + de + 1, fragLen);
                         query += frag; rightOff += fragLen;
                     } else if (qs == 0 && de == (tLen - 1)) {
                         if (leftOff > 0) { tmpAl.push_back(best); continue; }
                         unsigned fragLen = ds;
-                        if (query.size() + fragLen >= par.maxSeqLen) break;
+                        if (query.size() + fragLen >= par.maxSeqLen) { contigLog("B\t%u\t%u\t%u\tL\t%u\n", qKey, tlContigRound, best.dbKey, (unsigned) queue.size()); break; }
                         std::string frag = useReverse[tid] ? nuclRevFragment(ts + (tLen - ds), fragLen) : std::string(ts, fragLen);
                         query = frag + query; leftOff += fragLen;
                     }
                 }
+                contigLog("R\t%u\t%u\t%u\t%u\t%u\t%u\n", qKey, tlContigRound, leftOff, rightOff, (unsigned) tmpAl.size(), (unsigned) queue.size());
                 if (leftOff > 0 || rightOff > 0) couldExtend = true;
                 if (!queue.empty()) break;
                 qLen = query.length(); qp = query.c_str();
@@ -1012,14 +1032,23 @@ static int doContigMerge(const std::string &seqPath, const std::string &alnPath,
                     LocalAln al = ungappedByDiagonal(qp, qLen, ts, tLen, diag);
                     updateNuclAlignment(a, al, qp, qLen, ts, tLen);
                     a.rySeqId = getRYSeqId(a, qp, ts);
-                    if (a.seqId >= par.mergeSeqIdThr && a.rySeqId >= par.rySeqIdThr) queue.push(a);
+                    const bool again = a.seqId >= par.mergeSeqIdThr && a.rySeqId >= par.rySeqIdThr;
+                    contigLog("A\t%u\t%u\t%u\t%d\t%d\t%d\t%d\t%d\t%a\t%a\t%d\n", qKey, tlContigRound, a.dbKey, diag, a.qStartPos, a.qEndPos, a.dbStartPos, a.dbEndPos, (double) a.seqId, (double) a.rySeqId, (int) again);
+                    if (again) queue.push(a);
                 }
+                tlContigRound++;
+            }
+            if (eventLog) {
+                tlContigLog = NULL;
+#pragma omp critical(contig_event_log)
+                fwrite(events.data(), 1, events.size(), eventLog);
             }
             if (couldExtend) { query.push_back('\n'); __sync_or_and_fetch(&wasExtended[id], (uint8_t) 0x20); out.set(id, qKey, query, 1); }
         }
     }
     for (size_t id = 0; id < seq.size(); id++)  // :473-487
         if (!(wasExtended[id] & 0x20)) out.set(id, seq.key[id], std::string(seq.getData(id), seq.len[id] - 1), seq.ext[id]);
+    if (eventLog) fclose(eventLog);
     out.write(outPath, seq.dbtype);
     return 0;
 }

@@ -1,7 +1,8 @@
 """A second build of the library with other compile-time geometry, for A/B runs on the GPU box (CDM_LIB=<path> selects it):
 python scripts/build_variant.py <tag> <file.hip>[,<file2.hip>...] -DX=1 ...   ->  carpedeam_amd/_variants/libcarpedeam_hip_<tag>.so
 Only the named files are recompiled (with the extra flags; name EVERY file that includes the header the macro lives in); the other
-objects are the regular build's."""
+objects are the regular build's.  <file.hip>=<path> compiles <path> - an edited copy kept outside the tree, e.g. one with a fault put
+in to see which test catches it - in the place of csrc/<file.hip>."""
 import os
 import subprocess
 import sys
@@ -15,9 +16,11 @@ B.build()
 out_dir = os.path.join(B.HERE, "_variants")
 os.makedirs(out_dir, exist_ok=True)
 mine = []
+paths = dict(s.split("=", 1) if "=" in s else (s, os.path.join(B.CSRC, s)) for s in srcs)
+srcs = list(paths)
 for src in srcs:
     obj = os.path.join(out_dir, "%s_%s.o" % (src, tag))
-    subprocess.run([B.HIPCC] + B.HIP_FLAGS + flags + ["-c", os.path.join(B.CSRC, src), "-o", obj], check=True, capture_output=True)
+    subprocess.run([B.HIPCC] + B.HIP_FLAGS + flags + ["-I" + B.CSRC, "-c", paths[src], "-o", obj], check=True, capture_output=True)
     mine.append(obj)
 objs = [os.path.join(B.OBJ, f) for f in sorted(os.listdir(B.OBJ)) if f.endswith(".o") and f[:-2] not in srcs] + mine
 lib = os.path.join(out_dir, "libcarpedeam_hip_%s.so" % tag)
