@@ -132,6 +132,11 @@ MAP_DTYPE = np.dtype([(n, "<u4") for n in ("query", "target", "pos", "columns", 
 MAP_REVERSE, MAP_SECONDARY = 1, 2
 
 
+class DedupParams(C.Structure):
+    """cdm_dedup_params: the records' identity threshold, reads only as targets"""
+    _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
+
+
 class GapParams(C.Structure):
     """cdm_gap_params: the records' identity threshold, reads only as targets, the band, the two thresholds of a rescue, the scores"""
     _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32), ("band", C.c_uint32), ("min_columns", C.c_uint32), ("min_id_permille", C.c_uint32),
@@ -185,7 +190,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_alns_dedup", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -316,6 +321,7 @@ def lib():
         l.cdm_pileup_map.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(MapParams), vp, C.POINTER(C.POINTER(MapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(C.c_float)]
         l.cdm_map_free.argtypes = [C.POINTER(MapRec), u32p]
         l.cdm_map_free.restype = None
+        l.cdm_alns_dedup.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(DedupParams), C.POINTER(vp), vp, vp, C.POINTER(C.c_float)]
         l.cdm_pileup_gapped.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(GapParams), vp, C.POINTER(C.POINTER(GapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(u32p), u64p,
                                         C.POINTER(C.c_float)]
         l.cdm_gap_free.argtypes = [C.POINTER(GapRec), u32p, u32p]
@@ -923,6 +929,22 @@ class Ctx:
             C.memmove(mism.ctypes.data, words, nw * 4)
         lib().cdm_map_free(ptr, words)
         return stats, recs, mism
+
+    def alns_dedup(self, db, alns, queries, min_seq_id=0.0, skip_extended_targets=False, keep=False):
+        """the set without the duplicate reads on the listed queries (cdm_alns_dedup) -> (Alns, stats[nq, 4] uint64: counted, kept, removed,
+        largest); with keep (Alns, stats, keep): one uint8 per record of `alns`, 1 = the record is in the new set.  self.dedup_kernel_ms
+        holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats = np.zeros((nq, 4), np.uint64)
+        flags = np.zeros(alns.count, np.uint8)
+        par = DedupParams(float(min_seq_id), int(bool(skip_extended_targets)))
+        h, ms = C.c_void_p(), C.c_float(0.0)
+        self.dedup_kernel_ms = 0.0
+        _check(lib().cdm_alns_dedup(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), C.byref(h), _ptr(stats), _ptr(flags) if keep else None, C.byref(ms)))
+        self.dedup_kernel_ms = float(ms.value)
+        out = Alns(self, h, alns.n)
+        return (out, stats, flags) if keep else (out, stats)
 
     def pileup_gapped(self, db, hits, alns, queries, par=None, records=False):
         """the reads across insertions and deletions (cdm_pileup_gapped): the banded gapped alignment of the hits of the listed queries

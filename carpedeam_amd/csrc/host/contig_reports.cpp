@@ -1,11 +1,13 @@
 // The contig reports of the host binary (none is a module of the reference): contig_damage, contig_depth, contig_variants,
-// contig_breaks, contig_map and contig_indels, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
+// contig_breaks, contig_map, contig_indels and contig_dedup, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
 // contigs.  Every report stands on one pile-up: the contigs and the reads become one DB (contigs first, wasExtended 1; reads behind
 // them, 0), kmermatcher and rescorediagonal run on it with the reads loop's flags, and a cdm_pileup_* reduction counts, per contig,
 // the overlaps of the reads that seed on it: seeded UNGAPPED overlaps at the identity threshold, not a gapped mapping; a read counts
 // on the longest sequence of each k-mer group it falls into (kmermatcher's representative rule), possibly on several contigs.
 // --gapped 1 (all but contig_damage; contig_indels always): the set keeps its hits, cdm_pileup_gapped aligns the seeded pairs that
-// test refused across insertions and deletions within a band, and the rescued reads count as well.  The tables hold integers only.
+// test refused across insertions and deletions within a band, and the rescued reads count as well.  --dedup 1 (all but contig_indels):
+// cdm_alns_dedup takes the duplicate reads out of the set before any reduction sees it; contig_dedup writes what it found.  The tables
+// hold integers only.
 #include <algorithm>
 #include <cctype>
 #include <numeric>
@@ -107,6 +109,14 @@ GapOpts gapOpts(Args &a, const char *module, const char *whatGapped) {
     g.minSeqId = fflag(a, "--min-seq-id", 0.9f);
     return g;
 }
+// --dedup 0|1 of a command.  Together with --gapped 1 it is refused: the candidates of the gapped alignment are the hits that left no
+// record in the set, so a record this flag removed would come back as a rescued read.
+bool dedupFlag(Args &a, const char *module, bool gapped) {
+    const bool on = rangedFlag(a, module, "--dedup", 0, 0, 1, "0 counts every record, 1 leaves the duplicate reads out") != 0;
+    if (on && gapped) unsupported(std::string(module) + ": --dedup 1 with --gapped 1 is not supported by the MI355X path (rescue candidates are the hits without a record, so a removed "
+                                  "record would be rescued, and rescued reads need a duplicate rule of their own)");
+    return on;
+}
 const char *const TABLE_GAPPED = "0 counts the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions";
 
 // a sequence's name, or its key where the set carries no names
@@ -126,6 +136,39 @@ struct Frame {
     // the columns every table begins with: name, key, length
     void row(std::string &to, uint64_t i) const { std::string tmp; to += name(i, tmp); put(to, set->keys[i]); put(to, lens[i]); }
 };
+
+// The set of a PileSet without the duplicate reads on the contigs (cdm_alns_dedup with what the reports pass to every reduction: reads
+// only as targets, no second identity threshold), swapped in before any reduction; stats (may be NULL): nc x 4, the contigs' statistics.
+void dedupSet(cdm_ctx *ctx, PileSet &ps, const Frame &c, uint64_t *stats) {
+    std::vector<uint64_t> own;
+    if (!stats) { own.resize(c.nc * 4); stats = own.data(); }
+    cdm_dedup_params dp; dp.min_seq_id = 0.0f; dp.skip_extended_targets = 1;
+    cdm_alns *kept = NULL; float ms = 0.f;
+    check(cdm_alns_dedup(ctx, ps.both, ps.alns, c.q.data(), c.nc, &dp, &kept, stats, NULL, &ms), "duplicate reads");
+    if (getenv("CDM_TIMING")) fprintf(stderr, "  duplicate reads: %llu records, %llu removed, dedup kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
+                                      (unsigned long long) (cdm_alns_count(ps.alns) - cdm_alns_count(kept)), ms);
+    cdm_alns_free(ps.alns);
+    ps.alns = kept;
+}
+// ---- contig_dedup: what --dedup 1 takes out of the other reports' set, cdm_alns_dedup over the contigs.  One TSV line per contig:
+// the records of its row, those that count, the groups that stay, the duplicates and the largest group.
+const FlagSpec DEDUP_FLAGS[] = {{"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// no contigs: the header line alone.  The set of ps is the one without the duplicates afterwards.
+void dedupTable(cdm_ctx *ctx, const Frame &c, PileSet &ps, const std::string &outPath, Laps &laps) {
+    std::string text = "name\tkey\tlength\trecords\tcounted\tkept\tduplicates\tlargest\n";
+    if (c.nc) {
+        std::vector<uint64_t> off(cdm_seqdb_size(ps.both) + 1), stats(c.nc * 4);
+        check(cdm_alns_download(ctx, ps.alns, off.data(), NULL), "download of the set's offsets");
+        dedupSet(ctx, ps, c, stats.data());
+        for (uint64_t i = 0; i < c.nc; i++) {
+            c.row(text, i); put(text, off[i + 1] - off[i]);
+            for (int col = 0; col < 4; col++) put(text, stats[i * 4 + col]);
+            text.push_back('\n');
+        }
+        laps.lap("duplicate report: groups, table");
+    }
+    writeOrDie(&outPath, text);
+}
 
 // The rescued reads of a PileSet that kept its hits: cdm_pileup_gapped over the contigs with nucleotide.out's scores and the gap
 // costs of `align`; candidates and gapLetters: the sums of the per-contig statistics.
@@ -190,7 +233,7 @@ std::string contigLetters(cdm_ctx *ctx, const Frame &c, std::vector<uint64_t> &a
     return letters;
 }
 // ---- contig_damage: per-contig coverage and damage tables, cdm_pileup_profile over the contigs.  One TSV line per contig.
-const FlagSpec DAMAGE_FLAGS[] = {{"--damage-ends", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+const FlagSpec DAMAGE_FLAGS[] = {{"--damage-ends", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 void damageTable(cdm_ctx *ctx, const Frame &c, const PileSet &ps, long ends, const std::string &outPath, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns";
     for (long d = 1; d <= ends; d++) { const std::string n = std::to_string(d); text += "\t5p_C_" + n + "\t5p_CT_" + n + "\t3p_G_" + n + "\t3p_GA_" + n; }
@@ -216,7 +259,7 @@ void damageTable(cdm_ctx *ctx, const Frame &c, const PileSet &ps, long ends, con
 }
 // ---- contig_depth: per-contig depth, breadth and depth variance, cdm_pileup_depth over the contigs per read set.  One TSV line per
 // contig: the caller divides (mean = sum / window, variance = (sumsq - sum^2 / window) / (window - 1)).
-const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+const FlagSpec DEPTH_FLAGS[] = {{"--depth-edge", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--depth-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 // one read set's statistics (nc x 8) and, when asked for, the depth of every contig position back to back
 void depthSample(cdm_ctx *ctx, const Frame &c, const PileSet &ps, long edge, const GapOpts &gap, std::vector<uint64_t> &stats, std::vector<uint32_t> *track) {
     stats.assign(c.nc * 8, 0);
@@ -249,7 +292,7 @@ void depthFiles(const Frame &c, const std::vector<std::vector<uint64_t>> &stats,
 // contigs with the reads' majority letter at the D positions.  No call where no read seeds.
 const FlagSpec VARIANT_FLAGS[] = {{"--min-depth", 'U', 0, 0}, {"--min-alt-count", 'U', 0, 0}, {"--min-alt-percent", 'U', 0, 0}, {"--mask-ends", 'U', 0, 0}, {"--sites", 'U', 0, 0},
                                   {"--consensus", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0},
-                                  {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+                                  {"-v", 'N', 0, 0}, {"--dedup", 'U', 0, 0}, {0, 0, 0, 0}};
 // no contigs: the summary's header line alone, an empty sites file, an empty FASTA
 void variantReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const VariantOut &v, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns\tbases\tmismatches\tcalled\tdiffers\tvariable\n", sitesText, fasta;
@@ -301,7 +344,7 @@ void variantReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const Varian
 // at their breaks, with --span-track the spanning coverage of every boundary.  Reads shorter than twice the anchor span nothing, and
 // there is no break call where no read seeds.
 const FlagSpec BREAK_FLAGS[] = {{"--break-anchor", 'U', 0, 0}, {"--break-edge", 'U', 0, 0}, {"--min-span", 'U', 0, 0}, {"--min-span-percent", 'U', 0, 0}, {"--split", 'U', 0, 0},
-                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+                                {"--min-piece", 'U', 0, 0}, {"--span-track", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 // no contigs: the summary's header line alone, an empty FASTA, an empty track
 void breakReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const BreakOut &o, Laps &laps) {
     std::string text = "name\tkey\tlength\treads\tcolumns\twindow\tweak\tbreaks\tjoins\tmin_span\tsum_span\n", fasta, bed;
@@ -357,7 +400,7 @@ void breakReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const BreakOut
 // compared it - the letters its codes and N bits stand for - so SEQ, CIGAR and MD agree by construction.  No line for a read that
 // seeds nowhere.  --gapped 1: the rescued reads come as lines of their own (CIGAR with I and D, MD with ^, a trailing
 // XG:i:<gap letters>), merged into the others by (contig, position), the ungapped line first on equal keys.
-const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
 // SAM names a reference sequence once: two contigs of one name end the command
 void mapCheckNames(const SeqSet &contigs) {
     std::vector<std::string> names; std::string tmp;
@@ -574,10 +617,13 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
         if (ask.map) mapCheckNames(*contigs);
         const bool keepHits = (ask.map && ask.map->gap.on) || ask.indels || (ask.depthOut && ask.depthGap.on) || (ask.variants && ask.variants->gap.on) || (ask.breaks && ask.breaks->gap.on);
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, keepHits);
-        const std::pair<const void *, const char *> reports[] = {{ask.damageOut, "damage"}, {ask.depthOut, "depth"}, {ask.variants, "variant"}, {ask.breaks, "break"}, {ask.indels, "indel"}, {ask.map, "map"}};
+        const std::pair<const void *, const char *> reports[] = {{ask.damageOut, "damage"}, {ask.depthOut, "depth"}, {ask.variants, "variant"}, {ask.breaks, "break"}, {ask.indels, "indel"}, {ask.map, "map"},
+                                                                 {ask.dedupOut, "duplicate"}};
         for (const auto &r : reports)       // the lap carries the name of the first report that was asked for
             if (r.first) { laps.lap((std::string(r.second) + " report: kmermatcher, rescorediagonal").c_str()); break; }
+        if (ask.dedup && !ask.dedupOut) { dedupSet(ctx, ps, c, NULL); laps.lap("duplicate reads out of the set"); }      // before any reduction
     }
+    if (ask.dedupOut) dedupTable(ctx, c, ps, *ask.dedupOut, laps);
     if (ask.damageOut) damageTable(ctx, c, ps, ask.ends, *ask.damageOut, laps);
     if (ask.depthOut) {
         std::vector<std::vector<uint64_t>> stats(1); std::vector<uint32_t> track;
@@ -593,7 +639,7 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
 }
 int contigDamage(Args &a) {
     return contigReport(a, "contig_damage", false, "Usage: carpedeam contig_damage <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--damage-ends 16] [--min-seq-id 0.9] [-k 20]", DAMAGE_FLAGS,
-                        [&](PileAsk &ask) { ask.ends = damageEnds(a, "contig_damage"); ask.damageOut = &a.pos[2]; });
+                        [&](PileAsk &ask) { ask.ends = damageEnds(a, "contig_damage"); ask.dedup = dedupFlag(a, "contig_damage", false); ask.damageOut = &a.pos[2]; });
 }
 // N read sets, each freed before the next is loaded: a column group per set in one table
 int contigDepth(Args &a) {
@@ -601,6 +647,7 @@ int contigDepth(Args &a) {
                          DEPTH_FLAGS, [&](PileAsk &ask) {
         ask.edge = depthEdge(a, "contig_depth");
         ask.depthGap = gapOpts(a, "contig_depth", TABLE_GAPPED);
+        ask.dedup = dedupFlag(a, "contig_depth", ask.depthGap.on);
         ask.depthOut = &a.pos.back(); ask.trackOut = flagPath(a, "--depth-track");
         if (ask.trackOut && a.pos.size() > 3) unsupported("contig_depth: --depth-track with " + std::to_string(a.pos.size() - 2) + " read sets is not supported by the MI355X path (the track is written for one read set)");
     }, [&](cdm_ctx *ctx, const SeqSet *contigs, PileAsk &ask, Laps &laps) {
@@ -612,6 +659,7 @@ int contigDepth(Args &a) {
             if (!loadSeqSet(ctx, a.pos[1 + s], true, false, reads)) die("contig_depth: " + a.pos[1 + s] + " holds no reads");
             PileSet ps = pileupAlignments(ctx, contigs->db, reads.db, (int) iflag(a, "-k", 20), fflag(a, "--min-seq-id", 0.9f), ask.depthGap.on);
             laps.lap("depth report: reads up, kmermatcher, rescorediagonal");
+            if (ask.dedup) dedupSet(ctx, ps, c, NULL);      // per read set: duplicates are copies within one library
             depthSample(ctx, c, ps, ask.edge, ask.depthGap, stats[s], ask.trackOut ? &track : NULL);
             freePileSet(ps); cdm_seqdb_free(reads.db);
             laps.lap("depth report: depth");
@@ -626,6 +674,7 @@ int contigVariants(Args &a) {
                         "[--sites <tsvFile>] [--consensus <fastaFile>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", VARIANT_FLAGS, [&](PileAsk &ask) {
         v.opt = variantOpts(a, "contig_variants");
         v.gap = gapOpts(a, "contig_variants", TABLE_GAPPED);
+        ask.dedup = dedupFlag(a, "contig_variants", v.gap.on);
         v.summary = &a.pos[2]; v.sites = flagPath(a, "--sites"); v.consensus = flagPath(a, "--consensus");
         ask.variants = &v;
     });
@@ -636,6 +685,7 @@ int contigBreaks(Args &a) {
                         "[--split <fastaFile>] [--min-piece 1] [--span-track <bedGraph>] [--gapped 0] [--gap-band 8] [--gap-min-columns 32] [--min-seq-id 0.9] [-k 20]", BREAK_FLAGS, [&](PileAsk &ask) {
         o.opt = breakOpts(a, "contig_breaks");
         o.gap = gapOpts(a, "contig_breaks", TABLE_GAPPED);
+        ask.dedup = dedupFlag(a, "contig_breaks", o.gap.on);
         o.minPiece = rangedFlag(a, "contig_breaks", "--min-piece", 1, 1, 1048576, "a piece that is written has 1 to 1048576 letters at the least");
         o.summary = &a.pos[2]; o.split = flagPath(a, "--split"); o.track = flagPath(a, "--span-track");
         ask.breaks = &o;
@@ -650,9 +700,15 @@ int contigMap(Args &a) {
         if (o.readGroup && (o.readGroup->empty() || o.readGroup->find('\t') != std::string::npos))
             unsupported("contig_map: --read-group \"" + *o.readGroup + "\" is not supported by the MI355X path (a read group's ID is at least one character and holds no tab)");
         o.gap = gapOpts(a, "contig_map", "0 writes the ungapped overlaps alone, 1 adds the reads rescued across insertions and deletions");
+        ask.dedup = dedupFlag(a, "contig_map", o.gap.on);
         o.sam = &a.pos[2];
         ask.map = &o;
     });
+}
+int contigDedup(Args &a) {
+    return contigReport(a, "contig_dedup", true, "Usage: carpedeam contig_dedup <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-seq-id 0.9] [-k 20] [--threads N]. "
+                        "The duplicate reads it counts are the ones that --dedup 1 leaves out of contig_damage, contig_depth, contig_variants, contig_breaks and contig_map.", DEDUP_FLAGS,
+                        [&](PileAsk &ask) { ask.dedupOut = &a.pos[2]; });
 }
 int contigIndels(Args &a) {
     IndelOut o;

@@ -44,6 +44,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_map",
                                     /* insertion and deletion sites of the contigs from the gapped records of the same pile-up: not a module of the reference either */
                                     "contig_indels",
+                                    /* the duplicate reads that --dedup 1 takes out of the same pile-up: not a module of the reference either */
+                                    "contig_dedup",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

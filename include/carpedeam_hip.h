@@ -562,6 +562,41 @@ int  cdm_pileup_map(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
 void cdm_map_free(cdm_map_rec *recs, uint32_t *mism);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Duplicate reads out of an alignment set (not a module of the reference; csrc/pileup_dedup.hip): a second set over the same DB
+ * without the PCR copies on the listed queries.  Every reduction above takes a cdm_alns, so the set this call returns reaches each of
+ * them unchanged.  The rule is DeDup's for merged reads - both ends and the strand agree - on the records a set holds.  For a listed
+ * query q of qLen letters and a record that counts under the rule of the reductions above (min_seq_id, skip_extended_targets), with
+ * the oriented form (qs, qe, ds, de; reverse when qStart > qEnd) on a target of tLen letters:
+ *   u        = qs - ds, the read's unclipped start on the query, signed: -(tLen - 1) .. qLen - 1; its unclipped end is u + tLen - 1
+ *   group    the counted records of q with equal (reverse, u, tLen)
+ *   survivor the record of a group with the largest ident, among equals the one with the smallest index in the set's record array;
+ *            every other record of the group is removed
+ * So clipping at a query's end makes no duplicates (two reads of different lengths that show the same qs..qe differ in u or tLen), a
+ * forward and a reverse record on the same coordinates both stay, and two records of one target at one place are a group like any
+ * other.  Records that do not count are never removed and displace nothing.  Rows of queries that are not listed are copied whole.
+ * The order inside every row is kept; a set without duplicates comes back equal in every byte; the call is idempotent.
+ *   out     receives a new set over the same DB, released with cdm_alns_free; `alns` is not touched.  The per-record purine/pyrimidine
+ *           counts follow their records (cdm_alns_ry_download on *out: the input's values at the kept records); a set without them
+ *           gives a set without them
+ *   stats   n_queries x 4 uint64, per listed query: 0 counted, 1 kept (the number of groups), 2 removed, 3 largest (the largest group)
+ *   keep    NULL, or one byte per record of `alns` in its order: 1 = the record is in *out, 0 = it was removed
+ *   kernel_ms  NULL, or receives the device time of the kernels
+ * A NULL argument other than keep and kernel_ms, alns of another size than db, an index-only DB, a query index >= the DB's size or
+ * listed twice is CDM_ERR_INVALID; n_queries == 0 is CDM_OK: *out is a copy of the set and nothing is launched; a set with the
+ * coordinates -1 record is refused as cdm_pileup_profile refuses it; a listed query with 2^32 records or more is CDM_ERR_UNSUPPORTED
+ * (the record slots are 32 bits wide; not reachable at test size, not tested), and so is, with n_queries > 0, a DB whose longest
+ * sequence has 2^22 letters or more (the group key holds tLen in 22 bits and u in 23; no upload refuses such a DB, cdm_kmermatch
+ * does) - refused before anything is launched, kernel_ms 0.
+ * Not covered: the reads cdm_pileup_gapped rescues (they have no record in a set), marking instead of removing, a survivor chosen
+ * by base quality (a sequence DB carries none), optical duplicates. */
+typedef struct cdm_dedup_params {
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_dedup_params;
+int  cdm_alns_dedup(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                    const cdm_dedup_params *par, cdm_alns **out, uint64_t *stats, uint8_t *keep, float *kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The reads across insertions and deletions (not a module of the reference; csrc/pileup_gapped.hip): a banded affine-gap overlap
  * alignment with traceback on the seeded pairs the ungapped test refused.  `hits` is the prefilter result `alns` was rescored from (or
  * any hit set of the same DB).  A hit (q, t, score, diagonal) of a listed query q is a CANDIDATE when t != q, t is a sequence of the
