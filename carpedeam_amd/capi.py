@@ -137,6 +137,29 @@ class DedupParams(C.Structure):
     _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32)]
 
 
+class LinksParams(C.Structure):
+    """cdm_links_params: columns an end record has on its query, read letters beyond the query's end, the most end records of a read that
+    makes pairs, the pairs of a returned link, the records' identity threshold, reads only as targets"""
+    _fields_ = [("anchor", C.c_int32), ("overhang", C.c_int32), ("max_ends", C.c_int32), ("min_reads", C.c_int32), ("min_seq_id", C.c_float),
+                ("skip_extended_targets", C.c_int32)]
+
+    @classmethod
+    def default(cls, anchor=16, overhang=1, max_ends=16, min_reads=2, min_seq_id=0.0, skip_extended_targets=False):
+        """the values `carpedeam contig_links` passes without flags (it passes skip_extended_targets = 1)"""
+        return cls(int(anchor), int(overhang), int(max_ends), int(min_reads), float(min_seq_id), int(bool(skip_extended_targets)))
+
+
+class Link(C.Structure):
+    """cdm_link: the pairs of one canonical edge (a, oA) -> (b, oB)"""
+    _fields_ = [(n, C.c_uint32) for n in ("a", "b", "info", "reads", "forward", "mode_reads")] + [(n, C.c_int32) for n in ("gap_mode", "gap_min", "gap_max", "reserved")] + [
+        ("gap_sum", C.c_int64)]
+
+
+LINK_DTYPE = np.dtype([(n, "<u4") for n in ("a", "b", "info", "reads", "forward", "mode_reads")] + [(n, "<i4") for n in ("gap_mode", "gap_min", "gap_max", "reserved")] + [
+    ("gap_sum", "<i8")])
+LINK_A_MINUS, LINK_B_MINUS = 1, 2
+
+
 class GapParams(C.Structure):
     """cdm_gap_params: the records' identity threshold, reads only as targets, the band, the two thresholds of a rescue, the scores"""
     _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32), ("band", C.c_uint32), ("min_columns", C.c_uint32), ("min_id_permille", C.c_uint32),
@@ -190,7 +213,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_alns_dedup", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_alns_dedup", "cdm_pileup_links", "cdm_link_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -322,6 +345,9 @@ def lib():
         l.cdm_map_free.argtypes = [C.POINTER(MapRec), u32p]
         l.cdm_map_free.restype = None
         l.cdm_alns_dedup.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(DedupParams), C.POINTER(vp), vp, vp, C.POINTER(C.c_float)]
+        l.cdm_pileup_links.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(LinksParams), vp, vp, C.POINTER(C.POINTER(Link)), u64p, C.POINTER(C.c_float)]
+        l.cdm_link_free.argtypes = [C.POINTER(Link)]
+        l.cdm_link_free.restype = None
         l.cdm_pileup_gapped.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(GapParams), vp, C.POINTER(C.POINTER(GapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(u32p), u64p,
                                         C.POINTER(C.c_float)]
         l.cdm_gap_free.argtypes = [C.POINTER(GapRec), u32p, u32p]
@@ -945,6 +971,30 @@ class Ctx:
         self.dedup_kernel_ms = float(ms.value)
         out = Alns(self, h, alns.n)
         return (out, stats, flags) if keep else (out, stats)
+
+    def pileup_links(self, db, alns, queries, par=None, links=False):
+        """the links between the listed queries from the reads that bridge two of their ends (cdm_pileup_links; par: LinksParams, None =
+        LinksParams.default()) -> (stats[nq, 6] uint64: reads, columns, left_ends, right_ends, both_ends, links; totals[5] uint64: end
+        records, crowded reads, self pairs, pairs in links, links before min_reads); with links (stats, totals, links): the links at
+        min_reads as an array of LINK_DTYPE, ascending by (a, oA, b, oB).  self.links_kernel_ms holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        nq = len(q)
+        stats, totals = np.zeros((nq, 6), np.uint64), np.zeros(5, np.uint64)
+        par = LinksParams.default() if par is None else par
+        ptr, n_links, ms = C.POINTER(Link)(), C.c_uint64(0), C.c_float(0.0)
+        self.links_kernel_ms = 0.0
+        _check(lib().cdm_pileup_links(self.h, db.h, alns.h, _ptr(q), nq, C.byref(par), _ptr(stats), _ptr(totals), C.byref(ptr) if links else None,
+                                      C.byref(n_links) if links else None, C.byref(ms)))
+        self.links_kernel_ms = float(ms.value)
+        if not links:
+            return stats, totals
+        n = int(n_links.value)
+        assert (n == 0) == (not ptr)
+        recs = np.empty(n, LINK_DTYPE)
+        if n:
+            C.memmove(recs.ctypes.data, ptr, n * C.sizeof(Link))
+            lib().cdm_link_free(ptr)
+        return stats, totals, recs
 
     def pileup_gapped(self, db, hits, alns, queries, par=None, records=False):
         """the reads across insertions and deletions (cdm_pileup_gapped): the banded gapped alignment of the hits of the listed queries

@@ -1,13 +1,13 @@
 // The contig reports of the host binary (none is a module of the reference): contig_damage, contig_depth, contig_variants,
-// contig_breaks, contig_map, contig_indels and contig_dedup, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
+// contig_breaks, contig_map, contig_indels, contig_dedup and contig_links, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
 // contigs.  Every report stands on one pile-up: the contigs and the reads become one DB (contigs first, wasExtended 1; reads behind
 // them, 0), kmermatcher and rescorediagonal run on it with the reads loop's flags, and a cdm_pileup_* reduction counts, per contig,
 // the overlaps of the reads that seed on it: seeded UNGAPPED overlaps at the identity threshold, not a gapped mapping; a read counts
 // on the longest sequence of each k-mer group it falls into (kmermatcher's representative rule), possibly on several contigs.
 // --gapped 1 (all but contig_damage; contig_indels always): the set keeps its hits, cdm_pileup_gapped aligns the seeded pairs that
 // test refused across insertions and deletions within a band, and the rescued reads count as well.  --dedup 1 (all but contig_indels):
-// cdm_alns_dedup takes the duplicate reads out of the set before any reduction sees it; contig_dedup writes what it found.  The tables
-// hold integers only.
+// cdm_alns_dedup takes the duplicate reads out of the set before any reduction sees it; contig_dedup writes what it found.  contig_links
+// joins a read's records on different contigs (cdm_pileup_links): which contig ends belong together.  The tables hold integers only.
 #include <algorithm>
 #include <cctype>
 #include <numeric>
@@ -71,6 +71,8 @@ BreakOpts breakOpts(Args &a, const char *module) {
 struct MapOut { const std::string *sam, *readGroup; bool primaryOnly; GapOpts gap; };
 // what an indel report writes: the summary always, the other two files when named (gap.on always: the report is about the rescued reads)
 struct IndelOut { long minDepth, minCount, minPercent; GapOpts gap; const std::string *summary, *sites, *consensus; };
+// what a link report writes: the table always, the other two files when named
+struct LinkOut { long anchor, overhang, maxEnds, minReads; const std::string *table, *ends, *gfa; };
 
 namespace {
 const char LETTER[] = "ACGTN";
@@ -401,13 +403,13 @@ void breakReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const BreakOut
 // seeds nowhere.  --gapped 1: the rescued reads come as lines of their own (CIGAR with I and D, MD with ^, a trailing
 // XG:i:<gap letters>), merged into the others by (contig, position), the ungapped line first on equal keys.
 const FlagSpec MAP_FLAGS[] = {{"--read-group", 'U', 0, 0}, {"--primary-only", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--gapped", 'U', 0, 0}, {"--gap-band", 'U', 0, 0}, {"--gap-min-columns", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
-// SAM names a reference sequence once: two contigs of one name end the command
-void mapCheckNames(const SeqSet &contigs) {
+// SAM names a reference sequence once, and so does a link: two contigs of one name end the command
+void mapCheckNames(const SeqSet &contigs, const char *module = "contig_map", const char *what = "a SAM file") {
     std::vector<std::string> names; std::string tmp;
     for (uint64_t i = 0; i < contigs.keys.size(); i++) names.push_back(seqName(contigs, i, tmp));
     std::sort(names.begin(), names.end());
     for (size_t i = 1; i < names.size(); i++)
-        if (names[i] == names[i - 1]) die("contig_map: two contigs are named " + names[i] + "; a SAM file can not tell them apart");
+        if (names[i] == names[i - 1]) die(std::string(module) + ": two contigs are named " + names[i] + "; " + what + " can not tell them apart");
 }
 // no contigs: the header lines without @SQ
 void mapReport(cdm_ctx *ctx, const Frame &c, const SeqSet *reads, const PileSet &ps, const MapOut &o, Laps &laps) {
@@ -581,6 +583,63 @@ void indelReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const IndelOut
     }
     writeOrDie(o.summary, text); writeOrDie(o.sites, sitesText); writeOrDie(o.consensus, fasta);
 }
+// ---- contig_links: which contig ends belong together, cdm_pileup_links over the contigs.  One TSV line per link: the two contigs with
+// their orientations, the reads that bridge them, those seen in the canonical direction, and the gap between the two ends (negative:
+// the overlap) as the most frequent value with its count, the minimum, the maximum and the sum.  With --ends one line per contig with its
+// end records, with --gfa the contigs as segments and the links whose most frequent gap is an overlap or 0 as L lines (GFA 1 has no
+// form for letters between two segments: those links are in the table only).  Rescued reads take no part, a contig is never linked to
+// itself, and the letters of two overlapping ends are not compared: a link is what the reads say.  The defaults are reasoned, not
+// measured: the anchor is contig_breaks'; an overhang of 1 letter is enough because a link needs the read's head record on a second
+// contig anyway; two reads keep a lone chimeric read out.
+const FlagSpec LINK_FLAGS[] = {{"--link-anchor", 'U', 0, 0}, {"--link-overhang", 'U', 0, 0}, {"--link-max-ends", 'U', 0, 0}, {"--min-link-reads", 'U', 0, 0}, {"--ends", 'U', 0, 0}, {"--gfa", 'U', 0, 0},
+                               {"--dedup", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// a signed integer behind a tab
+void putSigned(std::string &to, long long v) { to.push_back('\t'); to += std::to_string(v); }
+// no contigs: an empty table, an empty ends file, the GFA header line alone
+void linkReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const LinkOut &o, Laps &laps) {
+    std::string text, endsText, gfa = "H\tVN:Z:1.0\n";
+    if (c.nc) {
+        std::vector<uint64_t> stats(c.nc * 6); uint64_t totals[5] = {0, 0, 0, 0, 0};
+        cdm_links_params lp; lp.anchor = (int32_t) o.anchor; lp.overhang = (int32_t) o.overhang; lp.max_ends = (int32_t) o.maxEnds; lp.min_reads = (int32_t) o.minReads;
+        lp.min_seq_id = 0.0f; lp.skip_extended_targets = 1;
+        cdm_link *links = NULL; uint64_t nLinks = 0; float ms = 0.f;
+        check(cdm_pileup_links(ctx, ps.both, ps.alns, c.q.data(), c.nc, &lp, stats.data(), totals, &links, &nLinks, &ms), "pile-up links");
+        if (getenv("CDM_TIMING")) fprintf(stderr, "  link report: %llu records, %llu end records, %llu crowded reads, %llu pairs, %llu links, %llu returned, link kernels %.3f ms\n", (unsigned long long) cdm_alns_count(ps.alns),
+                                          (unsigned long long) totals[0], (unsigned long long) totals[1], (unsigned long long) totals[3], (unsigned long long) totals[4], (unsigned long long) nLinks, ms);
+        std::string tmp;
+        // nameA oA nameB oB: the four columns a table line and an L line begin with
+        auto edge = [&](std::string &to, const cdm_link &k) {
+            to += c.name(k.a, tmp); to.push_back('\t'); to.push_back(k.info & 1u ? '-' : '+'); to.push_back('\t');
+            to += c.name(k.b, tmp); to.push_back('\t'); to.push_back(k.info & 2u ? '-' : '+');
+        };
+        for (uint64_t k = 0; k < nLinks; k++) {
+            const cdm_link &l = links[k];
+            edge(text, l); put(text, l.reads); put(text, l.forward); putSigned(text, l.gap_mode); put(text, l.mode_reads); putSigned(text, l.gap_min); putSigned(text, l.gap_max); putSigned(text, l.gap_sum);
+            text.push_back('\n');
+        }
+        if (o.ends)
+            for (uint64_t i = 0; i < c.nc; i++) {
+                c.row(endsText, i);
+                for (int col = 0; col < 6; col++) put(endsText, stats[i * 6 + col]);
+                endsText.push_back('\n');
+            }
+        if (o.gfa) {        // the contigs' own bytes
+            std::vector<uint64_t> at;
+            const std::string letters = contigLetters(ctx, c, at);
+            for (uint64_t i = 0; i < c.nc; i++) {
+                gfa += "S\t"; gfa += c.name(i, tmp); gfa.push_back('\t'); gfa.append(letters, at[i], c.lens[i]); gfa += "\tLN:i:"; put(gfa, c.lens[i], false); gfa.push_back('\n');
+            }
+            for (uint64_t k = 0; k < nLinks; k++) {
+                const cdm_link &l = links[k];
+                if (l.gap_mode > 0) continue;
+                gfa += "L\t"; edge(gfa, l); put(gfa, (unsigned long long) -(long long) l.gap_mode); gfa += "M\tRC:i:"; put(gfa, l.reads, false); gfa.push_back('\n');
+            }
+        }
+        cdm_link_free(links);
+        laps.lap("link report: links, tables");
+    }
+    writeOrDie(o.table, text); writeOrDie(o.ends, endsText); writeOrDie(o.gfa, gfa);
+}
 // A contig_* command: the usage line unless the positional arguments are right (argsOk), the flag check, what the command asks for
 // from its flags (fill: every refusal, before a device is opened), the context and the contigs, then the command's read sets (body).
 template <class Fill, class Body> int contigCommand(Args &a, const char *module, bool argsOk, const char *usage, const FlagSpec *flags, Fill fill, Body body) {
@@ -615,10 +674,11 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
     PileSet ps;
     if (c.nc) {
         if (ask.map) mapCheckNames(*contigs);
+        if (ask.links) mapCheckNames(*contigs, "contig_links", "a link");
         const bool keepHits = (ask.map && ask.map->gap.on) || ask.indels || (ask.depthOut && ask.depthGap.on) || (ask.variants && ask.variants->gap.on) || (ask.breaks && ask.breaks->gap.on);
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, keepHits);
         const std::pair<const void *, const char *> reports[] = {{ask.damageOut, "damage"}, {ask.depthOut, "depth"}, {ask.variants, "variant"}, {ask.breaks, "break"}, {ask.indels, "indel"}, {ask.map, "map"},
-                                                                 {ask.dedupOut, "duplicate"}};
+                                                                 {ask.dedupOut, "duplicate"}, {ask.links, "link"}};
         for (const auto &r : reports)       // the lap carries the name of the first report that was asked for
             if (r.first) { laps.lap((std::string(r.second) + " report: kmermatcher, rescorediagonal").c_str()); break; }
         if (ask.dedup && !ask.dedupOut) { dedupSet(ctx, ps, c, NULL); laps.lap("duplicate reads out of the set"); }      // before any reduction
@@ -635,6 +695,7 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
     if (ask.breaks) breakReport(ctx, c, ps, *ask.breaks, laps);
     if (ask.map) mapReport(ctx, c, ask.mapReads, ps, *ask.map, laps);
     if (ask.indels) indelReport(ctx, c, ps, *ask.indels, laps);
+    if (ask.links) linkReport(ctx, c, ps, *ask.links, laps);
     freePileSet(ps);
 }
 int contigDamage(Args &a) {
@@ -709,6 +770,19 @@ int contigDedup(Args &a) {
     return contigReport(a, "contig_dedup", true, "Usage: carpedeam contig_dedup <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--min-seq-id 0.9] [-k 20] [--threads N]. "
                         "The duplicate reads it counts are the ones that --dedup 1 leaves out of contig_damage, contig_depth, contig_variants, contig_breaks and contig_map.", DEDUP_FLAGS,
                         [&](PileAsk &ask) { ask.dedupOut = &a.pos[2]; });
+}
+int contigLinks(Args &a) {
+    LinkOut o;
+    return contigReport(a, "contig_links", true, "Usage: carpedeam contig_links <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--link-anchor 16] [--link-overhang 1] [--link-max-ends 16] [--min-link-reads 2] "
+                        "[--ends <tsvFile>] [--gfa <gfaFile>] [--dedup 0] [--min-seq-id 0.9] [-k 20] [--threads N]", LINK_FLAGS, [&](PileAsk &ask) {
+        o.anchor = rangedFlag(a, "contig_links", "--link-anchor", 16, 1, 1024, "an end record has 1 to 1024 columns on its contig");
+        o.overhang = rangedFlag(a, "contig_links", "--link-overhang", 1, 1, 1024, "an end record's read has 1 to 1024 letters beyond the contig's end");
+        o.maxEnds = rangedFlag(a, "contig_links", "--link-max-ends", 16, 2, 64, "a read that makes links has 2 to 64 end records at the most");
+        o.minReads = rangedFlag(a, "contig_links", "--min-link-reads", 2, 1, 1000000, "a link that is written has 1 to 1000000 reads at the least");
+        ask.dedup = dedupFlag(a, "contig_links", false);
+        o.table = &a.pos[2]; o.ends = flagPath(a, "--ends"); o.gfa = flagPath(a, "--gfa");
+        ask.links = &o;
+    });
 }
 int contigIndels(Args &a) {
     IndelOut o;

@@ -46,6 +46,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_indels",
                                     /* the duplicate reads that --dedup 1 takes out of the same pile-up: not a module of the reference either */
                                     "contig_dedup",
+                                    /* the contig ends that the bridging reads of the same pile-up join: not a module of the reference either */
+                                    "contig_links",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

@@ -1,6 +1,6 @@
 // What the reductions over the read pile-up (pileup.hip: cdm_pileup_profile; pileup_depth.hip: cdm_pileup_depth and
-// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map) and cdm_alns_dedup (pileup_dedup.hip), which
-// takes the duplicate reads out of the set they reduce, share: the rule by which a record counts, the
+// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map; pileup_links.hip: cdm_pileup_links) and
+// cdm_alns_dedup (pileup_dedup.hip), which takes the duplicate reads out of the set they reduce, share: the rule by which a record counts, the
 // work items (listed query, chunk of its records) and the tiles (listed query, DP_TILE positions) with their lookups, and the host
 // steps of a call - query sizes, batch cut, work items, sliced launches, the timed synchronisation, the caller's record array - and
 // what the users of cdm_pileup_gapped's records share: the walk over a record's operations and the host's check of them.  Every step

@@ -597,6 +597,66 @@ int  cdm_alns_dedup(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
                     const cdm_dedup_params *par, cdm_alns **out, uint64_t *stats, uint8_t *keep, float *kernel_ms);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Contig links from the reads that bridge two query ends (not a module of the reference; csrc/pileup_links.hip): which ends of the
+ * listed queries belong together, in which orientation, and how many letters lie between them or by how many they overlap - the
+ * edges of the assembly graph, from the pile-up the reductions above count.  All integers.  For the listed query at list index i, of
+ * qLen letters, and a record that counts under the rule of the reductions above (min_seq_id, skip_extended_targets), with the
+ * oriented form (qs, qe, ds, de; rev when qStart > qEnd) on a target (the read) of tLen letters:
+ *   u        = qs - ds, the read's unclipped start on the query (cdm_alns_dedup's u)
+ *   L        = max(0, -u), the read letters beyond the query's left end;  R = max(0, u + tLen - qLen), those beyond its right end
+ *   cols     = qe - qs + 1
+ *   end record  cols >= anchor, and exactly one of L >= overhang (it hangs left) and R >= overhang (it hangs right); h = that L or R.
+ *            A record that hangs both ways (a read longer than its query) is counted in both_ends and otherwise ignored
+ *   tail / head  in the read's own orientation the record is a TAIL record when (hangs right) != rev, a HEAD record otherwise
+ *   o        the query's orientation on the read: + when !rev, - when rev
+ * A read's end records are those of all listed queries together (records in rows of queries that are not listed are not read: a read
+ * between a listed and an unlisted query makes no link).  A read with more than max_ends end records is CROWDED: it makes no pair.
+ * Every other read makes a PAIR from every (tail record on list index x, head record on list index y):
+ *   x == y   a self pair: counted in totals[2], nothing else (cyclecheck is the tool for circles)
+ *   x != y   the edge (x, oX) -> (y, oY) with gap = hX + hY - tLen: that many read letters between the two queries when positive,
+ *            the queries abut at 0, they overlap by -gap letters when negative
+ *   canonical form  a < b: with x < y the edge as it stands, and the pair is FORWARD; otherwise (y, flip oY) -> (x, flip oX), the same
+ *            gap - the same junction read from the other strand
+ * Every pair counts: a read seeded twice on a query counts twice, as everywhere in the pile-up.  A LINK is the set of pairs with equal
+ * canonical (a, oA, b, oB):
+ *   a, b     indices into `queries`                       info      bit 0: oA is -, bit 1: oB is -
+ *   reads    its pairs                                    forward   those that were forward
+ *   gap_min, gap_max, gap_sum   minimum, maximum and 64-bit sum of the pairs' gaps
+ *   gap_mode the gap with the most pairs, among equals the smallest;  mode_reads  the pairs with that gap;  reserved  0
+ *   links   NULL (statistics only; n_links may then be NULL as well), or receives a malloc'ed array (cdm_link_free) of the links with
+ *           reads >= min_reads, ascending by (a, oA, b, oB) with + before -; *n_links = their number; none: *links = NULL, *n_links = 0.
+ *           The array is the caller's only when the call returns CDM_OK
+ *   stats   n_queries x 6 uint64, per listed query:
+ *             0 reads, 1 columns   cdm_pileup_depth's values       2 left_ends   end records that hang left
+ *             3 right_ends         end records that hang right     4 both_ends   records that hang both ways
+ *             5 links              returned links with the query as a or b
+ *   totals  5 uint64: 0 end records, 1 crowded reads, 2 self pairs, 3 pairs that entered a link, 4 links before min_reads
+ *   kernel_ms  NULL, or receives the device time of the kernels
+ * The call is deterministic (integer sums and maxima only), and `alns` is not touched; the set cdm_alns_dedup returns is a set like
+ * any other.  anchor and overhang in 1..1024, max_ends in 2..64, min_reads in 1..1000000; anything else, a NULL argument other than
+ * links, n_links and kernel_ms, alns of another size than db, an index-only DB, a query index >= the DB's size or listed twice is
+ * CDM_ERR_INVALID; n_queries == 0 is CDM_OK (nothing is launched, the totals are 0); a set with the coordinates -1 record is refused
+ * as cdm_pileup_profile refuses it.  CDM_ERR_UNSUPPORTED, before anything is launched and with kernel_ms 0: with n_queries > 0 a DB
+ * whose longest sequence has 2^22 letters or more (an end record holds h in 22 bits, a pair its gap in 23), and more than 2^24 listed
+ * queries (a list index has 24 bits in an end record and in a link's key).  CDM_ERR_UNSUPPORTED once they are counted: a listed query
+ * with 2^32 records or more, 2^32 end records or more, 2^32 pairs or more (the places of the two sorts are 32 bits wide); none of
+ * the three is reachable at test size, none is tested.
+ * Not covered: the reads cdm_pileup_gapped rescues, links of a query with itself, a check that the letters of two overlapping ends
+ * agree - a link is what the reads say -, joining the queries' letters, paired-end distance links (the reads are merged). */
+typedef struct cdm_links_params {
+    int32_t anchor;      /* 1..1024: columns a record needs on its contig */
+    int32_t overhang;    /* 1..1024: read letters beyond the contig's end */
+    int32_t max_ends;    /* 2..64: a read with more end records makes no pair */
+    int32_t min_reads;   /* 1..1000000: the links that are returned */
+    float   min_seq_id;
+    int32_t skip_extended_targets;
+} cdm_links_params;
+typedef struct cdm_link { uint32_t a, b, info, reads, forward, mode_reads; int32_t gap_mode, gap_min, gap_max, reserved; int64_t gap_sum; } cdm_link;   /* 48 bytes */
+int  cdm_pileup_links(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                      const cdm_links_params *par, uint64_t *stats, uint64_t *totals, cdm_link **links, uint64_t *n_links, float *kernel_ms);
+void cdm_link_free(cdm_link *links);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The reads across insertions and deletions (not a module of the reference; csrc/pileup_gapped.hip): a banded affine-gap overlap
  * alignment with traceback on the seeded pairs the ungapped test refused.  `hits` is the prefilter result `alns` was rescored from (or
  * any hit set of the same DB).  A hit (q, t, score, diagonal) of a listed query q is a CANDIDATE when t != q, t is a sequence of the
