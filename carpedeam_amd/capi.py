@@ -160,6 +160,21 @@ LINK_DTYPE = np.dtype([(n, "<u4") for n in ("a", "b", "info", "reads", "forward"
 LINK_A_MINUS, LINK_B_MINUS = 1, 2
 
 
+class Junction(C.Structure):
+    """cdm_junction: a canonical link (a, oA) -> (b, oB) with one gap value"""
+    _fields_ = [(n, C.c_uint32) for n in ("a", "b", "info")] + [("gap", C.c_int32)]
+
+
+class JunctionRes(C.Structure):
+    """cdm_junction_res: what the letters say at a junction"""
+    _fields_ = [(n, C.c_uint32) for n in ("columns", "matches", "voters", "flags")] + [("fill_off", C.c_uint64)] + [(n, C.c_uint32) for n in ("fill_len", "fill_min", "fill_n", "reserved")]
+
+
+JUNCTION_DTYPE = np.dtype([(n, "<u4") for n in ("a", "b", "info")] + [("gap", "<i4")])
+JUNCTION_RES_DTYPE = np.dtype([(n, "<u4") for n in ("columns", "matches", "voters", "flags")] + [("fill_off", "<u8")] + [(n, "<u4") for n in ("fill_len", "fill_min", "fill_n", "reserved")])
+JUNCTION_CONTAINED = 1
+
+
 class GapParams(C.Structure):
     """cdm_gap_params: the records' identity threshold, reads only as targets, the band, the two thresholds of a rescue, the scores"""
     _fields_ = [("min_seq_id", C.c_float), ("skip_extended_targets", C.c_int32), ("band", C.c_uint32), ("min_columns", C.c_uint32), ("min_id_permille", C.c_uint32),
@@ -213,7 +228,7 @@ EXPORTS = [
     "cdm_rescore_hamming", "cdm_align_hits", "cdm_align_mode", "cdm_pool_headroom", "cdm_pool_stats", "cdm_env_refresh",
     "cdm_pairs_merge", "cdm_pairs_count", "cdm_pairs_entries", "cdm_pairs_bytes", "cdm_pairs_kernel_ms", "cdm_pairs_download",
     "cdm_pairs_download_stream", "cdm_pairs_to_seqdb", "cdm_pairs_free",
-    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_alns_dedup", "cdm_pileup_links", "cdm_link_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
+    "cdm_pileup_profile", "cdm_pileup_depth", "cdm_pileup_bases", "cdm_sites_free", "cdm_pileup_breaks", "cdm_breaks_free", "cdm_pileup_map", "cdm_map_free", "cdm_alns_dedup", "cdm_pileup_links", "cdm_link_free", "cdm_pileup_junctions", "cdm_junction_free", "cdm_pileup_gapped", "cdm_gap_free", "cdm_pileup_indels", "cdm_indel_free", "cdm_pileup_depth_gapped", "cdm_pileup_bases_gapped", "cdm_pileup_breaks_gapped", "cdm_seqdb_concat",
     "cdm_comm_unique_id", "cdm_comm_create_rccl", "cdm_comm_create_ops", "cdm_comm_free", "cdm_comm_rank", "cdm_comm_world", "cdm_kmermatch_dist",
     "cdm_seqdb_allgather_owned", "cdm_reads_iteration_dist", "cdm_contig_iteration_dist", "cdm_comm_owned", "cdm_comm_last_path", "cdm_kpart_gather_at", "cdm_comm_standin_group", "cdm_comm_create_standin", "cdm_kpart_set_range",
 ]
@@ -348,6 +363,9 @@ def lib():
         l.cdm_pileup_links.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(LinksParams), vp, vp, C.POINTER(C.POINTER(Link)), u64p, C.POINTER(C.c_float)]
         l.cdm_link_free.argtypes = [C.POINTER(Link)]
         l.cdm_link_free.restype = None
+        l.cdm_pileup_junctions.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(LinksParams), vp, C.c_uint64, vp, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(u32p), C.POINTER(C.c_float)]
+        l.cdm_junction_free.argtypes = [C.POINTER(C.c_uint8), u32p]
+        l.cdm_junction_free.restype = None
         l.cdm_pileup_gapped.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(GapParams), vp, C.POINTER(C.POINTER(GapRec)), u64p, C.POINTER(u32p), u64p, C.POINTER(u32p), u64p,
                                         C.POINTER(C.c_float)]
         l.cdm_gap_free.argtypes = [C.POINTER(GapRec), u32p, u32p]
@@ -995,6 +1013,29 @@ class Ctx:
             C.memmove(recs.ctypes.data, ptr, n * C.sizeof(Link))
             lib().cdm_link_free(ptr)
         return stats, totals, recs
+
+    def pileup_junctions(self, db, alns, queries, junctions, par=None, counts=False):
+        """what the letters say at the junctions (cdm_pileup_junctions; junctions: an array of JUNCTION_DTYPE, ascending by (a, oA, b, oB);
+        par: LinksParams, None = LinksParams.default(), min_reads is ignored) -> (res: JUNCTION_RES_DTYPE per junction, letters: uint8
+        ASCII ACGTN, the voted fills back to back); with counts (res, letters, counts[letters, 5] uint32: A, C, G, T, N).
+        self.junctions_kernel_ms holds the device time of the call's kernels"""
+        q = np.ascontiguousarray(queries, np.uint32).reshape(-1)
+        j = np.ascontiguousarray(junctions, JUNCTION_DTYPE).reshape(-1)
+        res = np.zeros(len(j), JUNCTION_RES_DTYPE)
+        par = LinksParams.default() if par is None else par
+        lp, cp, ms = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)(), C.c_float(0.0)
+        self.junctions_kernel_ms = 0.0
+        _check(lib().cdm_pileup_junctions(self.h, db.h, alns.h, _ptr(q), len(q), C.byref(par), _ptr(j), len(j), _ptr(res), C.byref(lp), C.byref(cp) if counts else None, C.byref(ms)))
+        self.junctions_kernel_ms = float(ms.value)
+        n = int(res["fill_len"].sum())
+        assert (n == 0) == (not lp) and (not cp or counts)
+        letters, cnt = np.empty(n, np.uint8), np.empty((n, 5), np.uint32)
+        if n:
+            C.memmove(letters.ctypes.data, lp, n)
+            if counts:
+                C.memmove(cnt.ctypes.data, cp, n * 20)
+            lib().cdm_junction_free(lp, cp)
+        return (res, letters, cnt) if counts else (res, letters)
 
     def pileup_gapped(self, db, hits, alns, queries, par=None, records=False):
         """the reads across insertions and deletions (cdm_pileup_gapped): the banded gapped alignment of the hits of the listed queries

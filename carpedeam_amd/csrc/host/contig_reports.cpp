@@ -1,5 +1,5 @@
 // The contig reports of the host binary (none is a module of the reference): contig_damage, contig_depth, contig_variants,
-// contig_breaks, contig_map, contig_indels, contig_dedup and contig_links, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
+// contig_breaks, contig_map, contig_indels, contig_dedup, contig_links and contig_join, and pileReports, which ancient_assemble_fused (host/main.cpp) calls for its final
 // contigs.  Every report stands on one pile-up: the contigs and the reads become one DB (contigs first, wasExtended 1; reads behind
 // them, 0), kmermatcher and rescorediagonal run on it with the reads loop's flags, and a cdm_pileup_* reduction counts, per contig,
 // the overlaps of the reads that seed on it: seeded UNGAPPED overlaps at the identity threshold, not a gapped mapping; a read counts
@@ -7,13 +7,15 @@
 // --gapped 1 (all but contig_damage; contig_indels always): the set keeps its hits, cdm_pileup_gapped aligns the seeded pairs that
 // test refused across insertions and deletions within a band, and the rescued reads count as well.  --dedup 1 (all but contig_indels):
 // cdm_alns_dedup takes the duplicate reads out of the set before any reduction sees it; contig_dedup writes what it found.  contig_links
-// joins a read's records on different contigs (cdm_pileup_links): which contig ends belong together.  The tables hold integers only.
+// joins a read's records on different contigs (cdm_pileup_links): which contig ends belong together; contig_join asks the letters at those
+// ends (cdm_pileup_junctions) and writes the contigs joined along the links (host/contig_join.cpp).  The tables hold integers only.
 #include <algorithm>
 #include <cctype>
 #include <numeric>
 #include <omp.h>
 #include <sys/stat.h>
 
+#include "contig_join.h"
 #include "contig_reports.h"
 
 bool loadSeqSet(cdm_ctx *ctx, const std::string &path, bool shuffle, bool wantNames, SeqSet &in) {
@@ -73,6 +75,8 @@ struct MapOut { const std::string *sam, *readGroup; bool primaryOnly; GapOpts ga
 struct IndelOut { long minDepth, minCount, minPercent; GapOpts gap; const std::string *summary, *sites, *consensus; };
 // what a link report writes: the table always, the other two files when named
 struct LinkOut { long anchor, overhang, maxEnds, minReads; const std::string *table, *ends, *gfa; };
+// what a join report writes: the table always, the other two files when named
+struct JoinOut { long anchor, overhang, maxEnds, minLinkReads, overlapPercent; const std::string *table, *joined, *paths; };
 
 namespace {
 const char LETTER[] = "ACGTN";
@@ -640,6 +644,48 @@ void linkReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const LinkOut &
     }
     writeOrDie(o.table, text); writeOrDie(o.ends, endsText); writeOrDie(o.gfa, gfa);
 }
+// ---- contig_join: the contigs joined along their links.  contig_links' chain, then every returned link gets one decision (host/contig_join.h:
+// A ambiguous, W weak, C contained, X the letters disagree, S short, O circle, J joined): cdm_pileup_links returns the links contig_links
+// writes (min_reads is --min-link-reads: a lone chimeric read makes no end ambiguous), the links that pass A, W and C are the junctions of
+// cdm_pileup_junctions with gap = gap_mode, and the paths of J links are written as one record each.  --join-overlap-percent 90 is reasoned,
+// not measured: it is the identity the bridging reads themselves had to pass at --min-seq-id 0.9.
+const FlagSpec JOIN_FLAGS[] = {{"--link-anchor", 'U', 0, 0}, {"--link-overhang", 'U', 0, 0}, {"--link-max-ends", 'U', 0, 0}, {"--min-link-reads", 'U', 0, 0}, {"--joined", 'U', 0, 0}, {"--paths", 'U', 0, 0},
+                               {"--join-overlap-percent", 'U', 0, 0}, {"--dedup", 'U', 0, 0}, {"--min-seq-id", 'U', 0, 0}, {"-k", 'U', 0, 0}, {"--threads", 'N', 0, 0}, {"-v", 'N', 0, 0}, {0, 0, 0, 0}};
+// no contigs: three empty files
+void joinReport(cdm_ctx *ctx, const Frame &c, const PileSet &ps, const JoinOut &o, Laps &laps) {
+    std::string text, fasta, pathsText;
+    if (c.nc) {
+        std::vector<uint64_t> stats(c.nc * 6); uint64_t totals[5] = {0, 0, 0, 0, 0};
+        cdm_links_params lp; lp.anchor = (int32_t) o.anchor; lp.overhang = (int32_t) o.overhang; lp.max_ends = (int32_t) o.maxEnds; lp.min_reads = (int32_t) o.minLinkReads;
+        lp.min_seq_id = 0.0f; lp.skip_extended_targets = 1;
+        cdm_link *links = NULL; uint64_t nLinks = 0; float linkMs = 0.f, ms = 0.f;
+        check(cdm_pileup_links(ctx, ps.both, ps.alns, c.q.data(), c.nc, &lp, stats.data(), totals, &links, &nLinks, &linkMs), "pile-up links");
+        JoinPlan plan;
+        joinFirst(links, nLinks, c.lens, o.minLinkReads, plan);
+        std::vector<cdm_junction_res> res(plan.juncs.size());
+        uint8_t *fills = NULL;
+        check(cdm_pileup_junctions(ctx, ps.both, ps.alns, c.q.data(), c.nc, &lp, plan.juncs.data(), plan.juncs.size(), res.data(), &fills, NULL, &ms), "pile-up junctions");
+        if (getenv("CDM_TIMING")) {
+            unsigned long long voters = 0, letters = 0;
+            for (const cdm_junction_res &r : res) { voters += r.voters; letters += r.fill_len; }
+            fprintf(stderr, "  join report: %llu links, %llu junctions, %llu voters, %llu fill letters, link kernels %.3f ms, junction kernels %.3f ms\n", (unsigned long long) nLinks,
+                    (unsigned long long) res.size(), voters, letters, linkMs, ms);
+        }
+        joinDecide(links, nLinks, c.lens, res.data(), fills, o.overlapPercent, plan);
+        std::vector<std::string> names(c.nc); std::string tmp;
+        for (uint64_t i = 0; i < c.nc; i++) names[i] = c.name(i, tmp);
+        std::vector<uint64_t> at; std::string letters;
+        if (o.joined) letters = contigLetters(ctx, c, at);
+        const JoinContigs jc = {&names, &letters, &at, &c.lens};
+        text = joinTable(jc, links, nLinks, res.data(), plan);
+        if (o.joined) fasta = joinFasta(jc, plan);
+        if (o.paths) pathsText = joinPaths(jc, plan);
+        cdm_junction_free(fills, NULL);
+        cdm_link_free(links);
+        laps.lap("join report: links, junctions, paths");
+    }
+    writeOrDie(o.table, text); writeOrDie(o.joined, fasta); writeOrDie(o.paths, pathsText);
+}
 // A contig_* command: the usage line unless the positional arguments are right (argsOk), the flag check, what the command asks for
 // from its flags (fill: every refusal, before a device is opened), the context and the contigs, then the command's read sets (body).
 template <class Fill, class Body> int contigCommand(Args &a, const char *module, bool argsOk, const char *usage, const FlagSpec *flags, Fill fill, Body body) {
@@ -675,10 +721,11 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
     if (c.nc) {
         if (ask.map) mapCheckNames(*contigs);
         if (ask.links) mapCheckNames(*contigs, "contig_links", "a link");
+        if (ask.join) mapCheckNames(*contigs, "contig_join", "a join");
         const bool keepHits = (ask.map && ask.map->gap.on) || ask.indels || (ask.depthOut && ask.depthGap.on) || (ask.variants && ask.variants->gap.on) || (ask.breaks && ask.breaks->gap.on);
         ps = pileupAlignments(ctx, contigs->db, reads, kmerSize, minSeqId, keepHits);
         const std::pair<const void *, const char *> reports[] = {{ask.damageOut, "damage"}, {ask.depthOut, "depth"}, {ask.variants, "variant"}, {ask.breaks, "break"}, {ask.indels, "indel"}, {ask.map, "map"},
-                                                                 {ask.dedupOut, "duplicate"}, {ask.links, "link"}};
+                                                                 {ask.dedupOut, "duplicate"}, {ask.links, "link"}, {ask.join, "join"}};
         for (const auto &r : reports)       // the lap carries the name of the first report that was asked for
             if (r.first) { laps.lap((std::string(r.second) + " report: kmermatcher, rescorediagonal").c_str()); break; }
         if (ask.dedup && !ask.dedupOut) { dedupSet(ctx, ps, c, NULL); laps.lap("duplicate reads out of the set"); }      // before any reduction
@@ -696,6 +743,7 @@ void pileReports(cdm_ctx *ctx, const SeqSet *contigs, cdm_seqdb *reads, int kmer
     if (ask.map) mapReport(ctx, c, ask.mapReads, ps, *ask.map, laps);
     if (ask.indels) indelReport(ctx, c, ps, *ask.indels, laps);
     if (ask.links) linkReport(ctx, c, ps, *ask.links, laps);
+    if (ask.join) joinReport(ctx, c, ps, *ask.join, laps);
     freePileSet(ps);
 }
 int contigDamage(Args &a) {
@@ -782,6 +830,20 @@ int contigLinks(Args &a) {
         ask.dedup = dedupFlag(a, "contig_links", false);
         o.table = &a.pos[2]; o.ends = flagPath(a, "--ends"); o.gfa = flagPath(a, "--gfa");
         ask.links = &o;
+    });
+}
+int contigJoin(Args &a) {
+    JoinOut o;
+    return contigReport(a, "contig_join", true, "Usage: carpedeam contig_join <i:contigs DB|fast(a|q)[.gz]> <i:reads DB|fast(a|q)[.gz]> <o:tsvFile> [--joined <fastaFile>] [--paths <tsvFile>] [--join-overlap-percent 90] "
+                        "[--link-anchor 16] [--link-overhang 1] [--link-max-ends 16] [--min-link-reads 2] [--dedup 0] [--min-seq-id 0.9] [-k 20] [--threads N]", JOIN_FLAGS, [&](PileAsk &ask) {
+        o.overlapPercent = rangedFlag(a, "contig_join", "--join-overlap-percent", 90, 0, 100, "a percentage of the overlap's columns is 0 to 100");
+        o.anchor = rangedFlag(a, "contig_join", "--link-anchor", 16, 1, 1024, "an end record has 1 to 1024 columns on its contig");
+        o.overhang = rangedFlag(a, "contig_join", "--link-overhang", 1, 1, 1024, "an end record's read has 1 to 1024 letters beyond the contig's end");
+        o.maxEnds = rangedFlag(a, "contig_join", "--link-max-ends", 16, 2, 64, "a read that makes links has 2 to 64 end records at the most");
+        o.minLinkReads = rangedFlag(a, "contig_join", "--min-link-reads", 2, 1, 1000000, "a link that is written has 1 to 1000000 reads at the least");
+        ask.dedup = dedupFlag(a, "contig_join", false);
+        o.table = &a.pos[2]; o.joined = flagPath(a, "--joined"); o.paths = flagPath(a, "--paths");
+        ask.join = &o;
     });
 }
 int contigIndels(Args &a) {

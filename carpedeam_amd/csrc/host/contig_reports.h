@@ -1,4 +1,4 @@
-// host/contig_reports.cpp: the eight contig_* commands, and what ancient_assemble_fused (host/main.cpp) needs to write the same reports
+// host/contig_reports.cpp: the nine contig_* commands, and what ancient_assemble_fused (host/main.cpp) needs to write the same reports
 // for its final contigs - the sequence loader, the option parsers under its own module name, PileAsk and pileReports.
 #pragma once
 #include "cli.h"
@@ -11,6 +11,7 @@ int contigMap(Args &a);
 int contigIndels(Args &a);
 int contigDedup(Args &a);
 int contigLinks(Args &a);
+int contigJoin(Args &a);
 
 // a set of sequences on the device with the names and keys its report lines carry
 struct SeqSet { cdm_seqdb *db = NULL; std::vector<std::string> names; std::vector<uint32_t> keys; };
@@ -33,9 +34,10 @@ struct BreakOut { BreakOpts opt; long minPiece; const std::string *summary, *spl
 struct MapOut;
 struct IndelOut;
 struct LinkOut;
+struct JoinOut;
 // What a pileReports call is asked for (NULL: not asked for): the damage table with its ends, the depth table with its edge and
 // track, the variant, the break and the indel reports, the map report with the read set whose names and letters its lines carry, the
-// duplicate table, the link report.  dedup: the duplicate reads (cdm_alns_dedup over the contigs) leave the set before any reduction sees it.
+// duplicate table, the link report, the join report.  dedup: the duplicate reads (cdm_alns_dedup over the contigs) leave the set before any reduction sees it.
 struct PileAsk {
     bool dedup = false; const std::string *dedupOut = NULL;
     const std::string *damageOut = NULL; long ends = 0;
@@ -44,6 +46,7 @@ struct PileAsk {
     const MapOut *map = NULL; const SeqSet *mapReads = NULL;
     const IndelOut *indels = NULL;
     const LinkOut *links = NULL;
+    const JoinOut *join = NULL;
 };
 // The reports of one read set against one set of contigs: kmermatcher and rescorediagonal once, then each reduction that was asked
 // for on the same alignment set.  contigs == NULL: the header lines alone.  Neither DB is freed here.

@@ -48,6 +48,8 @@ static const char *const OWNED[] = {"kmermatcher", "rescorediagonal", "ancient_c
                                     "contig_dedup",
                                     /* the contig ends that the bridging reads of the same pile-up join: not a module of the reference either */
                                     "contig_links",
+                                    /* the contigs joined along those links, with the letters of the same pile-up's reads between them: not a module of the reference either */
+                                    "contig_join",
                                     /* the host-side modules of linclust's tail and the scripts' file modules (host/cluster.cpp) */
                                     "clust", "createsubdb", "filterdb", "mergeclusters", "result2repseq", "rmdb", "mvdb", "align", NULL};
 

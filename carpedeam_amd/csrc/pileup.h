@@ -1,5 +1,5 @@
 // What the reductions over the read pile-up (pileup.hip: cdm_pileup_profile; pileup_depth.hip: cdm_pileup_depth and
-// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map; pileup_links.hip: cdm_pileup_links) and
+// cdm_pileup_breaks; pileup_bases.hip: cdm_pileup_bases; pileup_map.hip: cdm_pileup_map; pileup_links.hip: cdm_pileup_links; pileup_junctions.hip: cdm_pileup_junctions) and
 // cdm_alns_dedup (pileup_dedup.hip), which takes the duplicate reads out of the set they reduce, share: the rule by which a record counts, the
 // work items (listed query, chunk of its records) and the tiles (listed query, DP_TILE positions) with their lookups, and the host
 // steps of a call - query sizes, batch cut, work items, sliced launches, the timed synchronisation, the caller's record array - and

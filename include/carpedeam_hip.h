@@ -641,8 +641,9 @@ int  cdm_alns_dedup(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, con
  * queries (a list index has 24 bits in an end record and in a link's key).  CDM_ERR_UNSUPPORTED once they are counted: a listed query
  * with 2^32 records or more, 2^32 end records or more, 2^32 pairs or more (the places of the two sorts are 32 bits wide); none of
  * the three is reachable at test size, none is tested.
- * Not covered: the reads cdm_pileup_gapped rescues, links of a query with itself, a check that the letters of two overlapping ends
- * agree - a link is what the reads say -, joining the queries' letters, paired-end distance links (the reads are merged). */
+ * Not covered: the reads cdm_pileup_gapped rescues, links of a query with itself, paired-end distance links (the reads are merged).
+ * A link is what the reads say: whether the letters of two overlapping ends agree, and the letters between two ends, are
+ * cdm_pileup_junctions' (below), and `carpedeam contig_join` joins the queries' letters along the links. */
 typedef struct cdm_links_params {
     int32_t anchor;      /* 1..1024: columns a record needs on its contig */
     int32_t overhang;    /* 1..1024: read letters beyond the contig's end */
@@ -655,6 +656,52 @@ typedef struct cdm_link { uint32_t a, b, info, reads, forward, mode_reads; int32
 int  cdm_pileup_links(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
                       const cdm_links_params *par, uint64_t *stats, uint64_t *totals, cdm_link **links, uint64_t *n_links, float *kernel_ms);
 void cdm_link_free(cdm_link *links);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * What the letters say at a junction (not a module of the reference; csrc/pileup_junctions.hip): the letters of two overlapping query
+ * ends compared, or the letters between two ends voted from the reads that bridge them.  A JUNCTION is a canonical link of
+ * cdm_pileup_links with ONE gap value: a < b are indices into `queries`, info bit 0: oA is -, bit 1: oB is - (cdm_link's convention).
+ * The junctions ascend strictly by (a, oA, b, oB), + before -.  ctx, db, alns, queries, n_queries and par are cdm_pileup_links' own;
+ * par->min_reads is ignored.  All integers.  The ORIENTED form of a query is the query for +, its reverse complement for - (the 2-bit
+ * code c becomes 3 - c, an N stays N); the link reads: oriented A, then oriented B.  With lenA and lenB the two queries' lengths:
+ *   gap < 0   an overlap of k = -gap letters.  k > min(lenA, lenB): the junction is CONTAINED - columns = 0, matches = 0, flags bit 0
+ *             (CDM_JUNCTION_CONTAINED).  Otherwise columns = k and matches = the j < k at which oriented A[lenA - k + j] and oriented
+ *             B[j] are the same base and neither is N (an N on either side is a mismatch, as in cdm_pileup_map's NM)
+ *   gap > 0   a fill of gap letters.  The VOTERS are the pairs of cdm_pileup_links' rule (same end records, same crowded reads, every
+ *             pair counts) whose canonical edge is the junction's and whose gap is the junction's.  A pair of a tail record with hX
+ *             and a head record with hY of a read of tLen letters has the letters read[tLen - hX .. hY) between the two queries -
+ *             gap letters, in the read's own orientation.  A forward pair (x < y) gives them as they stand, a pair that needed the
+ *             flip their reverse complement.  Per offset 0 .. gap-1 five 32-bit counts: A, C, G, T, N.  The voted letter is the base
+ *             with the largest count, the lowest code among equals; N where no voter has a base there (cdm_pileup_indels' rule for
+ *             inserted letters).  The offset's WINNING COUNT is that largest base count (0 where the letter is N)
+ *   gap == 0  nothing to compare, nothing to vote
+ * res, one cdm_junction_res per junction:
+ *   columns, matches   as above (0 unless gap < 0)       flags    bit 0 contained         reserved  0
+ *   voters    the pairs of the junction's edge with the junction's gap, whatever its sign: for a junction made of a returned link
+ *             with gap = gap_mode it is the link's mode_reads
+ *   fill_off, fill_len   the junction's letters in `letters` (fill_len = gap for gap > 0, else 0; fill_off = the sum of the fill_len in front)
+ *   fill_min  the smallest winning count over the fill's offsets, 0 without a fill         fill_n   the offsets voted N
+ *   letters   receives a malloc'ed array of sum(fill_len) bytes, ASCII ACGTN (NULL where that is 0)
+ *   counts    NULL, or receives a malloc'ed array of sum(fill_len) x 5 uint32: A, C, G, T, N per letter (NULL where that is 0)
+ *             Both arrays are the caller's only when the call returns CDM_OK, and go back through cdm_junction_free
+ *   kernel_ms NULL, or receives the device time of the kernels
+ * The call is deterministic (integer sums, minima and maxima only: two calls give byte-equal arrays), and `alns` is not touched.
+ * CDM_ERR_INVALID: a NULL argument other than counts and kernel_ms (junctions and res may be NULL with n_junctions == 0, queries with
+ * n_queries == 0), anchor, overhang or max_ends out of cdm_pileup_links' ranges, a >= b, b >= n_queries, info > 3, junctions out of
+ * order or repeated, and what cdm_pileup_links refuses about db, alns and queries.  CDM_ERR_UNSUPPORTED, before anything is launched
+ * and with kernel_ms 0: a DB whose longest sequence has 2^22 letters or more, more than 2^24 listed queries (cdm_pileup_links' two),
+ * 2^32 junctions or more, |gap| >= 2^22 (no pair has such a gap), and more than 2^26 fill letters in all - reasoned from the 20 bytes of counters a letter
+ * takes, not measured.  CDM_ERR_UNSUPPORTED once they are counted, as in cdm_pileup_links: a listed query with 2^32 records or more, 2^32
+ * end records or more (not reachable at test size, not tested).  n_queries == 0 or n_junctions == 0 is CDM_OK: nothing is launched.
+ * Not covered: the reads cdm_pileup_gapped rescues, a gapped comparison of the two ends (an overlap with an insertion shows as
+ * mismatches), quality-weighted votes. */
+#define CDM_JUNCTION_CONTAINED 1u
+typedef struct cdm_junction { uint32_t a, b, info; int32_t gap; } cdm_junction;      /* 16 bytes */
+typedef struct cdm_junction_res { uint32_t columns, matches, voters, flags; uint64_t fill_off; uint32_t fill_len, fill_min, fill_n, reserved; } cdm_junction_res;   /* 40 bytes */
+int  cdm_pileup_junctions(cdm_ctx *ctx, const cdm_seqdb *db, const cdm_alns *alns, const uint32_t *queries, uint64_t n_queries,
+                          const cdm_links_params *par, const cdm_junction *junctions, uint64_t n_junctions, cdm_junction_res *res,
+                          uint8_t **letters, uint32_t **counts, float *kernel_ms);
+void cdm_junction_free(uint8_t *letters, uint32_t *counts);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The reads across insertions and deletions (not a module of the reference; csrc/pileup_gapped.hip): a banded affine-gap overlap
